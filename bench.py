@@ -5,10 +5,13 @@ A "step" is one Langevin denoising step (score-network forward + update, dualenc
 synthetic GEOM-Drugs-shaped conformers.  `value` = conformers generated per second by a 5000-step sampling job =
 G_total / (ms_per_step * 5000 / 1000), whole job over all ranks, inputs resident in HBM when the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
       N > 1 without a launcher: this process never touches a GPU; it starts N fresh rank processes (one per GPU, RCCL over
       127.0.0.1) and relays rank 0's JSON line.  Under `python -m torch.distributed.run --nproc-per-node N` (the driver's
       form) RANK / LOCAL_RANK / WORLD_SIZE come from the environment.
+      A plain run measures the headline alone (with the in-step CFConv roofline of its timed steps).  --full adds the CPU
+      baseline, the runs reported under `extra` and the stand-alone CFConv aggregate roofline.  --dump-outputs DIR writes
+      the positions the timed steps computed (every batch's after its last step) to DIR/pos.npy, float32.
 
 Workloads:
   drugs200 (default)  BASELINE.json configs[2] as SURVEY §8(d) restates it (scripts/test.py:40-61,130-141): 200 Drugs-shaped
@@ -16,8 +19,8 @@ Workloads:
                    every batch runs --warmup + --steps steps; ms_per_step = one step of EVERY batch, value = all conformers
                    / (that x 5000).  "saturated" schedule (beta_end = 2e-5: sigma < 0.5 on every step, so the global SchNet
                    branch runs on every step and the radius graph stays at the 32-neighbour cap -- the heaviest per-step
-                   work the path can see) is the headline; `extra` carries the reference's default schedule with and without
-                   skipping the discarded global branch, and the filter-polynomial fallback (--radius-poly off), each on
+                   work the path can see) is the headline; `extra` (--full) carries the reference's default schedule with and
+                   without skipping the discarded global branch, and the filter-polynomial fallback (--radius-poly off), each on
                    every 4th batch.
   drugs            `--mols` distinct molecules x `--copies` conformers each in ONE batch per GPU (round 1-2 headline: 8 x 128)
   qm9 | large | alanine   QM9-shaped, 200-atom molecules (configs[4] shape), alanine dipeptide (configs[0]).
@@ -306,11 +309,12 @@ def timed_run(model, dev, b, cfg, W, K, schedule, skip, save_traj, seed, rank, u
 
 
 def run_job_steps(mdl, mcfg, batches, confs_of, schedule, sk, W_, K_, prof, *, dev, rank, world, seed, save_traj, use_dist, strong,
-                  every=1, gcalls=None, tile_acc=None, timed=None, edges_of=None, tiles_of=None):
+                  every=1, gcalls=None, tile_acc=None, timed=None, edges_of=None, tiles_of=None, outputs=None):
     """W_ + K_ denoising steps of every `every`-th packed batch of the job on this rank: (ms of one step summed over the batches,
     conformers, records, global-branch share, last run, CFConv profile sums).  With `use_dist` the ranks' positions (+ NaN
     flag) are all-gathered after EVERY step of every batch -- north_star's collective, weak and strong scaling alike (strong:
     every batch is first cut into per-rank graph ranges); the number of collectives is asserted: one per step.
+    `outputs`: a list that receives every timed batch's positions after its last step (host copies, taken after the timing).
     `timed` / `edges_of` / `tiles_of`: stand-ins for timed_run / live_edges / tile_stats (tests/test_dist_cpu.py runs this
     function with a CPU sampler stub over gloo)."""
     import torch
@@ -343,6 +347,8 @@ def run_job_steps(mdl, mcfg, batches, confs_of, schedule, sk, W_, K_, prof, *, d
         el, run, gfrac, gather, pr = timed(mdl, dev, b, mcfg, W_, K_, schedule, sk, save_traj, seed + bidx, rank, use_dist,
                                            profile=prof)
         run.check_nan()
+        if outputs is not None:
+            outputs.append(run.pos.detach().to("cpu"))
         if use_dist:
             assert gather is not None and gather.calls == W_ + K_, "one all-gather per denoising step"
             gcalls[0] += gather.calls
@@ -420,6 +426,22 @@ def load_pmc(precision, edges, kernels):
     return tj
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  When they hold more than `limit` bytes together, each keeps
+    the same seeded sample of its rows (sorted; the same rows for the same shapes, so that two builds compare output for output)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (limit / float(total))) - 1)
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     global JOB_STEPS
     ap = argparse.ArgumentParser()
@@ -436,8 +458,14 @@ def main():
                          "per-rank graph ranges, as agdiff_amd.driver shards it --, so that a scaling run measures the sharding and "
                          "the per-step all-gather on FIXED total work; weak: every rank samples its own copy of the job")
     ap.add_argument("--no-skip", action="store_true", help="run the global encoder even where its result is discarded")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the runs reported under `extra`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the CPU baseline, the runs reported under `extra` and the "
+                         "stand-alone CFConv aggregate roofline (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they computed to DIR/<name>.npy (float32): pos = every timed batch's "
+                         "positions after its last step, in batch order (pos_rank<r> per rank with more than one)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the runs reported under `extra`")
     ap.add_argument("--no-traj", action="store_true")
     ap.add_argument("--no-attr-far", action="store_true", help="local edges beyond the cutoff through the encoder MLP instead of their "
                                                                "far polynomials (A/B runs)")
@@ -505,7 +533,7 @@ def main():
 
     # The CPU leg runs first, in separate interpreter processes, before this process initialises the GPU.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(kind, args.schedule, args.seed)
 
     import torch
@@ -516,6 +544,9 @@ def main():
         raise SystemExit("rank %d: LOCAL_RANK %d but only %d GPU(s) visible" % (rank, local_rank, torch.cuda.device_count()))
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
+    # the sampler draws its Langevin noise from the default generators, whose initial seed need not be the same in every process:
+    # seeded here, so that the same arguments give the same inputs, noise included, in every run
+    torch.manual_seed(args.seed + rank)
     use_dist = world > 1 or args.force_dist
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -576,10 +607,12 @@ def main():
     gcalls = [0]          # all-gathers this rank issued in run_job (one per step per batch)
     tile_acc = {}         # tile statistics of the profiled CFConv launches (weighted by launches)
 
-    def run_job(mdl, mcfg, batches, confs_of, schedule, sk, W_, K_, prof, every=1, dist_here=True):
+    outputs = [] if args.dump_outputs else None       # positions after the last timed step of every batch (--dump-outputs)
+
+    def run_job(mdl, mcfg, batches, confs_of, schedule, sk, W_, K_, prof, every=1, dist_here=True, outputs=None):
         return run_job_steps(mdl, mcfg, batches, confs_of, schedule, sk, W_, K_, prof, every=every, dev=dev, rank=rank, world=world,
                              seed=args.seed, save_traj=save_traj, use_dist=use_dist and dist_here, strong=strong, gcalls=gcalls,
-                             tile_acc=tile_acc)
+                             tile_acc=tile_acc, outputs=outputs)
 
     def reduce_job(tot_ms, G_local, G_all_if_strong):
         tt = torch.tensor([tot_ms], dtype=torch.float64, device=dev)
@@ -600,7 +633,7 @@ def main():
         batches = driver.plan_batches(mols200, confs_of, driver.sharded_capacity(args.max_atoms, world) if strong else args.max_atoms)
         G_job = sum(confs_of(m["num_refs"]) for m in mols200)
         tot_ms, G_local, per_batch, global_frac, run, (prof_ms, prof_n, prof_flop, prof_edges) = run_job(
-            model, cfg, batches, confs_of, args.schedule, skip, W, K, profile)
+            model, cfg, batches, confs_of, args.schedule, skip, W, K, profile, outputs=outputs)
         # whole job = every rank works through its batches one after the other: time = max over ranks of its sum
         ms_per_step, G_total = reduce_job(tot_ms, G_local, G_job)      # ms for ONE step of EVERY batch of the slowest rank
         value = G_total / (ms_per_step * JOB_STEPS / 1e3)
@@ -624,6 +657,8 @@ def main():
         el, run, global_frac, gather, pr = timed_run(model, dev, b, cfg, W, K, args.schedule, skip, save_traj, args.seed,
                                                      rank, use_dist, profile=profile)
         G = b["num_graphs"]
+        if outputs is not None:
+            outputs.append(run.pos.detach().to("cpu"))
         if pr is not None and pr[1] > 0:
             E_b = live_edges(run)
             prof_ms, prof_n, prof_flop, prof_edges = pr[0], pr[1], float(E_b) * FLOP_PER_EDGE_CFCONV * pr[1], float(E_b) * pr[1]
@@ -652,6 +687,8 @@ def main():
               % (kind, mols, copies, "in ONE global batch cut into per-rank graph ranges" if strong
                  else "per GPU", run.topo.N, live_edges(run), run.topo.L, args.schedule, 100 * global_frac,
                  JOB_STEPS))
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, {"pos" if world == 1 else "pos_rank%d" % rank: torch.cat(outputs).numpy()})
 
     # ---- dominant operation = the two CFConvs of one InteractionBlock (encoder/schnet.py:136-162, 12 per forward).  With the
     # filter polynomials on it is ONE launch (k_cfconv_node: radius rows + local quad tiles per quad of targets), else one
@@ -764,9 +801,10 @@ def main():
                 "note": note}
 
     # ---- stand-alone CFConv aggregate (PyG propagate x_j * W, schnet.py:156-162) on the last batch's graph: the HBM-bound
-    # "scatter" kernel BASELINE.json's north_star prices against the HBM roofline (unfused form: W[E,F] streamed)
+    # "scatter" kernel BASELINE.json's north_star prices against the HBM roofline (unfused form: W[E,F] streamed); with --full
+    # (and --breakdown, whose per-op timings start from the graph this builds)
     agg_roof = None
-    if E > 0 and rank == 0:
+    if E > 0 and rank == 0 and (args.full or args.breakdown):
         F = 128
         if run._fused_front():      # (the sampler kept radius rows only: the full destination-sorted list of the same positions)
             lib.agdiff_graph_build(T_, W_, run.pos_p, ctypes.c_float(cfg.cutoff), stream)
@@ -923,7 +961,7 @@ def main():
                                      / (pms * 1e-3) / 1e12 / PEAK[args.precision]) if pn else None}
 
     extra, value_full_job = None, None
-    if rank == 0 and world == 1 and not args.no_extra and args.schedule == "saturated" and kind != "alanine":
+    if rank == 0 and world == 1 and args.full and not args.no_extra and args.schedule == "saturated" and kind != "alanine":
         del run
         Ke, We = min(K, 200), min(W, 10)
         every = 4 if d200 else 1

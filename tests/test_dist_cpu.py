@@ -316,6 +316,42 @@ def test_bench_job_loop_world8_gloo():
     assert sum(out[r][1] for r in range(8)) == sum(2 * (2 + i) for i in range(6))
 
 
+def test_bench_job_loop_outputs_and_dump(tmp_path):
+    """bench.py --dump-outputs: run_job_steps hands every batch's positions after its last step to `outputs`, in batch order;
+    dump_outputs writes them as float32 .npy, and above its byte limit the same seeded sample of rows on every call."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    from agdiff_amd import driver
+    rng = np.random.default_rng(5)
+    mols = []
+    for i in range(6):
+        at_, r_, c_, t_ = synth.random_molecule(rng, synth.sample_n_atoms(rng, "qm9"))
+        mols.append(dict(atom_type=at_, edge_index=np.stack([r_, c_]), edge_type=t_, num_refs=2 + i, name="m%d" % i, index=i))
+    confs_of = driver.num_confs("2x")
+    batches = driver.plan_batches(mols, confs_of, 400)
+    assert len(batches) >= 2
+    outputs = []
+    W, K = 2, 5
+    _, _, recs, _, _, _ = bench.run_job_steps(
+        None, None, batches, confs_of, "saturated", True, W, K, False, dev="cpu", rank=0, world=1, seed=11, save_traj=False,
+        use_dist=False, strong=False, timed=_stub_timed, edges_of=lambda r: 0, tiles_of=lambda r: None, outputs=outputs)
+    assert len(outputs) == len(batches) == len(recs)
+    for bidx, (o, r) in enumerate(zip(outputs, recs)):
+        assert o.shape == (r["atoms"], 3) and bool((o == 11 + bidx + W + K).all())      # (_stub_timed: seed + bidx + one per step)
+    pos = torch.cat(outputs).numpy().astype(np.float64)
+    bench.dump_outputs(str(tmp_path / "all"), {"pos": pos})
+    got = np.load(str(tmp_path / "all" / "pos.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, pos)
+    limit = pos.shape[0] * 12 // 3
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"pos": pos}, limit=limit)
+    s1, s2 = np.load(str(tmp_path / "s1" / "pos.npy")), np.load(str(tmp_path / "s2" / "pos.npy"))
+    assert 0 < s1.nbytes <= limit and s1.shape[1] == 3 and np.array_equal(s1, s2)
+
+
 def _run_job_shard_worker(rank, world, port, out, tmp):
     """driver.run_job(shard=True): every rank prepares ITS graph range of the next batch in the background
     (driver.prepare_batch(rank, world)) and hands the topology to the sampler of that range."""

@@ -9,12 +9,12 @@ mkdir -p $out
 cd $GRAFT_REPO_ROOT
 say() { echo "$(date +%T) $*"; }
 if [ $part = default ]; then
-  say "default bench (drugs200)"; t0=$SECONDS; python bench.py --gpus 1 --steps 20 --warmup 5 2>$out/${R}_bench_default.err | tail -1 > $out/${R}_${PREC}_bench.json; say "default bench took $((SECONDS - t0)) s wall"
+  say "default bench (drugs200)"; t0=$SECONDS; python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>$out/${R}_bench_default.err | tail -1 > $out/${R}_${PREC}_bench.json; say "default bench took $((SECONDS - t0)) s wall"
 elif [ $part = bench ] || [ $part = rest ]; then
   if [ $part = bench ]; then
-  say "default bench (drugs200)"; t0=$SECONDS; python bench.py --gpus 1 --steps 20 --warmup 5 2>$out/${R}_bench_default.err | tail -1 > $out/${R}_${PREC}_bench.json; say "default bench took $((SECONDS - t0)) s wall"
+  say "default bench (drugs200)"; t0=$SECONDS; python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>$out/${R}_bench_default.err | tail -1 > $out/${R}_${PREC}_bench.json; say "default bench took $((SECONDS - t0)) s wall"
   fi
-  say "drugs 8x128 + breakdown"; python bench.py --workload drugs --breakdown $out/${R}_${PREC}_breakdown.json --no-cpu-baseline 2>/dev/null | tail -1 > $out/${R}_bench_drugs_8x128.json
+  say "drugs 8x128 + breakdown"; python bench.py --workload drugs --breakdown $out/${R}_${PREC}_breakdown.json --full --no-cpu-baseline 2>/dev/null | tail -1 > $out/${R}_bench_drugs_8x128.json
   say "8x128 unfused front"; python bench.py --workload drugs --front unfused --steps 500 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $out/${R}_bench_drugs_8x128_unfused_front.json
   say "8x128 poly off"; python bench.py --workload drugs --radius-poly off --steps 300 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $out/${R}_bench_poly_off.json
   say "8x128 f32"; python bench.py --workload drugs --precision f32 --steps 300 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $out/${R}_bench_f32.json
@@ -23,7 +23,7 @@ elif [ $part = bench ] || [ $part = rest ]; then
   say "sharpness sweep"; python tools/sharpness_sweep.py --out $out/${R}_sharpness_sweep.json > /dev/null 2>&1
   say "per-kernel stand-alone times (both branches on one stream), 36 x 128 batch"; bash tools/kstats.sh . serial --workload drugs --mols 36 --copies 128 --serial > $out/${R}_kernel_times_serial_36x128.txt 2>&1
   say "default schedule"; python bench.py --schedule default --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $out/${R}_bench_drugs200_default_sched.json
-  say "qm9"; python bench.py --workload qm9 --mols 40 --copies 64 --steps 1000 --no-cpu-baseline 2>/dev/null | tail -1 > $out/${R}_bench_qm9.json
+  say "qm9"; python bench.py --workload qm9 --mols 40 --copies 64 --steps 1000 --full --no-cpu-baseline 2>/dev/null | tail -1 > $out/${R}_bench_qm9.json
   say "large"; python bench.py --workload large --mols 2 --copies 128 --steps 300 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $out/${R}_bench_large.json
   say "alanine"; python bench.py --workload alanine --mols 1 --copies 250 --schedule default --job-steps 100 --steps 100 --warmup 0 --no-cpu-baseline 2>/dev/null | tail -1 > $out/${R}_bench_alanine.json
   say "small batches"; python bench.py --workload drugs --mols 1 --copies 100 --steps 2000 --no-cpu-baseline --no-extra 2>/dev/null | tail -1 > $out/${R}_bench_small_batch.json
