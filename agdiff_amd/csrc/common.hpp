@@ -719,6 +719,7 @@ static inline bool ag_allow_big_lds(std::atomic<uint64_t>& done, size_t smem, K.
   if (done.load(std::memory_order_acquire) & bit) return true;
   const bool ok = ((hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) == hipSuccess) && ...);
   if (ok) done.fetch_or(bit, std::memory_order_release);
+  else (void)hipGetLastError();        // (the caller reports AGDIFF_ERR_LAUNCH: the refused attribute must not surface in the next HIP call)
   return ok;
 }
 // Host side: the variant a launcher chose, for agdiff_ws_t.variant_log (a host word the tests read), and a tuning field of

@@ -496,9 +496,14 @@ int graph_build_impl(const agdiff_params_t* p, const agdiff_topo_t* topo, const 
   // (1 x 100 conformers: 61 / 45 / 37 us with 256 / 512 / 1024 threads; 1024 molecules: 133 / 119 / 123)
   const int bd = topo->num_graphs >= 512 ? 512 : 1024;
   const size_t smem = (size_t)(3 * nmax + 3 * nmax + 2 * nmax * a.words) * 4;
-  if (smem > 48 * 1024) {
+  if (smem > 48 * 1024) {       // (molecules of more than 384 atoms)
+    // the attribute is the most this launcher ever asks for (AGDIFF_MAX_ATOMS_PER_GRAPH atoms), not all 160 KiB of a CU: dynamic
+    // plus static LDS (k_graph<true>'s segment tables, 6.4 KB) must fit 160 KiB, or the runtime refuses the attribute
+    constexpr int wmax = 2 * ((AGDIFF_MAX_ATOMS_PER_GRAPH + 63) / 64), nbig = wmax * 32;
+    constexpr size_t smem_max = (size_t)(3 * nbig + 3 * nbig + 2 * nbig * wmax) * 4;
+    static_assert(smem_max + 8 * 1024 <= 160 * 1024, "k_graph's LDS at AGDIFF_MAX_ATOMS_PER_GRAPH");
     static std::atomic<uint64_t> attr_done{0};
-    if (!ag_allow_big_lds(attr_done, (size_t)160 * 1024, k_graph<false>, k_graph<true>)) return AGDIFF_ERR_LAUNCH;
+    if (!ag_allow_big_lds(attr_done, smem_max, k_graph<false>, k_graph<true>)) return AGDIFF_ERR_LAUNCH;
   }
   k_graph<false><<<dim3((unsigned)topo->num_graphs), dim3(bd), smem, st>>>(a);
   AG_CHECK_LAUNCH();

@@ -247,11 +247,13 @@ def _edge_attr_fn(sd, e, typ):
     return fn
 
 
-def encoder_activation_max(sd, cfg, types=(0, 1, 2, 3, 12, 23, 24), far=10.0):
-    """Largest magnitude any activation of the MLP edge encoder (edge.py:84-103) and of the CFConv filter networks behind it
-    (schnet.py:169-179) takes as an MFMA operand, over lengths in [0, far x cutoff] and the common edge types: these depend on the
-    length and the type alone, so their range is a property of the checkpoint and is checked when it is packed (the split-fp16 mode
-    saturates operands at 65504; the state-dependent activations are flagged by the kernels: agdiff_ws_t.range_rows).  float64."""
+def encoder_activation_by_type(sd, cfg, far=10.0):
+    """[rows of bond_emb] float64: per edge type, the largest magnitude any activation of the MLP edge encoder (edge.py:84-103) and
+    of the CFConv filter networks behind it (schnet.py:169-179) takes as an MFMA operand, over lengths in [0, far x cutoff].  These
+    depend on the length and the type alone, so their range is a property of the checkpoint and is checked when it is packed (the
+    split-fp16 mode saturates operands at 65504; the state-dependent activations are flagged by the kernels: agdiff_ws_t.range_rows).
+    EVERY row of bond_emb is evaluated: a batch may bring any local type (ensure_local_types gives it a slot without a new check),
+    and no kernel flags these activations.  About a second of host time, once per checkpoint (PackedParams caches it)."""
     import torch
     import torch.nn.functional as F
     e = "edge_encoder_global"
@@ -259,23 +261,31 @@ def encoder_activation_max(sd, cfg, types=(0, 1, 2, 3, 12, 23, 24), far=10.0):
     few, feb = g(e + ".feature_expansion.weight"), g(e + ".feature_expansion.bias")
     W0, b0, W2, b2 = g(e + ".edge_feature_mlp.0.weight"), g(e + ".edge_feature_mlp.0.bias"), g(e + ".edge_feature_mlp.2.weight"), g(e + ".edge_feature_mlp.2.bias")
     C0, c0, C2, c2 = g(e + ".combination_mlp.0.weight"), g(e + ".combination_mlp.0.bias"), g(e + ".combination_mlp.2.weight"), g(e + ".combination_mlp.2.bias")
+    emb = g(e + ".bond_emb.weight")
     d = torch.linspace(0.0, float(far) * float(cfg.cutoff), 1025, dtype=torch.float64).view(-1, 1)
     x = F.gelu(F.linear(d, few, feb))
-    worst = float(x.abs().max())
+    # (the Linear over cat([x, emb]) split into its length half, shared, and its type half, one row per type: as the pack does)
+    xw0 = F.linear(x, W0[:, :H])
+    t1, t3 = F.linear(emb, W0[:, H:], b0), F.linear(emb, C0[:, H:], c0)
     LN2 = float(np.log(2.0))
-    for typ in types:
-        emb = g(e + ".bond_emb.weight")[int(typ)].expand(d.shape[0], -1)
-        h1 = F.gelu(F.linear(torch.cat([x, emb], 1), W0, b0))
-        h2 = F.linear(h1, W2, b2)
-        h3 = F.gelu(F.linear(torch.cat([h2, emb], 1), C0, c0))
+    nn0 = ["encoder_global.interactions.%d.%s.nn." % (k, conv) for k in range(cfg.num_convs) for conv in ("conv1", "conv2")]
+    Wf, bf = torch.cat([g(p + "0.weight") for p in nn0]), torch.cat([g(p + "0.bias") for p in nn0])
+    beta = torch.cat([g(p + "1.beta").expand(g(p + "0.bias").shape[0]) for p in nn0])
+    worst = torch.full((emb.shape[0],), float(x.abs().max()), dtype=torch.float64)
+    for a in range(0, emb.shape[0], 20):                   # (20 types at a time: ~20 MB per activation tensor)
+        h1 = F.gelu(xw0[None] + t1[a:a + 20, None])
+        h3 = F.gelu(F.linear(F.linear(h1, W2, b2), C0[:, :H]) + t3[a:a + 20, None])
         attr = F.linear(h3, C2, c2)
-        worst = max(worst, float(h1.abs().max()), float(h3.abs().max()), float(attr.abs().max()))
-        for k in range(cfg.num_convs):
-            for conv in ("conv1", "conv2"):
-                p = "encoder_global.interactions.%d.%s" % (k, conv)
-                sp = F.softplus(g(p + ".nn.1.beta") * F.linear(attr, g(p + ".nn.0.weight"), g(p + ".nn.0.bias"))) - LN2
-                worst = max(worst, float(sp.abs().max()))
-    return worst
+        sp = F.softplus(beta * F.linear(attr, Wf, bf)) - LN2
+        for v in (h1, h3, attr, sp):
+            worst[a:a + 20] = torch.maximum(worst[a:a + 20], v.abs().amax(dim=(1, 2)))
+    return worst.numpy()
+
+
+def encoder_activation_max(sd, cfg, types=None, far=10.0):
+    """max of encoder_activation_by_type over `types` (None: every row of bond_emb)."""
+    by = encoder_activation_by_type(sd, cfg, far)
+    return float(by.max() if types is None else by[np.asarray(list(types), dtype=np.int64)].max())
 
 
 def _poly_targets(sd, cfg, typ, with_head):
@@ -571,16 +581,19 @@ class PackedParams:
             self._pack_mlp_edge_encoder(sd, e, arrays, pack_blocks)
             if mode == 2 or lmode == 2:       # (activations that depend on the length and the type alone: their range is the checkpoint's;
                 # the local branch's kernels read the encoder's rows as operands too)
-                key = (_poly_weights_digest(sd, cfg), float(cfg.cutoff), int(cfg.num_convs), "activation_max")
+                key = (_poly_weights_digest(sd, cfg), float(cfg.cutoff), int(cfg.num_convs), "activation_by_type")
                 if key not in _FIT_CACHE:
-                    _FIT_CACHE[key] = encoder_activation_max(sd, cfg)
-                amax = _FIT_CACHE[key]
+                    _FIT_CACHE[key] = encoder_activation_by_type(sd, cfg)
+                by_type = _FIT_CACHE[key]
+                amax = float(by_type.max())
                 self.encoder_activation_max = amax
+                self.encoder_activation_type = int(by_type.argmax())
                 if not amax < SPLIT_FP16_ACT_LIMIT:
                     for branch, on in (("global", mode == 2), ("local", lmode == 2)):
                         if on:
                             self.split_fp16_report[branch]["clipped"] = True
                             self.split_fp16_report[branch]["activations"] = amax
+                            self.split_fp16_report[branch]["activation_type"] = self.encoder_activation_type
         arrays["schnet_emb"] = _np(sd, "encoder_global.embedding.weight")
         arrays["gin_emb"] = _np(sd, "encoder_local.node_emb.weight")
         self._pack_rest(sd, cfg, device, mode, arrays, scalars, pack_blocks)

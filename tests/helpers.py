@@ -71,6 +71,30 @@ def check_close(name, got, ref, precision, scale=1.0):
     return rn
 
 
+def per_graph_normwise(got, ref, graph, num):
+    """Normwise figure (rel_err) of every graph: rows of `got` / `ref` [n, ...] belong to graph `graph[n]` in [0, num)."""
+    got, ref = (torch.as_tensor(np.asarray(x.detach().cpu() if hasattr(x, "detach") else x), dtype=torch.float64).reshape(len(graph), -1)
+                for x in (got, ref))
+    gid = torch.as_tensor(np.asarray(graph), dtype=torch.int64)
+    d = torch.zeros(num, dtype=torch.float64).scatter_reduce_(0, gid, (got - ref).abs().amax(dim=1), "amax")
+    m = torch.zeros(num, dtype=torch.float64).scatter_reduce_(0, gid, ref.abs().amax(dim=1), "amax")
+    return (d / m.clamp_min(1e-30)).numpy()
+
+
+def check_per_graph(name, err, labels, precision, scale=1.0):
+    """Gate per-graph normwise figures `err` [graphs] at TOL_NORM[precision] x scale; the failure message names the worst graphs
+    (`labels`: one description per graph).  The worst figure is recorded with the check_close records."""
+    gate = TOL_NORM[precision] * scale
+    worst = float(err.max()) if err.size else 0.0
+    _RECORDS.append({"name": name, "precision": precision, "normwise": worst, "elementwise": None, "gate_norm": gate,
+                     "gate_elem": None, "graphs": int(err.size)})
+    print("parity %-48s %-7s per-graph normwise max %.2e over %d graphs" % (name, precision, worst, err.size))
+    bad = np.argsort(-err)[:5]
+    assert worst < gate, "%s (%s): per-graph normwise %.3e >= %.1e; worst: %s" % (
+        name, precision, worst, gate, "; ".join("%s %.3e" % (labels[i], err[i]) for i in bad))
+    return worst
+
+
 FORWARD_CASES = {
     "g3_forward_qm9_small": lambda: qm9_model_config(),
     "g3_forward_smooth_sparse": lambda: drugs_model_config(),
@@ -95,3 +119,35 @@ def sampler_case_kwargs(g):
             v = float(g[k])
             kw[k[3:]] = None if np.isnan(v) else v
     return kw
+
+
+def quad_cut_owners(quad_wg_ptr, quad_tgt, batch):
+    """The graphs k_cfconv_quad's workgroup ranges cut between: agdiff_topo_t.quad_wg_ptr splits the quads (quad_tgt, four target
+    nodes each, -1 = none; a quad holds targets of ONE graph) into 256 contiguous ranges by tile cost, not at graph boundaries.
+    Returns (owners, straddling, quad_graph): the sorted graph ids that own the quad on either side of an interior cut, those of
+    them whose quads fall on both sides of a cut, and the graph of every quad."""
+    w = np.asarray(quad_wg_ptr, dtype=np.int64)
+    qt = np.asarray(quad_tgt, dtype=np.int64).reshape(-1, 4)
+    batch = np.asarray(batch, dtype=np.int64)
+    quad_graph = batch[qt[:, 0]]
+    assert np.all(qt[:, 0] >= 0) and np.all(np.where(qt >= 0, batch[np.maximum(qt, 0)], quad_graph[:, None]) == quad_graph[:, None])
+    cuts = w[1:-1]
+    cuts = cuts[(cuts > 0) & (cuts < qt.shape[0])]
+    before, after = quad_graph[cuts - 1], quad_graph[cuts]
+    return np.union1d(before, after), np.unique(before[before == after]), quad_graph
+
+
+# The split-fp16 range bound of the length-only encoder activations (packing.encoder_activation_by_type) for a local edge type
+# outside the common seven: its bond_emb row scaled so that the encoder's hidden layer passes 65504 inside the cutoff (x 1e5 on
+# the synthetic checkpoint: ~9.5e4) while every other type keeps its activations (~35)
+ADVERSARIAL_TYPE = 4
+
+
+def scale_bond_emb_row(sd, typ=ADVERSARIAL_TYPE, factor=1e5):
+    """A copy of state dict `sd` with row `typ` of edge_encoder_global.bond_emb times `factor` (under both of its names: attribute
+    path and ModuleList alias)."""
+    from agdiff_amd import synth
+    k = "edge_encoder_global.bond_emb.weight"
+    w = sd[k].detach().clone()
+    w[typ] *= factor
+    return {n: (w.clone() if synth.canonical_key(n) == k else v) for n, v in sd.items()}

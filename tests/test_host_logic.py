@@ -789,3 +789,84 @@ def test_length_only_activations_beyond_fp16_range_send_the_branch_to_split_bf16
     pk = packing.PackedParams(sd, cfg, "cpu", "bf16x3", radius_poly="off")
     assert pk.precision_local == "f16x3" and pk.split_fp16_report["local"]["clipped"] and not pk.split_fp16_report["global"]["clipped"]
     assert not hasattr(packing.PackedParams(sd, cfg, "cpu", "bf16x3", radius_poly="off", precision_local="bf16x3"), "encoder_activation_max")
+
+
+def test_encoder_activation_bound_covers_every_edge_type():
+    """The split-fp16 range bound of the length-only activations (packing.encoder_activation_by_type) is evaluated for EVERY row of
+    bond_emb, not only for the seven common types: a batch may bring any local type (ensure_local_types slots it without a new check)
+    and neither k_edge_encoder nor k_cfconv_fused flags these activations.  Type 4 scaled (helpers.scale_bond_emb_row) so that the
+    encoder's hidden layer passes 65504 inside the cutoff while the seven common types stay where they were: the bound names type
+    4 and the pack sends both branches to split-bf16."""
+    from agdiff_amd import packing
+    from helpers import ADVERSARIAL_TYPE, scale_bond_emb_row
+    import torch.nn.functional as F
+    cfg = drugs_model_config()
+    sd = O.synth_state_dict_for(cfg)
+    common = [0, 1, 2, 3, 12, 23, 24]
+    base = packing.encoder_activation_by_type(sd, cfg)
+    assert base.shape == (100,) and base.max() < 1e3
+    bad = scale_bond_emb_row(sd)
+    by = packing.encoder_activation_by_type(bad, cfg)
+    assert int(by.argmax()) == ADVERSARIAL_TYPE and by[ADVERSARIAL_TYPE] > packing.SPLIT_FP16_ACT_LIMIT
+    assert np.array_equal(np.delete(by, ADVERSARIAL_TYPE), np.delete(base, ADVERSARIAL_TYPE)) and by[common].max() < 60000.0
+    assert packing.encoder_activation_max(bad, cfg, types=common) < 60000.0 <= packing.encoder_activation_max(bad, cfg)
+    # the per-type figure against a plain float64 evaluation of the encoder + filter networks, one type at a time
+    e = "edge_encoder_global"
+    g = lambda k: bad[k].detach().double()
+    d = torch.linspace(0.0, 10.0 * cfg.cutoff, 1025, dtype=torch.float64).view(-1, 1)
+    x = F.gelu(F.linear(d, g(e + ".feature_expansion.weight"), g(e + ".feature_expansion.bias")))
+    for ty in (0, ADVERSARIAL_TYPE, 24, 99):
+        emb = g(e + ".bond_emb.weight")[ty].expand(d.shape[0], -1)
+        h1 = F.gelu(F.linear(torch.cat([x, emb], 1), g(e + ".edge_feature_mlp.0.weight"), g(e + ".edge_feature_mlp.0.bias")))
+        h2 = F.linear(h1, g(e + ".edge_feature_mlp.2.weight"), g(e + ".edge_feature_mlp.2.bias"))
+        h3 = F.gelu(F.linear(torch.cat([h2, emb], 1), g(e + ".combination_mlp.0.weight"), g(e + ".combination_mlp.0.bias")))
+        attr = F.linear(h3, g(e + ".combination_mlp.2.weight"), g(e + ".combination_mlp.2.bias"))
+        ref = max(float(v.abs().max()) for v in (x, h1, h3, attr))
+        for k in range(cfg.num_convs):
+            for conv in ("conv1", "conv2"):
+                p = "encoder_global.interactions.%d.%s.nn." % (k, conv)
+                sp = F.softplus(g(p + "1.beta") * F.linear(attr, g(p + "0.weight"), g(p + "0.bias"))) - np.log(2.0)
+                ref = max(ref, float(sp.abs().max()))
+        assert abs(by[ty] - ref) <= 1e-9 * ref, (ty, by[ty], ref)
+        if ty == ADVERSARIAL_TYPE:        # (the encoder's hidden layer itself, inside the cutoff, is what passes fp16's range)
+            assert float(h1[d[:, 0] <= cfg.cutoff].abs().max()) > 65504.0
+    for radius_poly in ("off", "auto"):
+        pk = PackedParams(bad, cfg, "cpu", "f16x3", radius_poly=radius_poly)
+        for branch in ("global", "local"):
+            rep = pk.split_fp16_report[branch]
+            assert rep["clipped"] and rep["activation_type"] == ADVERSARIAL_TYPE and rep["activations"] == by.max(), (branch, rep)
+    pk = PackedParams(sd, cfg, "cpu", "f16x3")
+    assert not pk.split_fp16_report["global"]["clipped"] and not pk.split_fp16_report["local"]["clipped"]
+
+
+def test_quad_cut_owners_name_both_sides_of_every_workgroup_range_cut():
+    """helpers.quad_cut_owners, the graph selection of the product-shape parity test (test_hip_parity.py): for every interior cut of
+    agdiff_topo_t.quad_wg_ptr it returns the graph of the last quad before the cut and of the first one after it, nothing else; cuts
+    land inside graphs (a graph's quads in two workgroups: `straddling`) as well as between two graphs, so neither half of the
+    selection can silently go empty."""
+    from helpers import quad_cut_owners
+    b = synth.make_packed_batch("drugs", 12, 40, seed=7)
+    tp = BatchTopology(b["atom_type"], b["bond_index"], b["bond_type"], b["batch"], b["num_graphs"], device="cpu", group_targets=4)
+    assert tp.Q >= 256 and tp.quad_wg_ptr is not None
+    w, qt, ba = tp.quad_wg_ptr.numpy().astype(np.int64), tp.quad_tgt.numpy().astype(np.int64).reshape(-1, 4), b["batch"]
+    owners, straddling, qg = quad_cut_owners(w, qt, ba)
+    assert qg.shape == (tp.Q,) and np.all(np.diff(qg) >= 0)                       # quads in graph order, one graph each
+    assert np.array_equal(np.unique(qg), np.arange(b["num_graphs"]))
+    inside, between, want = 0, 0, set()
+    for c in w[1:-1]:
+        if 0 < c < tp.Q:
+            g0, g1 = int(ba[qt[c - 1, 0]]), int(ba[qt[c, 0]])
+            want |= {g0, g1}
+            assert g0 in owners and g1 in owners
+            if g0 == g1:
+                inside += 1
+                assert g0 in straddling
+            else:
+                between += 1
+    assert set(owners.tolist()) == want and set(straddling.tolist()) <= want
+    assert inside > 0 and between > 0 and len(straddling) == len({int(ba[qt[c, 0]]) for c in w[1:-1] if 0 < c < tp.Q and
+                                                                  ba[qt[c - 1, 0]] == ba[qt[c, 0]]})
+    # a graph straddles exactly when its quads fall into two ranges
+    wg_of = np.searchsorted(w, np.arange(tp.Q), side="right") - 1
+    two = {int(g) for g in np.unique(qg) if np.unique(wg_of[qg == g]).size > 1}
+    assert two == set(straddling.tolist())
