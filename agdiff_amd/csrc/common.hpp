@@ -223,13 +223,9 @@ __device__ __forceinline__ void ag_cvt_pair(AgIn<AG_H3>& o, int j, float v0, flo
   const auto hp = __builtin_amdgcn_cvt_pkrtz(v0, v1);
   // v - float(hi) as fma(v, one, -float(hi)) with a 1.0 the optimiser cannot see through: ONE v_fma_mix_f32 that reads the
   // fp16 half directly instead of v_cvt_f32_f16 + v_sub_f32 (the same single rounding: v * 1 is exact)
-#ifdef AG_NO_FMA_MIX        // (A/B builds: the two-instruction form)
-  const auto lp = __builtin_amdgcn_cvt_pkrtz(v0 - (float)hp[0], v1 - (float)hp[1]);
-#else
   float one = 1.0f;
   asm("" : "+s"(one));
   const auto lp = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf(v0, one, -(float)hp[0]), __builtin_fmaf(v1, one, -(float)hp[1]));
-#endif
   o.hi[j] = (_Float16)hp[0];
   o.hi[j + 1] = (_Float16)hp[1];
   o.lo[j] = (_Float16)lp[0];
@@ -246,13 +242,6 @@ __device__ __forceinline__ void ag_cvt_pair(AgIn<AG_F32>& o, int j, float v0, fl
   o.v[j >> 2][(j & 3) + 1] = v1;
 }
 __device__ __forceinline__ void ag_cvt_pair(AgIn<AG_BF3>& o, int j, float v0, float v1) {
-#ifdef AG_CVT_PAIR_SCALAR
-  const __bf16 h0 = (__bf16)v0, h1 = (__bf16)v1;
-  o.hi[j] = h0;
-  o.hi[j + 1] = h1;
-  o.lo[j] = (__bf16)(v0 - (float)h0);
-  o.lo[j + 1] = (__bf16)(v1 - (float)h1);
-#else
   // one v_cvt_pk_bf16_f32 per pair for hi and one for lo; the rounded values come back as floats by a shift / a mask of the
   // packed word (six instructions per pair: element-wise conversion compiled to eight)
   typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -265,7 +254,6 @@ __device__ __forceinline__ void ag_cvt_pair(AgIn<AG_BF3>& o, int j, float v0, fl
   o.hi[j + 1] = hp[1];
   o.lo[j] = lp[0];
   o.lo[j + 1] = lp[1];
-#endif
 }
 // The mixed second operand of agdiff_params_t.poly_plan 1 (ag_poly_features): hi = the split's hi of (v0, v1) as above; lo =
 // the hi part of (m0, m1) - own * (hi as float): with own = 1 and m = v the usual lo part, with own = 0 the hi part of m.
@@ -421,16 +409,6 @@ __device__ __forceinline__ void ag_dense(const AgIn<MODE> (&x)[NX], f32x4 (&o)[N
 template <int MODE, bool FLIP, bool KOUTER, int KT, int OT, int X0, int O0, int NX, int NO>
 __device__ __forceinline__ void ag_dense_lds(const AgIn<MODE> (&x)[NX], f32x4 (&o)[NO], const lds_u32x4* wl, int lane) {
   static_assert(X0 + KT <= NX && O0 + OT <= NO, "tile range");
-#ifdef AG_DENSE_LDS_PLAIN
-#pragma unroll
-  for (int s = 0; s < OT * KT; ++s) {
-    const int t = KOUTER ? s / OT : s % KT, ot = KOUTER ? s % OT : s / KT;
-    u32x4 w[2];
-    w[0] = wl[(s * 2) * 64 + lane];
-    w[1] = wl[(s * 2 + 1) * 64 + lane];
-    ag_block_mma<MODE, FLIP>(o[O0 + ot], x[X0 + t], w);
-  }
-#else
   // Output tiles in groups of G: the G blocks of a k-tile are read together and their MFMA passes interleaved over the G
   // accumulators (back-to-back MFMAs on one accumulator, each behind its own LDS read, made these layers a chain of
   // exposed latencies).  Per accumulator the order of the additions is unchanged (k-tile outer, pass inner).
@@ -444,13 +422,6 @@ __device__ __forceinline__ void ag_dense_lds(const AgIn<MODE> (&x)[NX], f32x4 (&
       for (int g = 0; g < G; ++g) {
         const int ot = og * G + g;
         const int s = KOUTER ? t * OT + ot : ot * KT + t;
-#ifdef AG_DENSE_LDS_HALF      // (timing experiment: every second weight block read from LDS, the others reused -- wrong results)
-        if (g & 1) {
-          w[g][0] = w[g - 1][0];
-          w[g][1] = w[g - 1][1];
-          continue;
-        }
-#endif
         w[g][0] = wl[(s * 2) * 64 + lane];
         w[g][1] = wl[(s * 2 + 1) * 64 + lane];
       }
@@ -461,7 +432,6 @@ __device__ __forceinline__ void ag_dense_lds(const AgIn<MODE> (&x)[NX], f32x4 (&
       }
     }
   }
-#endif
 }
 // Mixed source: unit 0 of every block (hi halves in AG_BF3, first k-half in AG_F32) from an LDS array that holds
 // only those units (64 u32x4 per block), unit 1 streamed from the full packed matrix in global memory PF blocks
@@ -711,6 +681,7 @@ __device__ __forceinline__ void ag_copy_lds(lds_u32x4* dst, const u32x4* __restr
 // function attributes PER DEVICE: `done` has one bit per device id, so a process that drives several GPUs sets the
 // attribute on each of them (setting it twice from two threads is harmless, hence no lock).
 #include <atomic>
+#include <type_traits>
 template <typename... K>
 static inline bool ag_allow_big_lds(std::atomic<uint64_t>& done, size_t smem, K... kernels) {
   int dev = 0;
@@ -728,6 +699,14 @@ static inline void ag_log_variant(const agdiff_ws_t* ws, int64_t bits) {
   if (ws && ws->variant_log) *ws->variant_log |= bits;
 }
 static inline int64_t ag_tune(int64_t v, int64_t dflt) { return v != 0 ? v : dflt; }
+// A launch in the arithmetic mode `mode` (agdiff_params_t.precision): f(std::integral_constant<int, AG_H3 / AG_BF3>{}), and
+// AG_F32 for every other value.
+template <typename F>
+static inline auto ag_by_mode(int mode, F&& f) {
+  if (mode == AG_H3) return f(std::integral_constant<int, AG_H3>{});
+  if (mode == AG_BF3) return f(std::integral_constant<int, AG_BF3>{});
+  return f(std::integral_constant<int, AG_F32>{});
+}
 // agdiff_sampler_front with the update's step read from a device table (front.hip; used by agdiff_step_graph_capture)
 int ag_sampler_front_table(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, const agdiff_step_args_t* s,
                            const agdiff_step_args_t* step_table, const int32_t* step_index, int32_t mode, float cutoff, void* stream);

@@ -3,8 +3,6 @@
 // One wave = one tile of 16 edges; activations stay in the MFMA accumulator layout between layers
 // (common.hpp).  Every MFMA kernel is instantiated for both arithmetic modes (AG_F32 / AG_BF3).
 #include "common.hpp"
-#include <cstdlib>
-#include <type_traits>
 
 namespace {
 
@@ -236,35 +234,9 @@ struct ConvArgs {
   float* agg_first;      // [chunks][192]
   int64_t max_chunks;
   int32_t chunk_tiles;   // tiles per chunk (agdiff_conv_chunk_tiles)
-  int32_t ablate;        // timing experiments only (AGDIFF_ABLATE env): bit0 skip layer 1, bit1 skip ssp,
-                         // bit2 skip layer 2, bit3 skip x gather, bit4 skip reduction, bit6 skip the next tile's e_attr
-                         // loads, bit7 skip the first layer's LDS weight reads
 };
 
-#ifdef AG_CONV_STAMPS
-// Diagnostic build only (make EXTRA=-DAG_CONV_STAMPS): per-phase wave cycles of k_cfconv_fused, summed over waves.
-__device__ unsigned long long ag_conv_stamp_acc[8];
-#define AG_STAMP(var)                                  \
-  do {                                                 \
-    __builtin_amdgcn_sched_barrier(0);                 \
-    var = __builtin_readcyclecounter();                \
-    __builtin_amdgcn_sched_barrier(0);                 \
-  } while (0)
-#else
-#define AG_STAMP(var) do { } while (0)
-#endif
-
-// Timing experiments (AGDIFF_ABLATE env) exist only in the diagnostic build (make EXTRA=-DAG_CONV_ABLATE): in the
-// product build the tile body has no uniform branches around its phases, which also gives the scheduler one region.
-#ifdef AG_CONV_ABLATE
-#define AG_ABL(bit) (a.ablate & (bit))
-#else
-#define AG_ABL(bit) false
-#endif
-
-#ifndef AG_CONV_WAVES
 #define AG_CONV_WAVES 8     // waves per workgroup (= per CU): 2 per SIMD
-#endif
 #define AG_CONV_LDS_BLOCKS 80   // resident 2-KiB weight blocks: filt_w1 (48: both convs' first layer) | filt_w2a (32)
 #define AG_CONV_NCH 12          // 16-channel tiles of the 192 filter channels (conv1: 0..7, conv2: 8..11)
 
@@ -297,7 +269,6 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
   // Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8); give each XCD a contiguous range of the
   // destination-sorted edge list per round, so that the x rows and list bounds of a molecule stay in ONE L2.
   const int wg = (gridDim.x % 8 == 0) ? (int)((blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8) : (int)blockIdx.x;
-  [[maybe_unused]] unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c0 = 0, c1 = 0;
 
   // edge attributes of the wave's NEXT tile are requested as soon as the current tile's first layer has consumed
   // its own (they land during the rest of the tile)
@@ -344,7 +315,6 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
       const int64_t tile = chunk * a.chunk_tiles + tt;
       const int64_t tbase = tile * AG_TW;
       if (tbase >= E) break;
-      AG_STAMP(c0);
       // opaque copy of the lane id: keeps hipcc from hoisting every lane-derived weight / table address
       // out of the tile loop (they would stay live across the whole body and spill)
       int lane = lane0;
@@ -363,7 +333,6 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
         }
         run_t = -1;
       }
-      AG_STAMP(c1); st[0] += c1 - c0; c0 = c1;       // meta loads, carry flush
 
       // per edge slot of my quarter (slot 4q + r lives in lane 4q + r): gather row of x, and the scales
       // lw(d)*C(d) of the two convs, which multiply the message: (H^T W2 + b2) . s . x[src]
@@ -388,16 +357,12 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
       // second filter layer per 16-channel tile, flipped (rows = edges, lanes = channels), then message and
       // destination-segmented reduction of that channel tile.  The x[src] rows of the next channel tile are
       // fetched before the current tile's reduction.
-      // x[src] rows (and the second-layer bias) of channel tile nt are requested AG_X_AHEAD channel tiles before their
+      // x[src] rows (and the second-layer bias) of channel tile nt are requested XA channel tiles before their
       // use through a small register ring: one channel tile (12 MFMAs) does not cover an L2 round trip under load
-#ifndef AG_X_AHEAD
-#define AG_X_AHEAD 2
-#endif
-      constexpr int XA = AG_X_AHEAD, XR = XA + 1;
+      constexpr int XA = 2, XR = XA + 1;
       f32x4 xring[XR];
       float bring[XR];
       auto fetch_x = [&](int nt) {
-        if (AG_ABL(8)) return;
         // base (SGPR pair) + 32-bit byte offset (VGPR) + immediate 64 nt: one instruction per gathered value
         const char* xb = reinterpret_cast<const char*>(a.xs);
 #pragma unroll
@@ -413,10 +378,8 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
         int64_t nxt = tile + 1;
         if (tt + 1 >= a.chunk_tiles) nxt = (chunk + cstride) * a.chunk_tiles;
         if (nxt * AG_TW < E && nxt < a.max_chunks * a.chunk_tiles) {
-          if (!(AG_ABL(64))) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) ag_load_attr(ea[t], a.e_attr, nxt, t, lane);
-          }
+          for (int t = 0; t < 4; ++t) ag_load_attr(ea[t], a.e_attr, nxt, t, lane);
           prefetch_meta(nxt, lane);
         }
       };
@@ -426,10 +389,7 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
         // t * 12 + ot), two output tiles (= one k-tile of the second layer) at a time, so that the softplus
         // and the operand split of one pair can issue between the MFMAs of the next.
         // weight blocks are read from LDS one step (two blocks) ahead of the MFMAs that use them
-#ifndef AG_L1_LDS_AHEAD
-#define AG_L1_LDS_AHEAD 1       // steps (of two blocks) the LDS weight reads run ahead of their MFMAs
-#endif
-        constexpr int WA = AG_L1_LDS_AHEAD, WR = WA + 1;
+        constexpr int WA = 1, WR = WA + 1;
         u32x4 wq[WR][2][2];
         const lds_u32x4* w1_lo = ag_lds_base(w1, lane);
         const lds_u32x4* w1_hi = ag_lds_base(w1 + 32 * 128, lane);
@@ -465,15 +425,13 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
           for (int t = 0; t < 4; ++t) {
             const int step = m * 4 + t;
             if (m < AG_CONV_NCH / 2) {
-              if (step + WA < 4 * (AG_CONV_NCH / 2) && !(AG_ABL(128))) fetch_w(wq[(step + WA) % WR], step + WA);
-              if (!(AG_ABL(1))) {
-                ag_block_mma<MODE, false>(h0, ea[t], wq[step % WR][0]);
-                ag_block_mma<MODE, false>(h1, ea[t], wq[step % WR][1]);
-              }
+              if (step + WA < 4 * (AG_CONV_NCH / 2)) fetch_w(wq[(step + WA) % WR], step + WA);
+              ag_block_mma<MODE, false>(h0, ea[t], wq[step % WR][0]);
+              ag_block_mma<MODE, false>(h1, ea[t], wq[step % WR][1]);
             }
             if (m > 0) {
               float v0 = (t < 2) ? hp0[2 * t] : hp1[2 * t - 4], v1 = (t < 2) ? hp0[2 * t + 1] : hp1[2 * t - 3];
-              if (!(AG_ABL(2))) { v0 = ag_ssp_base2(v0); v1 = ag_ssp_base2(v1); }
+              v0 = ag_ssp_base2(v0); v1 = ag_ssp_base2(v1);
               asm volatile("" : "+v"(v0), "+v"(v1));      // keep the softplus here (the IR sinks it to its use otherwise)
               ag_cvt_pair(hidb[m - 1], 2 * t, v0, v1);
             }
@@ -483,7 +441,6 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
         }
         prefetch_next();
       }
-      AG_STAMP(c1); st[1] += c1 - c0; c0 = c1;       // layer 1 + softplus + split (one pipeline)
       // Row masks of the first two targets of the tile, built once per tile: almost every 16-edge tile holds
       // the in-lists of one or two targets (in-degree >= 8), so the per-channel-tile reduction is 8 FMAs and two
       // quarter sums; tiles with more targets take the general loop.
@@ -498,7 +455,7 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
         }
       }
       float* const dp0 = dest_lo(t0, bound(0));
-      const bool fast = ntg <= 2 && !(AG_ABL(32));
+      const bool fast = ntg <= 2;
       const bool two = ntg == 2;
       // Fast reduction (one or two targets in the tile), free of branches so that it can be issued in the shadow
       // of the next channel tile's MFMAs: both masked sums are always formed; the first target's running sum is
@@ -540,16 +497,12 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
           g[b][1] = gl[((2 * pair + b) * 2 + 1) * 64];
         }
       };
-      AG_STAMP(c1); st[2] += c1 - c0; c0 = c1;       // bounds, masks
       // second-layer MFMAs of channel tile nt (flipped: rows = edges, lanes = channels), raw accumulators
       const lds_u32x4* w2a_l = ag_lds_base(w2a, lane);
-      // conv1's 32 second-layer blocks are read from LDS AG_L2_LDS_AHEAD blocks ahead of their MFMAs through a small
+      // conv1's 32 second-layer blocks are read from LDS LA blocks ahead of their MFMAs through a small
       // register ring (left to the compiler, every block's two reads were issued and waited for on the spot: 32
       // exposed LDS round trips per tile)
-#ifndef AG_L2_LDS_AHEAD
-#define AG_L2_LDS_AHEAD 1
-#endif
-      constexpr int LA = AG_L2_LDS_AHEAD, LR = LA + 1;
+      constexpr int LA = 1, LR = LA + 1;
       u32x4 w2q[LR][2];
       auto fetch_w2 = [&](int b) {             // b = nt * 4 + k
         w2q[b % LR][0] = w2a_l[(b * 2) * 64];
@@ -560,19 +513,17 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
       auto dense2 = [&](int nt) -> f32x4 {
         f32x4 z[1] = {{0.f, 0.f, 0.f, 0.f}};
         if (nt == 7) fetch_g(0);
-        if (!(AG_ABL(4))) {
-          if (nt < 8) {
+        if (nt < 8) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              const int b = nt * 4 + k;
-              if (b + LA < 32) fetch_w2(b + LA);
-              ag_block_mma<MODE, true>(z[0], hidb[k], w2q[b % LR]);
-            }
-          } else {
-            ag_block_mma<MODE, true>(z[0], hidb[4], g[0]);
-            ag_block_mma<MODE, true>(z[0], hidb[5], g[1]);
-            if (nt + 1 < AG_CONV_NCH) fetch_g(nt + 1 - 8);
+          for (int k = 0; k < 4; ++k) {
+            const int b = nt * 4 + k;
+            if (b + LA < 32) fetch_w2(b + LA);
+            ag_block_mma<MODE, true>(z[0], hidb[k], w2q[b % LR]);
           }
+        } else {
+          ag_block_mma<MODE, true>(z[0], hidb[4], g[0]);
+          ag_block_mma<MODE, true>(z[0], hidb[5], g[1]);
+          if (nt + 1 < AG_CONV_NCH) fetch_g(nt + 1 - 8);
         }
         return z[0];
       };
@@ -611,17 +562,13 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
             f32x4 t;
 #pragma unroll
             for (int r = 0; r < 4; ++r) t[r] = (zp[r] + bp) * mp[r];
-            if (AG_ABL(16)) {
-              p0[j] = t[0];
-            } else {
-              p0[j] = t[0] * w0[0];
+            p0[j] = t[0] * w0[0];
 #pragma unroll
-              for (int r = 1; r < 4; ++r) p0[j] = fmaf(t[r], w0[r], p0[j]);
-              if constexpr (kTwo) {
-                p1[j] = t[0] * w1[0];
+            for (int r = 1; r < 4; ++r) p0[j] = fmaf(t[r], w0[r], p0[j]);
+            if constexpr (kTwo) {
+              p1[j] = t[0] * w1[0];
 #pragma unroll
-                for (int r = 1; r < 4; ++r) p1[j] = fmaf(t[r], w1[r], p1[j]);
-              }
+              for (int r = 1; r < 4; ++r) p1[j] = fmaf(t[r], w1[r], p1[j]);
             }
             if (j == 3) {      // quarter q ends up with the sums of channel tile 4 g4 + q
               const float r0 = carry[g4] + ag_quarter_reduce_scatter4(p0[0], p0[1], p0[2], p0[3]);
@@ -651,7 +598,6 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
           reduce_general(z, nt, carry[nt >> 2]);
         }
       }
-      AG_STAMP(c1); st[3] += c1 - c0; c0 = c1;       // layer 2 + message + reduction (one pipeline)
       run_t = t1;
     }
     if (run_t >= 0) {
@@ -660,12 +606,6 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
       for (int i = 0; i < AG_CONV_NCH / 4; ++i) dp[16 * (4 * i + (lane0 >> 4)) + (lane0 & 15)] = carry[i];
     }
   }  // chunk loop
-#ifdef AG_CONV_STAMPS
-  if (lane0 == 0) {
-    for (int i = 0; i < 4; ++i) atomicAdd(&ag_conv_stamp_acc[i], st[i]);
-    atomicAdd(&ag_conv_stamp_acc[7], 1ull);
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------ pair head
@@ -824,9 +764,9 @@ struct AttrPolyArgs {
 // length lies in [0, cutoff] -- or in (cutoff, far_hi] when its type has a far set -- and whose type has a slot is evaluated
 // here (features once, one masked MFMA round per coefficient set present in the tile); the other rows are flagged for the
 // encoder MLP (agdiff_local_edge_rows).
-#ifndef AG_ATTRP_WAVES
-#define AG_ATTRP_WAVES 16        // (one 16-wave workgroup per CU: the kernel is bound by its row stores -- 0.055 ms without them, 0.135 with, at 8
-#endif                           // waves; twice the tiles in flight drain them 6 % faster: 0.127 ms for 417 MB on the 196 k-atom batch)
+// One 16-wave workgroup per CU: the kernel is bound by its row stores (0.055 ms without them, 0.135 with, at 8 waves; twice the
+// tiles in flight drain them 6 % faster: 0.127 ms for 417 MB on the 196 k-atom batch).
+#define AG_ATTRP_WAVES 16
 #define AG_ATTRP_MAX_SLOTS 9         // 9 x 16 KiB of coefficients in LDS
 template <int MODE>
 __global__ void __launch_bounds__(64 * AG_ATTRP_WAVES, AG_ATTRP_WAVES / 4) k_edge_attr_poly(AttrPolyArgs a) {
@@ -1037,17 +977,6 @@ __global__ void __launch_bounds__(AG_WG) k_cfconv_aggregate(const float* __restr
 
 }  // namespace
 
-#ifdef AG_CONV_STAMPS
-extern "C" int agdiff_debug_conv_stamps(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ag_conv_stamp_acc), sizeof(ag_conv_stamp_acc)) != hipSuccess) return AGDIFF_ERR_LAUNCH;
-  if (reset) {
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(ag_conv_stamp_acc), z, sizeof(z)) != hipSuccess) return AGDIFF_ERR_LAUNCH;
-  }
-  return AGDIFF_OK;
-}
-#endif
-
 // (set by agdiff_local_edge_rows around its call of agdiff_edge_encoder: the launch then only does the flagged tiles)
 static thread_local const int32_t* g_enc_tile_flags = nullptr;
 
@@ -1063,12 +992,7 @@ extern "C" int agdiff_edge_encoder(const agdiff_params_t* p, const int32_t* n_ed
     GaussArgs g{p->ge_offset, p->ge_emb, n_edges_dev, e_len, e_type, attr_frag, attr_rows, row_index, pos_index, mir_index,
                 max_tiles, p->ge_coeff * 1.44269504088896340736f};
     const dim3 grid((unsigned)((max_tiles + 3) / 4));
-    if (p->precision == AG_H3)
-      k_edge_gaussian<AG_H3><<<grid, dim3(256), 0, (hipStream_t)stream>>>(g);
-    else if (p->precision == AG_BF3)
-      k_edge_gaussian<AG_BF3><<<grid, dim3(256), 0, (hipStream_t)stream>>>(g);
-    else
-      k_edge_gaussian<AG_F32><<<grid, dim3(256), 0, (hipStream_t)stream>>>(g);
+    ag_by_mode(p->precision, [&](auto M) { k_edge_gaussian<decltype(M)::value><<<grid, dim3(256), 0, (hipStream_t)stream>>>(g); });
     AG_CHECK_LAUNCH();
     return AGDIFF_OK;
   }
@@ -1081,12 +1005,9 @@ extern "C" int agdiff_edge_encoder(const agdiff_params_t* p, const int32_t* n_ed
   const size_t smem = (size_t)80 * 2048;     // w1 (32 blocks) + w23 (32) + unit 0 of w4's 32 blocks
   static std::atomic<uint64_t> attr_done{0};
   if (!ag_allow_big_lds(attr_done, smem, k_edge_encoder<AG_BF3>, k_edge_encoder<AG_F32>, k_edge_encoder<AG_H3>)) return AGDIFF_ERR_LAUNCH;
-  if (p->precision == AG_H3)
-    k_edge_encoder<AG_H3><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
-  else if (p->precision == AG_BF3)
-    k_edge_encoder<AG_BF3><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
-  else
-    k_edge_encoder<AG_F32><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
+  ag_by_mode(p->precision, [&](auto M) {
+    k_edge_encoder<decltype(M)::value><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
+  });
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
@@ -1192,29 +1113,15 @@ int launch_cfconv_fused(const agdiff_params_t* p, int32_t k, int64_t max_e, cons
   a.agg_first = agg_first;
   a.max_chunks = max_chunks;
   a.chunk_tiles = chunk_tiles;
-  a.ablate = 0;
-#ifdef AG_CONV_ABLATE
-  {
-    static int abl = -1;
-    if (abl < 0) {
-      const char* e = getenv("AGDIFF_ABLATE");
-      abl = e ? atoi(e) : 0;
-    }
-    a.ablate = abl;
-  }
-#endif
   // persistent launch: one 8-wave workgroup per CU keeps 160 KiB of filter weights in LDS
   int64_t wgs = (max_chunks + AG_CONV_WAVES - 1) / AG_CONV_WAVES;
   if (wgs > 256) wgs = 256;
   const size_t smem = (size_t)AG_CONV_LDS_BLOCKS * 2048;
   static std::atomic<uint64_t> attr_done{0};
   if (!ag_allow_big_lds(attr_done, smem, k_cfconv_fused<AG_BF3>, k_cfconv_fused<AG_F32>, k_cfconv_fused<AG_H3>)) return AGDIFF_ERR_LAUNCH;
-  if (p->precision == AG_H3)
-    k_cfconv_fused<AG_H3><<<dim3((unsigned)wgs), dim3(64 * AG_CONV_WAVES), smem, (hipStream_t)stream>>>(a);
-  else if (p->precision == AG_BF3)
-    k_cfconv_fused<AG_BF3><<<dim3((unsigned)wgs), dim3(64 * AG_CONV_WAVES), smem, (hipStream_t)stream>>>(a);
-  else
-    k_cfconv_fused<AG_F32><<<dim3((unsigned)wgs), dim3(64 * AG_CONV_WAVES), smem, (hipStream_t)stream>>>(a);
+  ag_by_mode(p->precision, [&](auto M) {
+    k_cfconv_fused<decltype(M)::value><<<dim3((unsigned)wgs), dim3(64 * AG_CONV_WAVES), smem, (hipStream_t)stream>>>(a);
+  });
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
@@ -1312,7 +1219,7 @@ int launch_pair_head_poly(const agdiff_params_t* p, const int32_t* n_edges_dev, 
 #undef AG_HEADP_KERNELS
   const dim3 grid((unsigned)wgs), block(64 * AG_PERSIST_WAVES);
   hipStream_t st = (hipStream_t)stream;
-  auto by_terms = [&](auto MODE_) {
+  ag_by_mode(p->precision, [&](auto MODE_) {
     constexpr int MODE = decltype(MODE_)::value;
     switch (p->poly_kt) {
       case 1: k_pair_head_poly<MODE, 1><<<grid, block, smem, st>>>(a); break;
@@ -1320,10 +1227,7 @@ int launch_pair_head_poly(const agdiff_params_t* p, const int32_t* n_edges_dev, 
       case 3: k_pair_head_poly<MODE, 3><<<grid, block, smem, st>>>(a); break;
       default: k_pair_head_poly<MODE, 4><<<grid, block, smem, st>>>(a); break;
     }
-  };
-  if (p->precision == AG_H3) by_terms(std::integral_constant<int, AG_H3>{});
-  else if (p->precision == AG_BF3) by_terms(std::integral_constant<int, AG_BF3>{});
-  else by_terms(std::integral_constant<int, AG_F32>{});
+  });
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
@@ -1364,19 +1268,16 @@ extern "C" int agdiff_local_edge_rows(const agdiff_params_t* p, const agdiff_top
   a.far_hi = a.far_slots > 0 ? p->attr_poly_far_hi : p->cutoff;
   a.two_over_far = a.far_slots > 0 ? 2.0f / (p->attr_poly_far_hi - p->cutoff) : 0.0f;
   int64_t wgs = (ctiles + AG_ATTRP_WAVES - 1) / AG_ATTRP_WAVES;
-  if (wgs > (AG_ATTRP_WAVES >= 16 ? 256 : 512)) wgs = AG_ATTRP_WAVES >= 16 ? 256 : 512;
+  if (wgs > 256) wgs = 256;
   const size_t smem = (size_t)(p->poly_num_slots + a.far_slots) * 8 * 2048;
   static std::atomic<uint64_t> attr_done{0};
   if (!ag_allow_big_lds(attr_done, (size_t)AG_ATTRP_MAX_SLOTS * 8 * 2048, k_edge_attr_poly<AG_BF3>, k_edge_attr_poly<AG_F32>,
                         k_edge_attr_poly<AG_H3>))
     return AGDIFF_ERR_LAUNCH;
   // (the local branch's arithmetic mode: attr_poly_typed_pk is packed in it)
-  if (p->precision_local == AG_H3)
-    k_edge_attr_poly<AG_H3><<<dim3((unsigned)wgs), dim3(64 * AG_ATTRP_WAVES), smem, st>>>(a);
-  else if (p->precision_local == AG_BF3)
-    k_edge_attr_poly<AG_BF3><<<dim3((unsigned)wgs), dim3(64 * AG_ATTRP_WAVES), smem, st>>>(a);
-  else
-    k_edge_attr_poly<AG_F32><<<dim3((unsigned)wgs), dim3(64 * AG_ATTRP_WAVES), smem, st>>>(a);
+  ag_by_mode(p->precision_local, [&](auto M) {
+    k_edge_attr_poly<decltype(M)::value><<<dim3((unsigned)wgs), dim3(64 * AG_ATTRP_WAVES), smem, st>>>(a);
+  });
   AG_CHECK_LAUNCH();
   ag_log_variant(ws, AGDIFF_VAR_ATTR_POLY);
   // the flagged tiles (if any) through the MLP: the launch returns before staging its weights when the count is 0
@@ -1414,12 +1315,9 @@ extern "C" int agdiff_pair_head(const agdiff_head_params_t* hp, const int32_t* n
   if (!ag_allow_big_lds(attr_done, smem, k_pair_head<AG_BF3>, k_pair_head<AG_F32>, k_pair_head<AG_H3>)) return AGDIFF_ERR_LAUNCH;
   // (operand-form edge_attr tiles must have been written in the head's mode: the global encoder writes them in p->precision,
   // which is what head_global carries; head_local reads fp32 rows)
-  if (hp->precision == AG_H3)
-    k_pair_head<AG_H3><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
-  else if (hp->precision == AG_BF3)
-    k_pair_head<AG_BF3><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
-  else
-    k_pair_head<AG_F32><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
+  ag_by_mode(hp->precision, [&](auto M) {
+    k_pair_head<decltype(M)::value><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
+  });
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

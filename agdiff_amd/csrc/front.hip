@@ -380,7 +380,6 @@ __global__ void __launch_bounds__(AG_FRONT_THREADS) k_sampler_front(FrontArgs a)
   __syncthreads();
   // canonical radius edges per target: one of j -> i / i -> j when both are radius edges (the one with src < dst), and
   // every radius edge without such a mirror
-  int wave_ctotal = 0;
   for (int i = wave; i < n; i += nwaves) {
     int cdeg = 0;
     for (int c = 0; 64 * c < n; ++c) {
@@ -390,7 +389,6 @@ __global__ void __launch_bounds__(AG_FRONT_THREADS) k_sampler_front(FrontArgs a)
       cdeg += __popcll(__ballot(canon));
     }
     if (lane == 0) scan_c[i] = cdeg;
-    wave_ctotal += cdeg;
   }
   __syncthreads();
   // inclusive scan of scan_c (n <= 512) by ONE wave: eight consecutive counts per lane, a shuffle scan of the lanes' sums (the

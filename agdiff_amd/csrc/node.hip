@@ -1045,16 +1045,12 @@ extern "C" int agdiff_schnet_node_stage_split(const agdiff_params_t* p, const ag
   if (tiles <= ag_node_split_max_tiles(p)) {       // small batch: four waves per tile (k_schnet_node_stage_split)
     ag_log_variant(ws, AGDIFF_VAR_NODE_SPLIT4);
     const dim3 grid((unsigned)tiles), block(256);
-#define AG_LAUNCH_SPLIT(M)                                                                  \
-    do {                                                                                    \
-      if (a.finish && a.prep) k_schnet_node_stage_split<M, true, true><<<grid, block, 0, st>>>(a);        \
-      else if (a.finish) k_schnet_node_stage_split<M, true, false><<<grid, block, 0, st>>>(a);            \
-      else k_schnet_node_stage_split<M, false, true><<<grid, block, 0, st>>>(a);                          \
-    } while (0)
-    if (p->precision == AG_H3) AG_LAUNCH_SPLIT(AG_H3);
-    else if (p->precision == AG_BF3) AG_LAUNCH_SPLIT(AG_BF3);
-    else AG_LAUNCH_SPLIT(AG_F32);
-#undef AG_LAUNCH_SPLIT
+    ag_by_mode(p->precision, [&](auto M) {
+      constexpr int MODE = decltype(M)::value;
+      if (a.finish && a.prep) k_schnet_node_stage_split<MODE, true, true><<<grid, block, 0, st>>>(a);
+      else if (a.finish) k_schnet_node_stage_split<MODE, true, false><<<grid, block, 0, st>>>(a);
+      else k_schnet_node_stage_split<MODE, false, true><<<grid, block, 0, st>>>(a);
+    });
     AG_CHECK_LAUNCH();
     return AGDIFF_OK;
   }
@@ -1067,16 +1063,11 @@ extern "C" int agdiff_schnet_node_stage_split(const agdiff_params_t* p, const ag
                         k_schnet_node_stage<AG_F32, true>, k_schnet_node_stage<AG_H3, true>))
     return AGDIFF_ERR_LAUNCH;
   const dim3 grid((unsigned)((tiles + waves - 1) / waves)), block(64 * waves);
-  if (p->precision == AG_H3) {
-    if (ldsw) k_schnet_node_stage<AG_H3, true><<<grid, block, smem, st>>>(a);
-    else k_schnet_node_stage<AG_H3, false><<<grid, block, 0, st>>>(a);
-  } else if (p->precision == AG_BF3) {
-    if (ldsw) k_schnet_node_stage<AG_BF3, true><<<grid, block, smem, st>>>(a);
-    else k_schnet_node_stage<AG_BF3, false><<<grid, block, 0, st>>>(a);
-  } else {
-    if (ldsw) k_schnet_node_stage<AG_F32, true><<<grid, block, smem, st>>>(a);
-    else k_schnet_node_stage<AG_F32, false><<<grid, block, 0, st>>>(a);
-  }
+  ag_by_mode(p->precision, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if (ldsw) k_schnet_node_stage<MODE, true><<<grid, block, smem, st>>>(a);
+    else k_schnet_node_stage<MODE, false><<<grid, block, 0, st>>>(a);
+  });
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
@@ -1120,18 +1111,17 @@ extern "C" int agdiff_gin_encoder(const agdiff_params_t* p, const agdiff_topo_t*
     hipStream_t st = (hipStream_t)stream;
     k_gin_gather<<<dim3((unsigned)((((topo->num_nodes + 7) / 8) + 7) / 8 * 8)), dim3(256), 0, st>>>(a);   // grid: multiple of 8 (XCD ranges)
     AG_CHECK_LAUNCH();
-    if (p->precision_local == AG_H3) {
-      if (persistent) k_gin_layer_persistent<AG_H3><<<grid, block, smem, st>>>(a);
-      else if (ldsw) k_gin_layer<AG_H3, true><<<grid, block, smem, st>>>(a);
-      else k_gin_layer<AG_H3, false><<<grid, block, 0, st>>>(a);
-    } else if (p->precision_local == AG_BF3) {
-      if (persistent) k_gin_layer_persistent<AG_BF3><<<grid, block, smem, st>>>(a);
-      else if (ldsw) k_gin_layer<AG_BF3, true><<<grid, block, smem, st>>>(a);
-      else k_gin_layer<AG_BF3, false><<<grid, block, 0, st>>>(a);
-    } else {
-      if (ldsw) k_gin_layer<AG_F32, true><<<grid, block, smem, st>>>(a);
-      else k_gin_layer<AG_F32, false><<<grid, block, 0, st>>>(a);
-    }
+    ag_by_mode(p->precision_local, [&](auto M) {
+      constexpr int MODE = decltype(M)::value;
+      if constexpr (MODE != AG_F32) {         // (no fp32 instance of the persistent kernel)
+        if (persistent) {
+          k_gin_layer_persistent<MODE><<<grid, block, smem, st>>>(a);
+          return;
+        }
+      }
+      if (ldsw) k_gin_layer<MODE, true><<<grid, block, smem, st>>>(a);
+      else k_gin_layer<MODE, false><<<grid, block, 0, st>>>(a);
+    });
     AG_CHECK_LAUNCH();
     in = bufs[cur];
     cur ^= 1;

@@ -3,18 +3,8 @@
 // vectoriser turns the per-row accumulation FMAs into v_pk_fma_f32 fed by register shuffles (358 v_mov per kernel), and
 // packed fp32 next to MFMAs costs issue time instead of saving it (MI355X_MICROARCH.md, per-instruction cycle constants).
 #include "common.hpp"
-#include <type_traits>
 
 #define AG_CONV_NCH 12          // 16-channel tiles of the 192 filter channels (conv1: 0..7, conv2: 8..11)
-
-#ifdef AG_QUAD_STAMPS      // (debug build: start / end clock of every workgroup of the last k_cfconv_quad launch -- tools/quad_stamps.py)
-__device__ unsigned long long ag_quad_stamp[2 * 256];
-extern "C" int agdiff_debug_quad_stamps(unsigned long long* out) {      // (reads the stamps and clears them for the next launch)
-  static unsigned long long zero[2 * 256];
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ag_quad_stamp), sizeof(ag_quad_stamp)) != hipSuccess) return AGDIFF_ERR_LAUNCH;
-  return hipMemcpyToSymbol(HIP_SYMBOL(ag_quad_stamp), zero, sizeof(zero)) == hipSuccess ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;
-}
-#endif
 
 namespace {
 
@@ -85,44 +75,15 @@ struct NodeConvArgs {
 // of two spill 28 registers at 16 waves (1.14 against 1.01 ms per launch); ONE channel tile per group fits with 5 spills under the
 // one-pass plan and wins 4 % on a 36-molecule batch but LOSES 6 % on the default job's batches (0.976 against 0.920 ms).
 // Small launches (fewer than two quads per wave of a full grid: tune_cfconv_four_min_quads) keep the 12-wave shape: more
-// workgroups for the same quads (23 k atoms: even; 4 k atoms: 12 waves 3 % ahead).  -DAG_NODE_GRP / -DAG_NODECONV_WAVES force one
-// shape on every instantiation (A/B builds).
+// workgroups for the same quads (23 k atoms: even; 4 k atoms: 12 waves 3 % ahead).
 template <int NKT, bool FOUR, int PLAN = 0>
 struct NodeConvShape {
-#ifdef AG_NODE_GRP
-  static constexpr int GRP = AG_NODE_GRP;
-#else
   static_assert(!FOUR || NKT == 1, "four waves per SIMD: one k-tile");
-  static constexpr int GRP = (FOUR || NKT >= 3) ? 2 : 3;
-#endif
-#ifdef AG_NODECONV_WAVES
-  static constexpr int WAVES = AG_NODECONV_WAVES;
-#else
-  static constexpr int WAVES = FOUR ? 16 : NKT >= 3 ? 8 : 12;       // (three / four k-tiles: 256 registers per lane)
   static_assert(PLAN >= 0 && PLAN <= 3, "poly_plan");
-#endif
+  static constexpr int GRP = (FOUR || NKT >= 3) ? 2 : 3;
+  static constexpr int WAVES = FOUR ? 16 : NKT >= 3 ? 8 : 12;       // (three / four k-tiles: 256 registers per lane)
 };
-#ifndef AG_NODE_XD
 #define AG_NODE_XD 2                        // x groups in flight (ring of buffers; must divide the number of groups: static indices)
-#endif
-#ifndef AG_NODE_XD_FOUR
-#define AG_NODE_XD_FOUR AG_NODE_XD          // ... of the four-waves-per-SIMD shape (six groups of two channel tiles: 2 or 3)
-#endif
-#ifndef AG_QUAD_META_NT
-#define AG_QUAD_META_NT 0     // radius rows' inputs of k_cfconv_quad: 1 non-temporal loads (as k_cfconv_node), 0 cached
-#endif
-#ifndef AG_QUAD_WAHEAD
-#define AG_QUAD_WAHEAD 0       // k_cfconv_quad: 1 = coefficient blocks read one group ahead of their MFMAs (measured: no gain, 2 spills)
-#endif
-#ifndef AG_QUAD_FEATURES2
-#define AG_QUAD_FEATURES2 1    // k_cfconv_quad: both feature sets of a tile from one routine (ag_poly_features2_mixed)
-#endif
-#ifndef AG_QUAD_STORE_NT
-#define AG_QUAD_STORE_NT 1
-#endif
-#ifndef AG_QUAD_DYNAMIC
-#define AG_QUAD_DYNAMIC 1      // k_cfconv_quad: a workgroup's quads dealt to its waves as they finish (0: quad p_begin + wave, + WAVES, ...)
-#endif
 // PLAN (agdiff_params_t.poly_plan): 0 three passes for every term; 1 one pass for the high terms, whose coefficients the
 // host has bounded -- at NKT 1 two MFMAs per channel tile (hi x hi of all 32 terms, then both cross terms of terms 0..15 in
 // one instruction: ag_poly_features<.., true> / the mixed unit 1 of the blocks), at NKT >= 2 every k-tile but the first by its hi x hi
@@ -222,7 +183,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_node(NodeConvA
     }
   };
   // x[src] values of a group of GRP channel tiles, two groups in flight
-  constexpr int XD = (GRP == 2) ? AG_NODE_XD_FOUR : AG_NODE_XD;
+  constexpr int XD = AG_NODE_XD;
   static_assert((AG_CONV_NCH / GRP) % XD == 0 && XD >= 2, "ring of x buffers");
   f32x4 xg[XD][GRP];
   uint32_t xoff[4];
@@ -396,7 +357,6 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_node(NodeConvA
       have_pf = has_next;
     };
     int j = 0;
-#ifndef AG_NODE_NO_LOCAL        // (timing experiment: the kernel without its local tiles)
     for (; j < c_nL; ++j) {
       // the tile's set: one of the LDS-resident ones, or -- a rare type -- straight from L2; a type without a polynomial ran
       // with scale 0 (next_features) against the radius set
@@ -404,7 +364,6 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_node(NodeConvA
       if (slot >= a.lds_slots) tile(j, reinterpret_cast<const u32x4*>(a.poly_typed) + (size_t)slot * SET + lane, accL);
       else tile(j, wl_l + (size_t)(slot >= 0 ? 1 + slot : 0) * SET, accL);
     }
-#endif
     // (the four targets one after the other through shifting copies: indexing the quad's fields by k would put it in scratch)
     int ta = c_t0, tb = c_t1, tc = c_t2, td = c_t3, na = c_n0, nb = c_n1, nc = c_n2, nd = c_n3;
 #pragma nounroll
@@ -451,14 +410,12 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
   constexpr int NG = AG_CONV_NCH / GRP;
   ag_copy_lds(wl, reinterpret_cast<const u32x4*>(a.poly_rad), SET);
   if (a.lds_slots > 0) ag_copy_lds(wl + SET, reinterpret_cast<const u32x4*>(a.poly_typed), a.lds_slots * SET);
-#if AG_QUAD_DYNAMIC
   // the workgroup's quads are DEALT to its waves as they finish (one LDS counter): a quad has 5 to 13 tiles, and with the static
   // deal (quad p_begin + wave, + WAVES, ...) the slowest wave of a workgroup walked 18..35 % more tiles than the average one
   // (counted on the default job's batches).  A quad's result does not depend on the wave that computes it.
   typedef __attribute__((address_space(3))) int lds_ctr_t;
   lds_ctr_t* next_quad = reinterpret_cast<lds_ctr_t*>(wl + (size_t)(1 + (a.lds_slots > 0 ? a.lds_slots : 0)) * SET) + WAVES * 32;
   if (threadIdx.x == 0) *next_quad = WAVES;
-#endif
   // edge type -> coefficient set, in LDS: a local tile's set is looked up when its features are made, by an LDS read.  (As a second,
   // dependent global load in the tile's prefetch it had to wait for the type to arrive -- and with it, in order, for every gather
   // in flight: a local tile cost 1.5 x a radius tile, tools/quad_stamps.py.)
@@ -512,7 +469,6 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
   int pf_src[4] = {0, 0, 0, 0};
   auto ldf = [](const float* base, uint32_t byte_off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off); };
   auto ldi = [](const int32_t* base, uint32_t byte_off) { return *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(base) + byte_off); };
-  [[maybe_unused]] auto ldf_nt = [](const float* base, uint32_t byte_off) { return __builtin_nontemporal_load(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off)); };
   auto prefetch_local = [&](int rows) {
     const uint32_t e4 = (uint32_t)(rows + col) * 4u;
     const uint32_t r16 = (uint32_t)(rows + 4 * q) * 4u;
@@ -530,24 +486,17 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
     const int rbq = qi[slot * 16 + q], rbc = qi[slot * 16 + cq], cnt = qi[slot * 16 + 4 + cq];
     const uint32_t e4 = (uint32_t)(rbc + 4 * t + cr) * 4u;
     const uint32_t r16 = (uint32_t)(rbq + 4 * t) * 4u;
-#if AG_QUAD_META_NT
-    const u32x4 s4 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(a.rad_src) + r16));
-    pf_d = ldf_nt(a.rad_len, e4);
-    pf_s1 = ldf_nt(a.r_scale1, e4);
-    pf_s2 = ldf_nt(a.r_scale2, e4);
-#else
     // (cached: a quarter's four rows are a quarter of a line, the next three tiles read the rest of it)
     const u32x4 s4 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(a.rad_src) + r16);
     pf_d = ldf(a.rad_len, e4);
     pf_s1 = ldf(a.r_scale1, e4);
     pf_s2 = ldf(a.r_scale2, e4);
-#endif
 #pragma unroll
     for (int r = 0; r < 4; ++r) pf_src[r] = (int)s4[r];
     pf_slot = -1;
     pf_dead = 4 * t + cr >= cnt;
   };
-  constexpr int XD = (GRP == 2) ? AG_NODE_XD_FOUR : AG_NODE_XD;
+  constexpr int XD = AG_NODE_XD;
   static_assert((AG_CONV_NCH / GRP) % XD == 0 && XD >= 2, "ring of x buffers");
   f32x4 xg[XD][GRP];
   uint32_t xoff[4];
@@ -570,9 +519,8 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
     ag_static_for<0, XD - 1>([&](auto G) { fetch_xg(G, decltype(G)::value); });
   };
   const lds_u32x4* wl_l = wl + lane;
-  // The coefficient blocks of a group of GRP channel tiles (pk [12][NKT]: block ct * NKT + t) are read into `w` ONE GROUP AHEAD of
-  // their MFMAs -- straight after the MFMAs of the group before have issued, into the registers those have just read -- so that the
-  // LDS round trip runs beside the sums of the group before instead of in front of the MFMAs that wait for it.
+  // The coefficient blocks of a group of GRP channel tiles (pk [12][NKT]: block ct * NKT + t), read into `w` in front of the group's
+  // MFMAs.  (Read one group ahead, beside the sums of the group before, they were measured at no gain and 2 spilled registers.)
   u32x4 w[GRP][NKT][2];
   auto load_w = [&](auto base, auto GG) {
     constexpr int C0 = GRP * decltype(GG)::value;
@@ -618,7 +566,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
       pf_slot = loc ? (sl < 0 ? -2 : sl) : pf_slot;
     }
     const float s1 = pf_dead ? 0.0f : pf_s1, s2 = pf_dead ? 0.0f : pf_s2;
-    if constexpr (MIXED && AG_QUAD_FEATURES2) {
+    if constexpr (MIXED) {
       ag_poly_features2_mixed<MODE>(pf_d, a.two_over_rc, q, ph1[0], s1, ph2[0], s2);
     } else {
       ag_poly_features<MODE, NKT, MIXED>(pf_d, a.two_over_rc, q, ph1, s1);
@@ -627,9 +575,6 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
   };
   float acc[AG_CONV_NCH];
 
-#ifdef AG_QUAD_STAMPS
-  if (threadIdx.x == 0 && gridDim.x <= 256) ag_quad_stamp[2 * blockIdx.x] = wall_clock64();
-#endif
   int p = p_begin + wave;
   if (p >= p_end) return;                       // (no barrier below)
   AG_RQ_DECL(c_);
@@ -637,13 +582,9 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
   AG_RQ_LOAD(c_, p, 0);
   bool have_pf = false;
   while (p < p_end) {
-#if AG_QUAD_DYNAMIC
     int take = 0;
     if (lane == 0) take = __hip_atomic_fetch_add(next_quad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     const int pn = p_begin + __builtin_amdgcn_readfirstlane(take);
-#else
-    const int pn = p + WAVES;
-#endif
     AG_RQ_DECL(x_);
     if (pn < p_end) AG_RQ_LOAD(x_, pn, cslot ^ 1);
     const int ntiles = c_nL + c_nR;
@@ -672,7 +613,6 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
     // every outstanding load would have to land).
     auto tile = [&](int j, auto base) {
       const bool has_next = (j + 1 < ntiles) || ntiles_next > 0;
-      if (AG_QUAD_WAHEAD) load_w(base, std::integral_constant<int, 0>{});
       prefetch_tile(has_next ? j + 1 : j);
       auto sums = [&](auto GG, const f32x4 (&z)[GRP]) {
         constexpr int gg = decltype(GG)::value;
@@ -687,17 +627,13 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
       };
       f32x4 z[2][GRP];
       fetch_xg(std::integral_constant<int, XD - 1>{}, XD - 1);
-      if (!AG_QUAD_WAHEAD) load_w(base, std::integral_constant<int, 0>{});
+      load_w(base, std::integral_constant<int, 0>{});
       mma_w(std::integral_constant<int, 0>{}, z[0]);
-      if (AG_QUAD_WAHEAD) load_w(base, std::integral_constant<int, 1>{});
       __builtin_amdgcn_sched_barrier(0);
       ag_static_for<1, NG>([&](auto G) {
         constexpr int g = decltype(G)::value;
-        if (!AG_QUAD_WAHEAD) load_w(base, G);
+        load_w(base, G);
         mma_w(G, z[g & 1]);
-        if constexpr (g + 1 < NG) {
-          if (AG_QUAD_WAHEAD) load_w(base, std::integral_constant<int, g + 1>{});
-        }
         sums(std::integral_constant<int, g - 1>{}, z[(g - 1) & 1]);
         if constexpr (g + XD - 1 < NG) {
           fetch_xg(std::integral_constant<int, (g - 1) % XD>{}, g + XD - 1);
@@ -724,20 +660,13 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES / 4) k_cfconv_quad(NodeConvA
       char* dp = reinterpret_cast<char*>(a.agg) + (uint32_t)(aoff + col * 4);
 #pragma unroll
       for (int ct = 0; ct < AG_CONV_NCH; ++ct)
-#if AG_QUAD_STORE_NT
         __builtin_nontemporal_store(a.unscale * acc[ct], reinterpret_cast<float*>(dp + 64 * ct));
-#else
-        *reinterpret_cast<float*>(dp + 64 * ct) = a.unscale * acc[ct];
-#endif
     }
     if (ntiles == 0) have_pf = false;
     p = pn;
     c_nL = x_nL, c_lt0 = x_lt0, c_nR = x_nR;
     cslot ^= 1;
   }
-#ifdef AG_QUAD_STAMPS      // (the workgroup's LAST wave to pass here leaves the latest clock)
-  if (lane == 0 && gridDim.x <= 256) atomicMax(&ag_quad_stamp[2 * blockIdx.x + 1], (unsigned long long)wall_clock64());
-#endif
 #undef AG_RQ_DECL
 #undef AG_RQ_LOAD
 }
@@ -836,17 +765,15 @@ extern "C" int agdiff_cfconv_node(const agdiff_params_t* p, const agdiff_topo_t*
                          (a.lds_slots < a.num_slots ? AGDIFF_VAR_POLY_L2_SETS : 0) | (four ? AGDIFF_VAR_CFCONV_NODE_FOUR : 0) |
                          (quad ? AGDIFF_VAR_CFCONV_NODE_QUAD : 0));
   const int plan = p->poly_plan;
-  auto by_terms = [&](auto MODE_, int pl) {
+  return ag_by_mode(p->precision, [&](auto MODE_) {
     constexpr int MODE = decltype(MODE_)::value;
+    const int pl = MODE == AG_F32 ? 0 : plan;
     switch (p->poly_kt) {
       case 1: return launch_cfconv_node_t<MODE, 1>(a, pl, four, quad, smem, stream);
       case 2: return launch_cfconv_node_t<MODE, 2>(a, pl, four, quad, smem, stream);
       case 3: return launch_cfconv_node_t<MODE, 3>(a, pl, four, quad, smem, stream);
       default: return launch_cfconv_node_t<MODE, 4>(a, pl, four, quad, smem, stream);
     }
-  };
-  if (p->precision == AG_H3) return by_terms(std::integral_constant<int, AG_H3>{}, plan);
-  if (p->precision == AG_BF3) return by_terms(std::integral_constant<int, AG_BF3>{}, plan);
-  return by_terms(std::integral_constant<int, AG_F32>{}, 0);
+  });
 }
 

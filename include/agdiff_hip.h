@@ -141,7 +141,7 @@ typedef struct agdiff_head_params {
                                 (agdiff_params_t.poly_kt) */
   float b3;
   int32_t act;               /* AGDIFF_ACT_*: config.mlp_act, the activation between the head's layers (models/common.py:62-66:
-                                getattr(F, name); configs/*.yml: relu) */
+                                getattr(F, name); the shipped configs: relu) */
   int32_t precision;         /* as agdiff_params_t.precision, or 2 (split-fp16: only with attr_rows) */
   int32_t pad0;
   int32_t* range_rows;       /* as agdiff_ws_t.range_rows (the head's hidden layer; an edge flags its source node), or null.

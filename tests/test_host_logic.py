@@ -1,7 +1,11 @@
 """CPU: host-side logic of the product (module tree / state_dict layout, weight packing and
 folding, topology building, C-ABI loading).  No GPU compute calls."""
 import ctypes
+import glob
 import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -870,3 +874,31 @@ def test_quad_cut_owners_name_both_sides_of_every_workgroup_range_cut():
     wg_of = np.searchsorted(w, np.arange(tp.Q), side="right") - 1
     two = {int(g) for g in np.unique(qg) if np.unique(wg_of[qg == g]).size > 1}
     assert two == set(straddling.tolist())
+
+
+_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_kernel_sources_have_no_build_switches():
+    """One shipped form per kernel: no preprocessor conditional of the product sources names an AG_ macro.  The timing and
+    diagnostic branches live in tools/ablations/timing_branches.patch."""
+    csrc = os.path.join(_REPO, "agdiff_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "common.hpp"),
+                                                              os.path.join(_REPO, "include", "agdiff_hip.h")]
+    assert len(files) == 9
+    cond = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b.*\bAG_")
+    hits = ["%s:%d: %s" % (os.path.basename(f), i + 1, l.strip()) for f in files for i, l in enumerate(open(f)) if cond.match(l)]
+    assert not hits, hits
+
+
+def test_timing_branches_patch_applies_to_the_product_sources(tmp_path):
+    """tools/build_variant.sh builds every variant from a copy of agdiff_amd/csrc with tools/ablations/timing_branches.patch
+    applied: the patch must apply to the product sources as they are, without fuzz."""
+    exe = shutil.which("patch")
+    if exe is None:
+        pytest.skip("patch is not installed")
+    shutil.copytree(os.path.join(_REPO, "agdiff_amd", "csrc"), str(tmp_path / "agdiff_amd" / "csrc"),
+                    ignore=shutil.ignore_patterns("_build"))
+    with open(os.path.join(_REPO, "tools", "ablations", "timing_branches.patch")) as f:
+        r = subprocess.run([exe, "-p1", "--dry-run", "--fuzz=0"], stdin=f, cwd=str(tmp_path), capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr

@@ -1,4 +1,5 @@
-"""Diagnostic: per-phase wave-cycle shares of k_cfconv_fused (needs `make -C agdiff_amd/csrc clean all EXTRA=-DAG_CONV_STAMPS`)."""
+"""Diagnostic: per-phase wave-cycle shares of k_cfconv_fused, from a diagnostic build of edge.hip:
+   bash tools/build_variant.sh edge.hip stamps -DAG_CONV_STAMPS;  AGDIFF_LIB=$PWD/_ab/lib_stamps.so python tools/conv_stamps.py"""
 import ctypes, json, subprocess, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

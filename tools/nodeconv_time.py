@@ -92,15 +92,4 @@ pk.set_tuning(poly_lds_sets=0)
 out["node_stage_x%d_ms" % (nc + 1)] = timeit(lambda: [lib.agdiff_schnet_node_stage_split(P, Tp, Wp, k, 1, st) for k in range(nc + 1)])
 out["scales_radius_ms"] = timeit(lambda: lib.agdiff_edge_scales_split(P, Tp, Wp, 0, st))
 out["graph_build_ms"] = timeit(lambda: lib.agdiff_graph_build_ex(Tp, Wp, run.pos_p, ctypes.c_float(cfg.cutoff), 1, st))
-if hasattr(lib, "agdiff_debug_node_stamps"):      # diagnostic build (-DAG_NODE_STAMPS): where a wave's time goes in a radius tile
-    buf = (ctypes.c_uint64 * 8)()
-    pk.set_tuning(local_poly_off=1)
-    lib.agdiff_debug_node_stamps(None, 1)
-    lib.agdiff_cfconv_node(P, Tp, Wp, 0, st)
-    torch.cuda.synchronize()
-    lib.agdiff_debug_node_stamps(buf, 1)
-    v = list(buf)
-    out["stamps_radius_only"] = {"cycles_per_tile_by_step": [x / max(v[5], 1) for x in v[:5]], "tiles": v[5],
-                                 "clock_GHz": v[7] / max(v[6], 1) * 0.1}
-    pk.set_tuning(local_poly_off=0)
 print(json.dumps(out))
