@@ -396,6 +396,336 @@ __global__ void k_local_lengths(const int32_t* __restrict__ src, const int32_t* 
   }
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The same graph for molecules of ANY size (agdiff_graph_build_large): no adjacency is stored, in LDS or anywhere else.
+// One integer per atom replaces a mask row: thr[i] = index (inside the molecule) of target i's 33rd in-range candidate, or
+// INT_MAX when it has fewer.  The radius edge j -> i then exists iff d2(i, j) < r^2 and j <= thr[i] and j != i, and d2 is
+// symmetric bit for bit ((a - b)^2 == (b - a)^2), so both a target's row (its in-edges, and for each the mirror test "does
+// i -> j exist") and a source's column (its out-edges: out-degree, ref2dst) are decided from positions + thr[] + the static
+// local lists (in-list of i: loc_in_ptr / loc_in_eid / loc_src, sources ascending; out-list of i: the local edges
+// [loc_out_ptr[i], loc_out_ptr[i + 1]), targets ascending), which the walk follows with two cursors.
+//
+// Grid: the ATOMS of the batch in blocks of AG_LG_TARGETS, whatever molecule they belong to (a wave finds its atom's molecule
+// by bisection of graph_ptr), one wave per atom at a time, 64 candidates per ballot: a 4096-atom molecule is spread over 256
+// workgroups.  Positions are read from global memory, not staged in LDS: a workgroup's atoms may belong to several
+// molecules, a molecule's block (12 B per atom, 48 KB at 4096 atoms) stays in L2 while its workgroups run, and the 64 lanes
+// of a chunk read 768 consecutive bytes.
+// Launches: thr -> degrees (row walk: in / canonical, column walk: out) -> exclusive scans over ALL atoms (in_ptr, out_ptr
+// and the canonical offsets are plain prefix sums in atom order: no per-molecule base, no atomics, nothing depends on the
+// order in which workgroups arrive) -> fill (row walk again) -> ref2dst and the mirrors' positions (column walk + bisection
+// of the finished in-lists).  Scratch: ws->g_deg holds thr[], ws->g_cdeg the canonical degrees and then their scan.
+#define AG_LG_THREADS 256
+#define AG_LG_TARGETS 16
+#define AG_LG_NO_THR 0x7fffffff
+#define AG_LG_MIRROR_PENDING (-2)
+
+struct LargeArgs {
+  GraphArgs g;
+  const int32_t* loc_out_ptr;
+  const int32_t* loc_dst;
+  int32_t* thr;        // [N] ws->g_deg
+  int32_t* cscan;      // [N] ws->g_cdeg
+  int32_t* num_edges;
+  int32_t* num_canon;
+  int32_t num_nodes;
+  int32_t max_edges;
+};
+
+__device__ __forceinline__ int lg_graph_of(const int32_t* __restrict__ gp, int G, int node) {
+  int lo = 0, hi = G;                       // gp[lo] <= node < gp[hi]; empty graphs (gp[g] == gp[g + 1]) are stepped over
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (gp[mid] <= node) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// position of source `key` in the finished in-list [lo, hi) of a target (sources ascending; the edge exists)
+__device__ __forceinline__ int lg_find(const int32_t* __restrict__ e_src, int lo, int hi, int key) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (e_src[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(AG_LG_THREADS) k_lg_thr(LargeArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int t = wave; t < AG_LG_TARGETS; t += AG_LG_THREADS / 64) {
+    const int gi = blockIdx.x * AG_LG_TARGETS + t;
+    if (gi >= a.num_nodes) break;
+    const int g = lg_graph_of(a.g.graph_ptr, a.g.num_graphs, gi);
+    const int g0 = a.g.graph_ptr[g], n = a.g.graph_ptr[g + 1] - g0;
+    const float xi = a.g.pos[3 * (size_t)gi], yi = a.g.pos[3 * (size_t)gi + 1], zi = a.g.pos[3 * (size_t)gi + 2];
+    int cnt = 0, thr = AG_LG_NO_THR;
+    for (int c = 0; 64 * c < n; ++c) {
+      const int j = 64 * c + lane;
+      const bool valid = j < n;
+      const size_t jj = (size_t)g0 + (valid ? j : 0);
+      const float d2 = dist2_nofma(xi, yi, zi, a.g.pos[3 * jj], a.g.pos[3 * jj + 1], a.g.pos[3 * jj + 2]);
+      const bool within = valid && d2 < a.g.r2;
+      const uint64_t wmask = __ballot(within);
+      if (cnt + __popcll(wmask) >= AGDIFF_RADIUS_CAP) {
+        const uint64_t hit = __ballot(within && cnt + __popcll(wmask & lt) == AGDIFF_RADIUS_CAP - 1);
+        thr = 64 * c + __builtin_ctzll(hit);
+        break;
+      }
+      cnt += __popcll(wmask);
+    }
+    if (lane == 0) a.thr[gi] = thr;
+  }
+}
+
+// The column of source atom gs (lanes = targets, ascending): OUT-degree, and with REF the (src, dst)-order permutation.
+template <bool REF>
+__device__ __forceinline__ int lg_column(const LargeArgs& a, int gs, int g0, int n, int lane, uint64_t lt) {
+  const int s = gs - g0;
+  const float xs = a.g.pos[3 * (size_t)gs], ys = a.g.pos[3 * (size_t)gs + 1], zs = a.g.pos[3 * (size_t)gs + 2];
+  int ok = a.loc_out_ptr[gs];
+  const int ok1 = a.loc_out_ptr[gs + 1];
+  int q0 = REF ? a.g.out_ptr[gs] : 0, outdeg = 0;
+  // (the cursor's next entry is kept in a register: a chunk without local entries then costs no dependent load)
+  int next_d = ok < ok1 ? a.loc_dst[ok] - g0 : AG_LG_NO_THR;
+  for (int c = 0; 64 * c < n; ++c) {
+    uint64_t omask = 0;
+    while (next_d < 64 * (c + 1)) {
+      omask |= 1ull << (next_d - 64 * c);
+      ++ok;
+      next_d = ok < ok1 ? a.loc_dst[ok] - g0 : AG_LG_NO_THR;
+    }
+    const int i = 64 * c + lane;
+    const bool valid = i < n;
+    const size_t ii = (size_t)g0 + (valid ? i : 0);
+    const float d2 = dist2_nofma(a.g.pos[3 * ii], a.g.pos[3 * ii + 1], a.g.pos[3 * ii + 2], xs, ys, zs);
+    const bool rad = valid && d2 < a.g.r2 && i != s && s <= a.thr[ii];
+    const bool e = rad || ((omask >> lane) & 1ull);
+    const uint64_t xmask = __ballot(e);
+    if (REF && e) {
+      const int q = q0 + __popcll(xmask & lt);
+      if (q < a.max_edges) a.g.ref2dst[q] = lg_find(a.g.e_src, a.g.in_ptr[ii], a.g.in_ptr[ii + 1], gs);
+    }
+    q0 += __popcll(xmask);
+    outdeg += __popcll(xmask);
+  }
+  return outdeg;
+}
+
+// The row of target atom gi (lanes = candidate sources, ascending): in-degree and canonical in-degree; with FILL the lists.
+template <bool FILL>
+__device__ __forceinline__ void lg_row(const LargeArgs& a, const float* sseg, int gi, int g0, int n, int lane, uint64_t lt,
+                                       int& deg_out, int& cdeg_out) {
+  const int i = gi - g0;
+  const float xi = a.g.pos[3 * (size_t)gi], yi = a.g.pos[3 * (size_t)gi + 1], zi = a.g.pos[3 * (size_t)gi + 2];
+  const int thr_i = a.thr[gi];
+  int lk = a.g.loc_in_ptr[gi], ok = a.loc_out_ptr[gi];
+  const int lk1 = a.g.loc_in_ptr[gi + 1], ok1 = a.loc_out_ptr[gi + 1];
+  // candidates beyond both the threshold and the last local source cannot be edges
+  const int last_loc = lk1 > lk ? a.g.loc_src[a.g.loc_in_eid[lk1 - 1]] - g0 : -1;
+  const int upper = max(min(thr_i, n - 1), last_loc);
+  int p0 = FILL ? a.g.in_ptr[gi] : 0, cp0 = FILL ? a.cscan[gi] : 0;
+  int rp0 = gi * AGDIFF_RAD_STRIDE;
+  int deg = 0, cdeg = 0;
+  // (both cursors' next entries are kept in registers: a chunk without local entries costs no dependent load)
+  int next_s = lk < lk1 ? a.g.loc_src[a.g.loc_in_eid[lk]] - g0 : AG_LG_NO_THR;
+  int next_d = ok < ok1 ? a.loc_dst[ok] - g0 : AG_LG_NO_THR;
+  for (int c = 0; 64 * c <= upper; ++c) {
+    uint64_t lmask = 0, omask = 0;
+    int nk = lk;
+    while (next_s < 64 * (c + 1)) {
+      lmask |= 1ull << (next_s - 64 * c);
+      ++nk;
+      next_s = nk < lk1 ? a.g.loc_src[a.g.loc_in_eid[nk]] - g0 : AG_LG_NO_THR;
+    }
+    int no = ok;
+    while (next_d < 64 * (c + 1)) {
+      omask |= 1ull << (next_d - 64 * c);
+      ++no;
+      next_d = no < ok1 ? a.loc_dst[no] - g0 : AG_LG_NO_THR;
+    }
+    const int j = 64 * c + lane;
+    const bool valid = j < n;
+    const size_t jj = (size_t)g0 + (valid ? j : 0);
+    const float d2 = dist2_nofma(xi, yi, zi, a.g.pos[3 * jj], a.g.pos[3 * jj + 1], a.g.pos[3 * jj + 2]);
+    const bool within = valid && d2 < a.g.r2 && j != i;
+    const bool lin = (lmask >> lane) & 1ull, lout = (omask >> lane) & 1ull;
+    const bool e = lin || (within && j <= thr_i);
+    const uint64_t emask = __ballot(e);
+    const uint64_t rmask = emask & ~lmask;
+    // the edge the other way round, i -> j
+    const bool rout = e && within && i <= a.thr[jj];
+    int ty = 0, eid = -1;
+    if (lin) {
+      eid = a.g.loc_in_eid[lk + __popcll(lmask & lt)];
+      ty = a.g.loc_type[eid];
+    }
+    bool mir, canon;
+    if (a.g.canon_radius_only) {
+      const bool rad = e && !lin;
+      mir = rad && rout && !lout;
+      canon = rad && (j < i || !mir);
+    } else {
+      mir = e && (rout || lout) && lin == lout && (!lin || ty == a.g.loc_type[ok + __popcll(omask & lt)]);
+      canon = e && (j < i || !mir);
+    }
+    const uint64_t cmask = __ballot(canon);
+    if (FILL && e) {
+      const int p = p0 + __popcll(emask & lt);
+      const float len = ag_sqrt_rn(d2);
+      if (p < a.max_edges) {
+        a.g.e_loc[p] = eid >= 0 ? a.g.loc_row[eid] : -1;
+        a.g.e_src[p] = g0 + j;
+        a.g.e_dst[p] = gi;
+        a.g.e_type[p] = ty;
+        a.g.e_len[p] = len;
+      }
+      if (a.g.rad_cnt && eid < 0) {
+        const int rp = rp0 + __popcll(rmask & lt);
+        a.g.rad_src[rp] = g0 + j;
+        a.g.rad_len[rp] = len;
+        if (a.g.r_scale) {
+          const float C = cf_envelope(len, a.g.cutoff, a.g.smooth);
+          for (int cc = 0; cc < a.g.n_scales; ++cc) a.g.r_scale[(size_t)cc * a.g.rpad + rp] = cf_dist_weight(sseg + cc * 100, len) * C;
+        }
+      }
+      if (canon) {
+        const int cp = cp0 + __popcll(cmask & lt);
+        if (cp < a.max_edges) {
+          a.g.c_len[cp] = len;
+          a.g.c_type[cp] = ty;
+          a.g.c_src[cp] = g0 + j;
+          a.g.c_dst[cp] = gi;
+          a.g.c_pos[cp] = p;
+          a.g.c_mir[cp] = mir ? AG_LG_MIRROR_PENDING : -1;      // (k_lg_ref looks the position up once every list is written)
+        }
+      }
+    }
+    p0 += __popcll(emask);
+    cp0 += __popcll(cmask);
+    rp0 += __popcll(rmask);
+    deg += __popcll(emask);
+    cdeg += __popcll(cmask);
+    lk = nk;
+    ok = no;
+  }
+  if (FILL && a.g.rad_cnt) {
+    const int cnt = rp0 - gi * AGDIFF_RAD_STRIDE;
+    if (lane == 0) a.g.rad_cnt[gi] = cnt;
+    if (a.g.r_scale && lane < ((cnt + AG_TW - 1) / AG_TW) * AG_TW - cnt) {     // pad rows, as k_graph writes them
+      const int rp = rp0 + lane;
+      a.g.rad_src[rp] = gi;
+      a.g.rad_len[rp] = 0.0f;
+      for (int cc = 0; cc < a.g.n_scales; ++cc) a.g.r_scale[(size_t)cc * a.g.rpad + rp] = 0.0f;
+    }
+  }
+  deg_out = deg;
+  cdeg_out = cdeg;
+}
+
+__global__ void __launch_bounds__(AG_LG_THREADS) k_lg_count(LargeArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int t = wave; t < AG_LG_TARGETS; t += AG_LG_THREADS / 64) {
+    const int gi = blockIdx.x * AG_LG_TARGETS + t;
+    if (gi >= a.num_nodes) break;
+    const int g = lg_graph_of(a.g.graph_ptr, a.g.num_graphs, gi);
+    const int g0 = a.g.graph_ptr[g], n = a.g.graph_ptr[g + 1] - g0;
+    int deg, cdeg;
+    lg_row<false>(a, nullptr, gi, g0, n, lane, lt, deg, cdeg);
+    const int outdeg = lg_column<false>(a, gi, g0, n, lane, lt);
+    if (lane == 0) {            // counts now, offsets after k_lg_scan
+      a.g.in_ptr[gi] = deg;
+      a.g.out_ptr[gi] = outdeg;
+      a.cscan[gi] = cdeg;
+    }
+  }
+}
+
+// Exclusive scans over all N atoms, in place: block 0 in-degrees -> in_ptr[N + 1] (total -> num_edges), block 1 out-degrees ->
+// out_ptr[N + 1], block 2 canonical degrees -> cscan[N] (total -> num_canon).  Every thread owns a run of consecutive atoms.
+__global__ void __launch_bounds__(1024) k_lg_scan(LargeArgs a) {
+  int32_t* arr = blockIdx.x == 0 ? a.g.in_ptr : blockIdx.x == 1 ? a.g.out_ptr : a.cscan;
+  const int N = a.num_nodes;
+  const int per = (N + 1023) / 1024;
+  const int lo = min((int)threadIdx.x * per, N), hi = min(lo + per, N);
+  int sum = 0;
+  for (int k = lo; k < hi; ++k) sum += arr[k];
+  __shared__ int wtot[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int s = sum;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(s, o);
+    if (lane >= o) s += u;
+  }
+  if (lane == 63) wtot[wv] = s;
+  __syncthreads();
+  int run = s - sum;
+  for (int w = 0; w < wv; ++w) run += wtot[w];
+  for (int k = lo; k < hi; ++k) {
+    const int v = arr[k];
+    arr[k] = run;
+    run += v;
+  }
+  if (threadIdx.x == 1023) {
+    if (blockIdx.x < 2) arr[N] = run;
+    if (blockIdx.x == 0) *a.num_edges = run;
+    if (blockIdx.x == 2) *a.num_canon = run;
+  }
+}
+
+__global__ void __launch_bounds__(AG_LG_THREADS) k_lg_fill(LargeArgs a) {
+  __shared__ float sseg[2 * AGDIFF_MAX_CONVS * 100];
+  if (a.g.r_scale) {
+    for (int i = threadIdx.x; i < a.g.n_scales * 100; i += blockDim.x) sseg[i] = a.g.dw[i / 100][i % 100];
+    __syncthreads();
+  }
+  // the per-molecule views of the scans
+  const int N = a.num_nodes, G = a.g.num_graphs;
+  for (int g = blockIdx.x * AG_LG_THREADS + threadIdx.x; g <= G; g += gridDim.x * AG_LG_THREADS) {
+    const int n0 = a.g.graph_ptr[g];
+    const int e0 = a.g.in_ptr[n0], c0 = n0 < N ? a.cscan[n0] : *a.num_canon;
+    const_cast<int32_t*>(a.g.graph_edge_ptr)[g] = e0;
+    const_cast<int32_t*>(a.g.graph_canon_ptr)[g] = c0;
+    if (g < G) {
+      const int n1 = a.g.graph_ptr[g + 1];
+      a.g.graph_edge_cnt[g] = a.g.in_ptr[n1] - e0;
+      a.g.graph_canon_cnt[g] = (n1 < N ? a.cscan[n1] : *a.num_canon) - c0;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int t = wave; t < AG_LG_TARGETS; t += AG_LG_THREADS / 64) {
+    const int gi = blockIdx.x * AG_LG_TARGETS + t;
+    if (gi >= N) break;
+    const int g = lg_graph_of(a.g.graph_ptr, G, gi);
+    const int g0 = a.g.graph_ptr[g], n = a.g.graph_ptr[g + 1] - g0;
+    int deg, cdeg;
+    lg_row<true>(a, sseg, gi, g0, n, lane, lt, deg, cdeg);
+  }
+}
+
+__global__ void __launch_bounds__(AG_LG_THREADS) k_lg_ref(LargeArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  const int N = a.num_nodes;
+  for (int t = wave; t < AG_LG_TARGETS; t += AG_LG_THREADS / 64) {
+    const int gi = blockIdx.x * AG_LG_TARGETS + t;
+    if (gi >= N) break;
+    const int g = lg_graph_of(a.g.graph_ptr, a.g.num_graphs, gi);
+    const int g0 = a.g.graph_ptr[g], n = a.g.graph_ptr[g + 1] - g0;
+    lg_column<true>(a, gi, g0, n, lane, lt);
+  }
+  // the canonical entries of this block's targets: the mirror i -> j of the canonical edge j -> i sits in j's in-list
+  const int a0 = blockIdx.x * AG_LG_TARGETS, a1 = min(a0 + AG_LG_TARGETS, N);
+  const int c0 = a.cscan[a0], c1 = min(a1 < N ? a.cscan[a1] : *a.num_canon, a.max_edges);
+  for (int cp = c0 + (int)threadIdx.x; cp < c1; cp += AG_LG_THREADS)
+    if (a.g.c_mir[cp] == AG_LG_MIRROR_PENDING) {
+      const int j = a.g.c_src[cp];
+      a.g.c_mir[cp] = lg_find(a.g.e_src, a.g.in_ptr[j], a.g.in_ptr[j + 1], a.g.c_dst[cp]);
+    }
+}
+
 }  // namespace
 
 extern "C" int agdiff_graph_build(const agdiff_topo_t* topo, const agdiff_ws_t* ws, const float* pos, float cutoff,
@@ -405,7 +735,7 @@ extern "C" int agdiff_graph_build(const agdiff_topo_t* topo, const agdiff_ws_t* 
 
 namespace {
 int graph_build_impl(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, const float* pos, float cutoff,
-                     int32_t canon_radius_only, void* stream);
+                     int32_t canon_radius_only, void* stream, bool force_large = false);
 }
 
 extern "C" int agdiff_graph_build_ex(const agdiff_topo_t* topo, const agdiff_ws_t* ws, const float* pos, float cutoff,
@@ -419,9 +749,53 @@ extern "C" int agdiff_graph_build_scaled(const agdiff_params_t* p, const agdiff_
   return graph_build_impl(p, topo, ws, pos, cutoff, canon_radius_only, stream);
 }
 
+extern "C" int agdiff_graph_build_large(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws,
+                                        const float* pos, float cutoff, int32_t canon_radius_only, void* stream) {
+  if (p && (!ws || !ws->r_scale || !ws->rad_cnt || p->num_convs > AGDIFF_MAX_CONVS)) return AGDIFF_ERR_ARG;
+  return graph_build_impl(p, topo, ws, pos, cutoff, canon_radius_only, stream, true);
+}
+
+extern "C" int agdiff_graph_large_grid(const agdiff_topo_t* topo, int64_t* out) {
+  if (!topo || !out || topo->num_nodes <= 0) return AGDIFF_ERR_ARG;
+  out[0] = (topo->num_nodes + AG_LG_TARGETS - 1) / AG_LG_TARGETS;
+  out[1] = AG_LG_TARGETS;
+  return AGDIFF_OK;
+}
+
 namespace {
+// agdiff_graph_build_large's five launches (`a` filled by graph_build_impl)
+int graph_build_large(const GraphArgs& ga, const agdiff_topo_t* topo, const agdiff_ws_t* ws, hipStream_t st) {
+  if (!ws->g_deg || !ws->g_cdeg || !topo->loc_out_ptr || !topo->loc_in_ptr || (topo->num_local > 0 && (!topo->loc_dst || !topo->loc_src ||
+      !topo->loc_in_eid || !topo->loc_type)))
+    return AGDIFF_ERR_ARG;
+  if (topo->num_nodes * (int64_t)AGDIFF_RAD_STRIDE >= (1ll << 31) || topo->max_edges >= (1ll << 31)) return AGDIFF_ERR_LIMIT;
+  LargeArgs a;
+  a.g = ga;
+  a.loc_out_ptr = topo->loc_out_ptr;
+  a.loc_dst = topo->loc_dst;
+  a.thr = ws->g_deg;
+  a.cscan = ws->g_cdeg;
+  a.num_edges = ws->num_edges;
+  a.num_canon = ws->num_canon;
+  a.num_nodes = (int32_t)topo->num_nodes;
+  a.max_edges = (int32_t)topo->max_edges;
+  const unsigned blocks = (unsigned)((topo->num_nodes + AG_LG_TARGETS - 1) / AG_LG_TARGETS);
+  ag_log_variant(ws, AGDIFF_VAR_GRAPH_LARGE);
+  k_lg_thr<<<blocks, AG_LG_THREADS, 0, st>>>(a);
+  AG_CHECK_LAUNCH();
+  k_lg_count<<<blocks, AG_LG_THREADS, 0, st>>>(a);
+  AG_CHECK_LAUNCH();
+  k_lg_scan<<<3, 1024, 0, st>>>(a);
+  AG_CHECK_LAUNCH();
+  k_lg_fill<<<blocks, AG_LG_THREADS, 0, st>>>(a);
+  AG_CHECK_LAUNCH();
+  k_lg_ref<<<blocks, AG_LG_THREADS, 0, st>>>(a);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
 int graph_build_impl(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, const float* pos, float cutoff,
-                     int32_t canon_radius_only, void* stream) {
+                     int32_t canon_radius_only, void* stream, bool force_large) {
   if (!topo || !ws || !pos || topo->num_graphs <= 0 || topo->num_nodes <= 0 || (topo->num_local > 0 && !topo->loc_row))
     return AGDIFF_ERR_ARG;
   if (!ws->graph_edge_cnt || !ws->graph_edge_ptr || !ws->in_ptr || !ws->out_ptr || !ws->e_src || !ws->e_dst ||
@@ -430,9 +804,8 @@ int graph_build_impl(const agdiff_params_t* p, const agdiff_topo_t* topo, const 
       !ws->c_pos || !ws->c_mir)
     return AGDIFF_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  // The host (agdiff_amd/topology.py) guarantees max atoms per graph <= AGDIFF_MAX_ATOMS_PER_GRAPH and
-  // passes it through max_edges bookkeeping; the kernels size LDS for the compile-time limit's word count
-  // actually needed, which the host stores in graph_edge_cnt capacity order: words from max atoms.
+  // Up to AGDIFF_MAX_ATOMS_PER_GRAPH atoms per molecule: k_graph, LDS sized for the word count the batch's largest molecule
+  // needs.  Beyond (up to AGDIFF_MAX_ATOMS_LARGE): the k_lg_* kernels.
   GraphArgs a;
   a.graph_ptr = topo->graph_ptr;
   a.loc_in_ptr = topo->loc_in_ptr;
@@ -488,7 +861,10 @@ int graph_build_impl(const agdiff_params_t* p, const agdiff_topo_t* topo, const 
     a.smooth = p->smooth;
   }
   const int max_atoms = (int)topo->max_atoms_per_graph;
-  if (max_atoms <= 0 || max_atoms > AGDIFF_MAX_ATOMS_PER_GRAPH) return AGDIFF_ERR_LIMIT;
+  if (max_atoms <= 0 || max_atoms > AGDIFF_MAX_ATOMS_LARGE) return AGDIFF_ERR_LIMIT;
+  // molecules past the LDS path's limit (and agdiff_graph_build_large on any batch): the mask-free build
+  a.words = 0;
+  if (force_large || max_atoms > AGDIFF_MAX_ATOMS_PER_GRAPH) return graph_build_large(a, topo, ws, st);
   a.words = 2 * ((max_atoms + 63) / 64);
   const int nmax = a.words * 32;
   // threads per molecule: a wave walks its targets one after the other (per target a chain of ballots and dependent

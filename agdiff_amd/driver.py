@@ -69,13 +69,17 @@ def plan_batches(mols, confs_of, max_atoms):
     leaves many half-empty batches when a few molecules have hundreds of conformers (GEOM test molecules carry 50-500
     references, utils/datasets.py:720-721), and a half-empty batch costs nearly a full one per denoising step.
     Results are keyed by molecule index, so the order inside the batches does not matter; every batch keeps its
-    molecules in ascending index order."""
+    molecules in ascending index order.  Molecules of more than AGDIFF_MAX_ATOMS_PER_GRAPH atoms share batches only with
+    each other: one of them sends its whole batch down the large path (mask-free graph build, unfused sampler front), which
+    Drugs-sized molecules have no reason to take."""
+    from . import _lib
     need = [int(m["atom_type"].shape[0]) * confs_of(m["num_refs"]) for m in mols]
+    large = [int(m["atom_type"].shape[0]) > _lib.MAX_ATOMS_PER_GRAPH for m in mols]
     order = sorted(range(len(mols)), key=lambda k: (-need[k], k))
     bins, room = [], []
     for k in order:
         for b in range(len(bins)):
-            if need[k] <= room[b]:
+            if need[k] <= room[b] and large[bins[b][0]] == large[k]:
                 bins[b].append(k)
                 room[b] -= need[k]
                 break

@@ -683,7 +683,7 @@ class LangevinRun:
         sg = getattr(model, "step_graphs", "auto")
         self._use_graphs = bool((sg is True or (sg == "auto" and N <= model.STEP_GRAPH_MAX_NODES)) and on_step is None and
                                 noise_mode == "chunked" and self.pk.poly_kt > 0 and getattr(model, "fused_front", True) and
-                                not getattr(model, "front_split_graph", False))
+                                not getattr(model, "front_split_graph", False) and not self.topo.large)
         self._graphs, self._step_table, self._step_index, self._dev_index = {}, None, None, None
         # (a capture needs a stream of its own: the legacy default stream, which torch hands out as the current one, cannot be captured)
         self._gstream = torch.cuda.Stream(device=dev) if self._use_graphs else None
@@ -742,8 +742,11 @@ class LangevinRun:
 
     def _fused_front(self):
         """The polynomial path keeps the serial front of a step in one launch (agdiff_sampler_front: update of step t +
-        radius graph of step t + 1): whenever the radius edges have their polynomials and the graph is built here."""
-        return self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True)
+        radius graph of step t + 1): whenever the radius edges have their polynomials and the graph is built here.  Not for a
+        batch with a molecule of more than AGDIFF_MAX_ATOMS_PER_GRAPH atoms (topo.large): agdiff_sampler_front keeps a
+        molecule's masks in LDS; such a batch runs update, graph build (agdiff_graph_build_large) and forward launch by launch,
+        and with them no step graphs (they replay the fused front)."""
+        return self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large
 
     def _fill_args(self, a, k, dev, N):
         sig, step_size, noise_scale, use_global = self._sched[k]

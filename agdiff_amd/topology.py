@@ -73,6 +73,47 @@ def _group_order(need, GT):
     return hit
 
 
+def extend_graph_order_sparse(n, bond_src, bond_dst, bond_type, order=3, num_types=None):
+    """extend_graph_order_np (agdiff_amd/synth.py) without the dense n x n matrices and their products: the pairs at graph
+    distance k = 2 .. order are found by joining the pairs at distance k - 1 with the bond list (numpy sorts: linear in the
+    number of pairs, which a bounded valence keeps proportional to n).  Same result, same (row, col) order.  BatchTopology
+    uses it for molecules of more than AGDIFF_MAX_ATOMS_PER_GRAPH atoms, where the dense form takes minutes."""
+    from .synth import NUM_BOND_TYPES
+    num_types = NUM_BOND_TYPES if num_types is None else num_types
+    n = int(n)
+    bs, bd = np.asarray(bond_src, dtype=np.int64), np.asarray(bond_dst, dtype=np.int64)
+    bkey, inv = np.unique(bs * n + bd, return_inverse=True)
+    tsum = np.zeros(bkey.shape[0], dtype=np.int64)
+    np.add.at(tsum, inv.reshape(-1), np.asarray(bond_type, dtype=np.int64))
+    offdiag = (bkey // n) != (bkey % n)
+    adj = bkey[offdiag]                                   # binarised adjacency without the diagonal, sorted by (row, col)
+    a_src, a_dst = adj // n, adj % n
+    nb_ptr = np.concatenate([[0], np.cumsum(np.bincount(a_src, minlength=n))])
+    seen = np.union1d(np.arange(n, dtype=np.int64) * (n + 1), adj)       # pairs at distance <= k - 1 (diagonal included)
+    frontier = adj
+    keys, types = [bkey], [tsum]
+    for k in range(2, order + 1):
+        f_src, f_dst = frontier // n, frontier % n
+        deg = nb_ptr[f_dst + 1] - nb_ptr[f_dst]
+        rep_src = np.repeat(f_src, deg)
+        # neighbours of every frontier pair's end point: positions nb_ptr[f_dst] .. in the sorted adjacency
+        first = np.repeat(nb_ptr[f_dst], deg)
+        within = np.arange(rep_src.shape[0]) - np.repeat(np.cumsum(deg) - deg, deg)
+        cand = np.unique(rep_src * n + a_dst[first + within])
+        frontier = np.setdiff1d(cand, seen, assume_unique=True)
+        seen = np.union1d(seen, frontier)
+        keys.append(frontier)
+        types.append(np.full(frontier.shape[0], num_types + k - 1, dtype=np.int64))
+    # (extend_graph_order_np asserts that no bond entry meets a higher-order pair: a bond is at distance <= 1, except a
+    # self-loop, whose type it keeps as the dense form does)
+    key = np.concatenate(keys)
+    typ = np.concatenate(types)
+    o = np.argsort(key, kind="stable")
+    key, typ = key[o], typ[o]
+    keep = typ != 0
+    return key[keep] // n, key[keep] % n, typ[keep]
+
+
 class BatchTopology:
     # agdiff_cfconv_node gives a wave a GROUP of targets (quad_tgt): four for batches that fill the chip that way (one
     # 16-row local tile then serves four targets: fewest tiles), two or one for small batches, where there are more wave
@@ -114,7 +155,9 @@ class BatchTopology:
                 n = int(counts[g])
                 if n == 0:
                     continue
-                r, c, t = extend_graph_order_np(n, bi[0][sel] - gptr[g], bi[1][sel] - gptr[g], bt[sel], order=order)
+                # (dense adjacency powers up to the small path's limit, as ever; beyond it the sparse restatement)
+                extend = extend_graph_order_np if n <= _lib.MAX_ATOMS_PER_GRAPH else extend_graph_order_sparse
+                r, c, t = extend(n, bi[0][sel] - gptr[g], bi[1][sel] - gptr[g], bt[sel], order=order)
                 rs.append(r + gptr[g]); cs.append(c + gptr[g]); ts.append(t)
             bi = np.stack([np.concatenate(rs), np.concatenate(cs)]) if rs else np.zeros((2, 0), dtype=np.int64)
             bt = np.concatenate(ts) if ts else np.zeros(0, dtype=np.int64)
@@ -160,8 +203,11 @@ class BatchTopology:
         self.max_edges = int(cap.sum())
         self.max_in_degree = int(cap.max()) if N else 0
         self.max_atoms = int(counts.max())
-        if self.max_atoms > _lib.MAX_ATOMS_PER_GRAPH:
-            raise NotImplementedError("graphs with more than %d atoms are not supported" % _lib.MAX_ATOMS_PER_GRAPH)
+        if self.max_atoms > _lib.MAX_ATOMS_LARGE:
+            raise NotImplementedError("graphs with more than %d atoms are not supported" % _lib.MAX_ATOMS_LARGE)
+        # A batch with a molecule past the LDS graph build's limit takes the large path as a whole (agdiff_graph_build_large,
+        # unfused sampler front): it has no use for the [N][W] mask arrays (W grows with the largest molecule)
+        self.large = self.max_atoms > _lib.MAX_ATOMS_PER_GRAPH
         if N * 192 * 4 >= 2 ** 32 or self.max_edges >= 2 ** 31 - 64:
             raise NotImplementedError("batch too large for 32-bit offsets; split it")
 
@@ -237,7 +283,13 @@ class BatchTopology:
             block = need_order[gptr[ga]:gptr[gb]].reshape(gb - ga, n, need_order.shape[1])
             starts = np.concatenate([[0], np.flatnonzero(~(block[1:] == block[:-1]).all(axis=(1, 2))) + 1, [gb - ga]])
             for sa, sb in zip(starts[:-1], starts[1:]):
-                idx = _group_order(block[sa], GT)
+                if n <= _lib.MAX_ATOMS_PER_GRAPH:
+                    idx = _group_order(block[sa], GT)
+                else:
+                    # agdiff_group_order's search swaps atoms between every pair of groups: quadratic in n per pass (minutes
+                    # at 4096 atoms).  A large molecule takes the search's first start as it is: the atoms sorted by their
+                    # need vectors, like needs next to each other (the search gains ~6 % of the local tiles on Drugs)
+                    idx = np.lexsort(block[sa].T[::-1]).astype(np.int64)
                 if idx.size % GT:
                     idx = np.concatenate([idx, np.full(GT - idx.size % GT, -1, dtype=idx.dtype)])
                 grp = np.full((idx.size // GT, 4), -1, dtype=np.int64)          # (always four entries per group: -1 = none)
@@ -308,13 +360,16 @@ class BatchTopology:
         self.lt_real = real_t
         self.quad_wg_ptr = i32(wg_ptr) if wg_ptr.size else None
         # static local in-adjacency masks (agdiff_topo_t.loc_bits): bit (src - first atom of the molecule) of row dst
-        W = 2 * ((self.max_atoms + 63) // 64)
-        bits = np.zeros(N * W, dtype=np.uint32)
-        if L:
-            jl = src - gptr[ba[src]]
-            # (the local edges are unique, so every (row, word) sums DISTINCT powers of two: exact in float64, and a bincount)
-            bits = np.bincount(dst * W + (jl >> 5), weights=np.ldexp(1.0, (jl & 31).astype(np.int32)), minlength=N * W).astype(np.uint32)
-        self.loc_bits = torch.from_numpy(bits.view(np.int32)).to(device)
+        if self.large:
+            self.loc_bits = None
+        else:
+            W = 2 * ((self.max_atoms + 63) // 64)
+            bits = np.zeros(N * W, dtype=np.uint32)
+            if L:
+                jl = src - gptr[ba[src]]
+                # (the local edges are unique, so every (row, word) sums DISTINCT powers of two: exact in float64, and a bincount)
+                bits = np.bincount(dst * W + (jl >> 5), weights=np.ldexp(1.0, (jl & 31).astype(np.int32)), minlength=N * W).astype(np.uint32)
+            self.loc_bits = torch.from_numpy(bits.view(np.int32)).to(device)
         self.lt_eid = eid_t
         self.lc_tpos = i32(tpos[lc_pos])
         self.lc_tmir = i32(np.where(lc_mir >= 0, tpos[np.maximum(lc_mir, 0)], -1))
@@ -462,7 +517,8 @@ class Workspace:
         self.l_len_p = f32(ptiles * TW)
         self.h0, self.xs0 = f32(N * 128), f32(N * 192)
         self.enc_flags = i32(1 + (topo.Lc + TW - 1) // TW)
-        self.g_inbits = i32(N * 2 * ((topo.max_atoms + 63) // 64))
+        # (the count -> fill hand-over of the LDS graph build; agdiff_graph_build_large keeps no masks)
+        self.g_inbits = None if getattr(topo, "large", False) else i32(N * 2 * ((topo.max_atoms + 63) // 64))
         self.g_deg, self.g_cdeg = i32(N), i32(N)
         self.agg_loc = f32(N * 192)
         self.agg_first_loc = f32((ptiles + lchunk - 1) // lchunk * 192)

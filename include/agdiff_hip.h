@@ -23,12 +23,19 @@
 extern "C" {
 #endif
 
-#define AGDIFF_ABI_VERSION 46
+#define AGDIFF_ABI_VERSION 47
 #define AGDIFF_HIDDEN 128          /* config.hidden_dim; InteractionBlock.lin hard-codes 256 = 2*128 (schnet.py:190) */
 #define AGDIFF_MAX_CONVS 8         /* >= config.num_convs (6) */
 #define AGDIFF_MAX_CONVS_LOCAL 8   /* >= config.num_convs_local (4) */
 #define AGDIFF_NUM_EDGE_TYPES 100  /* rows of bond_emb (edge.py:49) */
-#define AGDIFF_MAX_ATOMS_PER_GRAPH 512
+#define AGDIFF_MAX_ATOMS_PER_GRAPH 512   /* most atoms per molecule of the LDS graph build (k_graph) and of agdiff_sampler_front */
+#define AGDIFF_MAX_ATOMS_LARGE 16384     /* most atoms per molecule at all (agdiff_graph_build_large).  The large build keeps nothing per
+                                            molecule in LDS and its offsets are the batch's (32-bit: checked per batch by the host), so
+                                            no size is a hard wall; the bound is set by cost: the build tests all n^2 pairs of a molecule
+                                            (at 16384 atoms 2.7e8 per pass; measured: 3.1 ms for 16 x 4096 atoms, the same pair count), the
+                                            molecule's positions (12 B per atom: 192 KB) still sit in one XCD's 4 MB L2 next to the lists
+                                            being written, and the host's per-molecule work stays in seconds.  Larger systems want a cell
+                                            list, which this rule (first 33 candidates in INDEX order) does not map onto. */
 #define AGDIFF_RADIUS_CAP 33       /* max_num_neighbors + 1 (torch_cluster.radius_graph, common.py:217) */
 #define AGDIFF_TILE 16             /* edges / nodes per MFMA tile */
 #define AGDIFF_MAX_CHUNK_TILES 8   /* most tiles one wave walks per chunk in the fused CFConv kernel (128 edges) */
@@ -274,6 +281,8 @@ typedef struct agdiff_params {
 #define AGDIFF_VAR_FUSED_FRONT 8192     /* agdiff_sampler_front: update of step t + radius graph of step t + 1 in one launch */
 #define AGDIFF_VAR_CFCONV_NODE_FOUR 16384 /* agdiff_cfconv_node ran its four-waves-per-SIMD shape (tune_cfconv_four_min_quads) */
 #define AGDIFF_VAR_CFCONV_NODE_QUAD 32768 /* agdiff_cfconv_node walked the radius rows in quad tiles (tune_cfconv_quad_tiles) */
+#define AGDIFF_VAR_GRAPH_LARGE 65536    /* graph build without adjacency masks (agdiff_graph_build_large: a molecule of more than
+                                           AGDIFF_MAX_ATOMS_PER_GRAPH atoms in the batch, or called directly) */
 
 /* ---- static topology of one packed batch (host builds it once per batch) ---------------------
  * Graphs are contiguous node ranges (PyG Batch, utils/misc.py:88-90).  "Local" edges are the
@@ -283,7 +292,8 @@ typedef struct agdiff_topo {
   int64_t num_graphs;        /* G */
   int64_t num_local;         /* L: local edges, in reference order (sorted by (src, dst)) */
   int64_t max_edges;         /* capacity of the per-edge buffers: sum_i (33 + local in-degree_i) */
-  int64_t max_atoms_per_graph; /* <= AGDIFF_MAX_ATOMS_PER_GRAPH */
+  int64_t max_atoms_per_graph; /* <= AGDIFF_MAX_ATOMS_LARGE; above AGDIFF_MAX_ATOMS_PER_GRAPH the graph builds take the large path and
+                                agdiff_sampler_front refuses (AGDIFF_ERR_LIMIT) */
   int64_t max_in_degree;     /* max_i (33 + local in-degree_i); any value (a list may span several chunks) */
   const int32_t* graph_ptr;  /* [G+1] node offsets */
   const int32_t* atom_type;  /* [N] */
@@ -342,7 +352,7 @@ typedef struct agdiff_topo {
   const int32_t* quad_wg_ptr;/* [257] or null: workgroup w of agdiff_cfconv_node's 256 persistent workgroups (k_cfconv_quad) owns the quads
                                 [quad_wg_ptr[w], quad_wg_ptr[w+1]) -- contiguous ranges of like tile counts; null (or fewer workgroups):
                                 equal quad counts */
-  const int32_t* loc_bits;   /* [N][W], W = 2 ceil(max_atoms_per_graph / 64) 32-bit words, or null: the static local in-adjacency of
+  const int32_t* loc_bits;   /* (null for batches with max_atoms_per_graph > AGDIFF_MAX_ATOMS_PER_GRAPH) [N][W], W = 2 ceil(max_atoms_per_graph / 64) 32-bit words, or null: the static local in-adjacency of
                                 every atom as a bit mask over its molecule's atoms -- bit (j - graph_ptr[g]) of row i is set when
                                 the local edge j -> i exists.  agdiff_sampler_front copies a molecule's rows into LDS (the radius
                                 graph excludes local pairs); null: it builds them from loc_in_ptr / loc_in_eid / loc_src per step */
@@ -425,10 +435,10 @@ typedef struct agdiff_ws {
   float*   l_attr_frag;      /* [ceil(Lp/16)] tiles x 2048 floats: edge_attr of the local edges in operand form, by padded-list
                                 position (only written / read when the local edges go through the filter MLPs) */
   float*   l_len_p;          /* [Lp] lengths of the local edges by padded-list position (agdiff_local_lengths; pads stay 0) */
-  int32_t* g_inbits;         /* [N][2 * ceil(max_atoms_per_graph / 64)] hand-over from the graph build's count pass to its fill
+  int32_t* g_inbits;         /* (may be null; never used by agdiff_graph_build_large) [N][2 * ceil(max_atoms_per_graph / 64)] hand-over from the graph build's count pass to its fill
                                 pass: row i = in-adjacency bit mask of atom i inside its molecule (optional, with g_deg / g_cdeg) */
-  int32_t* g_deg;            /* [N] in-degrees */
-  int32_t* g_cdeg;           /* [N] canonical in-degrees */
+  int32_t* g_deg;            /* [N] in-degrees (agdiff_graph_build_large, which needs both: each target's candidate threshold) */
+  int32_t* g_cdeg;           /* [N] canonical in-degrees (agdiff_graph_build_large: then their exclusive scan) */
   int32_t* enc_flags;        /* [1 + ceil(Lc/16)]: agdiff_local_edge_rows: [0] = tiles of the canonical local list that hold an edge
                                 longer than the cutoff (or of a type without a polynomial) this step, [1 + tile] = the 16-bit mask
                                 of those rows: the encoder MLP evaluates exactly them, the polynomials all the others */
@@ -493,6 +503,16 @@ int agdiff_graph_build_ex(const agdiff_topo_t* topo, const agdiff_ws_t* ws, cons
  * what the denoising loop calls (one launch less per step than agdiff_graph_build_ex + agdiff_edge_scales_split(0)). */
 int agdiff_graph_build_scaled(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, const float* pos,
                               float cutoff, int32_t canon_radius_only, void* stream);
+
+/* The same graph, bit for bit and in the same order, built WITHOUT per-molecule adjacency masks (csrc/graph.hip, k_lg_*): for
+ * molecules of up to AGDIFF_MAX_ATOMS_LARGE atoms, a molecule spread over ceil(n / 16) workgroups.  The three entry points above
+ * take this path by themselves when topo->max_atoms_per_graph > AGDIFF_MAX_ATOMS_PER_GRAPH; called directly it serves any batch.
+ * p null: as agdiff_graph_build_ex; p given: as agdiff_graph_build_scaled.  Needs ws->g_deg and ws->g_cdeg (scratch); reads neither
+ * ws->g_inbits nor topo->loc_bits.  Five launches; deterministic (offsets from scans over the atoms, no atomics). */
+int agdiff_graph_build_large(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, const float* pos,
+                             float cutoff, int32_t canon_radius_only, void* stream);
+/* Launch shape of agdiff_graph_build_large for this batch: out[0] = workgroups per launch, out[1] = atoms (targets) per workgroup. */
+int agdiff_graph_large_grid(const agdiff_topo_t* topo, int64_t* out /* [host] */);
 
 /* get_distance on the static local edges (geometry.py:5-6 applied to edge_index[:, local_edge_mask]): one evaluation per
  * canonical local edge, written to l_len of the edge and of its mirror, to lc_len and -- where the workspace has them --
