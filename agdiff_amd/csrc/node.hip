@@ -1210,3 +1210,102 @@ extern "C" int agdiff_diffusion_loss(const agdiff_params_t* p, const agdiff_topo
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
+
+// ------------------------------------------------------------------------------ counter-based noise (agdiff_counter_noise)
+// Counter-based standard normals for the sampler: Philox4x32-10 + Box-Muller.  Every value is a pure function of (seed, the
+// graph's 64-bit stream id, the atom's index inside its graph, the step's schedule index) -- where a conformer sits in the packed
+// batch, what is packed beside it and how the batch is cut over ranks do not enter.  One thread = one atom x AG_NOISE_ROWS
+// consecutive step rows; nothing is shared between threads (no LDS, no atomics).  (Kept in this translation unit, next to the
+// update kernel that consumes the rows.)
+
+namespace {
+
+constexpr int AG_NOISE_ROWS = 8;        // step rows per thread: the atom's graph is looked up once for all of them
+
+struct NoiseArgs {
+  const int32_t* graph_ptr;   // [G + 1]
+  const int64_t* stream_id;   // [G]
+  const int32_t* steps;       // [S]
+  float* out;                 // [S][N][3]
+  uint32_t key0, key1;
+  int32_t N, G, S;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped by the Weyl constants
+// between rounds.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&o)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// r = sqrt(-2 ln u), u = ((x >> 8) + 0.5) 2^-24 = t 2^-25 in (0, 1), t = 2 k + 1 odd: r <= sqrt(50 ln 2) = 5.887.  t has 25 bits, one
+// more than fp32 holds: below one half u is exact as it stands; above, 1 - u = (2^25 - t) 2^-25 is, and ln u = log1p(-(1 - u))
+// keeps the small radii next to u = 1 (r = sqrt(2 (1 - u)) there: a u rounded to fp32 would move them by up to 2.4e-4).
+__device__ __forceinline__ float bm_radius(uint32_t x) {
+  const uint32_t t = 2u * (x >> 8) + 1u;
+  const float l = t < (1u << 24) ? logf((float)t * 0x1p-25f) : log1pf(-(float)((1u << 25) - t) * 0x1p-25f);
+  return sqrtf(-2.0f * l);
+}
+// (cos, sin) of 2 pi u for the same u: the angle is pi t 2^-24 with t = 2 k + 1 odd; t >= 2^24 is the half turn behind t - 2^24,
+// which fp32 holds exactly, so the argument of sincospif carries no rounding.
+__device__ __forceinline__ void bm_angle(uint32_t x, float& c, float& s) {
+  const uint32_t t = 2u * (x >> 8) + 1u;
+  const bool half = t >= (1u << 24);
+  sincospif((float)(t & 0xFFFFFFu) * 0x1p-24f, &s, &c);
+  if (half) { c = -c; s = -s; }
+}
+
+__global__ void __launch_bounds__(256) k_counter_noise(NoiseArgs a) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.N) return;
+  // the atom's graph: the last g with graph_ptr[g] <= i (an empty graph shares its offset with its successor, which wins)
+  int lo = 0, hi = a.G;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.graph_ptr[mid] <= i) lo = mid; else hi = mid;
+  }
+  const uint64_t sid = (uint64_t)a.stream_id[lo];
+  const uint32_t c0 = (uint32_t)(i - a.graph_ptr[lo]), c2 = (uint32_t)sid, c3 = (uint32_t)(sid >> 32);
+  const int s0 = blockIdx.y * AG_NOISE_ROWS, s1 = min(s0 + AG_NOISE_ROWS, a.S);
+  for (int s = s0; s < s1; ++s) {
+    uint32_t x[4];
+    philox4x32_10(c0, (uint32_t)a.steps[s], c2, c3, a.key0, a.key1, x);     // (steps[s] = -1 is c1 = 0xFFFFFFFF: pos_init)
+    float cx, sx, cz, sz;
+    bm_angle(x[1], cx, sx);
+    bm_angle(x[3], cz, sz);
+    const float r0 = bm_radius(x[0]), r1 = bm_radius(x[2]);
+    float* o = a.out + ((size_t)s * (size_t)a.N + (size_t)i) * 3;
+    o[0] = r0 * cx;
+    o[1] = r0 * sx;
+    o[2] = r1 * cz;           // (the sine branch of the second pair is dropped)
+  }
+}
+
+}  // namespace
+
+// torch.randn_like(pos) per denoising step (dualenc.py:529) and torch.randn(batch.num_nodes, 3) for pos_init
+// (scripts/test.py:146), as a function of (seed, stream id, atom, step) instead of a generator's running state.
+extern "C" int agdiff_counter_noise(const agdiff_topo_t* topo, const int64_t* stream_id, uint64_t seed, const int32_t* steps,
+                                    int32_t num_steps, float* out, void* stream) {
+  if (!topo || !stream_id || !steps || !out || num_steps < 0 || topo->num_nodes < 0 || topo->num_graphs < 0) return AGDIFF_ERR_ARG;
+  if (num_steps == 0 || topo->num_nodes == 0) return AGDIFF_OK;
+  if (!topo->graph_ptr || topo->num_graphs == 0) return AGDIFF_ERR_ARG;
+  const int64_t row_blocks = ((int64_t)num_steps + AG_NOISE_ROWS - 1) / AG_NOISE_ROWS;
+  if (topo->num_nodes > 0x7fffffff - 256 || topo->num_graphs > 0x7fffffff || row_blocks > 65535) return AGDIFF_ERR_LIMIT;
+  NoiseArgs a{topo->graph_ptr, stream_id, steps, out, (uint32_t)seed, (uint32_t)(seed >> 32),
+              (int32_t)topo->num_nodes, (int32_t)topo->num_graphs, num_steps};
+  k_counter_noise<<<dim3((unsigned)((topo->num_nodes + 255) / 256), (unsigned)row_blocks), dim3(256), 0, (hipStream_t)stream>>>(a);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}

@@ -113,11 +113,14 @@ def shard_of(packed, rank, world):
         return None, (g0, g1), (0, 0)
     at, bi, bt, ba, lo, hi = take_graph_range(np.asarray(packed["atom_type"]), np.asarray(packed["bond_index"]),
                                               np.asarray(packed["bond_type"]), np.asarray(packed["batch"]), g0, g1)
-    return dict(atom_type=at, bond_index=bi, bond_type=bt, batch=ba, num_graphs=g1 - g0), (g0, g1), (lo, hi)
+    part = dict(atom_type=at, bond_index=bi, bond_type=bt, batch=ba, num_graphs=g1 - g0)
+    if packed.get("stream_ids") is not None:           # (driver.pack_batch: the graphs' random-stream ids go with them)
+        part["stream_ids"] = np.asarray(packed["stream_ids"])[g0:g1]
+    return part, (g0, g1), (lo, hi)
 
 
 def sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=False, max_retry=2, log=print, group=None,
-                         pos_init=None, noise=None, topology=None):
+                         pos_init=None, noise=None, topology=None, counter_seed=None):
     """driver.sample_batch for one packed batch sharded over the ranks of `group` by contiguous graph ranges
     (SURVEY §8e): every rank samples its range, the shards' positions (+ NaN flag) are all-gathered after every
     denoising step (StepAllGather), and the last gather is the job's result on every rank.  Molecules in which a NaN
@@ -125,12 +128,15 @@ def sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=False,
     `pos_init` [N,3] / `noise` [steps,N,3] for the WHOLE batch replace the first attempt's draws (tests).
     Returns (pos [N,3] cpu, traj or None, ok [num molecules]) like driver.sample_batch; pos and ok are identical on all
     ranks, the trajectories [steps, N, 3] are gathered to rank 0 only (None elsewhere).  A rank that raises while the
-    others sample keeps issuing its collectives, then every rank raises."""
-    from .driver import SAMPLE_STATS, _arithmetic, _sort_results, subset_batch
+    others sample keeps issuing its collectives, then every rank raises.
+    `counter_seed`: as in driver.sample_batch -- every rank draws its share from the stream ids of its graph range, so the
+    sharded job draws what the one-GPU job draws."""
+    from .driver import SAMPLE_STATS, _arithmetic, _check_counter, _counter_kwargs, _sort_results, subset_batch
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
     spans = packed["spans"]
     n_mol, N = len(spans), packed["atom_type"].shape[0]
+    _check_counter(model, packed, counter_seed)
     pos_out = torch.full((N, 3), float("nan"))
     traj_out = None
     ok = np.zeros(n_mol, dtype=bool)
@@ -151,7 +157,13 @@ def sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=False,
         err, traj, bad_local, range_local = None, None, np.zeros(0, dtype=bool), []
         if mine is not None:
             try:
-                p0 = pos_init[lo:hi].to(device) if (first and pos_init is not None) else torch.randn(hi - lo, 3).to(device)
+                counter = _counter_kwargs(mine, counter_seed, tries)
+                if first and pos_init is not None:
+                    p0 = pos_init[lo:hi].to(device)
+                elif counter:
+                    p0 = model.counter_normals(mine["batch"], counter["stream_ids"], counter_seed, [-1])[0]
+                else:
+                    p0 = torch.randn(hi - lo, 3).to(device)
                 with _arithmetic(model, wide):
                     # (`topology`: this rank's range of the whole batch, prepared ahead by driver.prepare_batch: first attempt only)
                     extra = {"topology": topology} if (topology is not None and sub is packed) else {}
@@ -160,7 +172,7 @@ def sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=False,
                                                T(mine["batch"]), mine["num_graphs"], False, clip_local=clip_local,
                                                save_traj=save_traj, raise_on_nan=False,
                                                noise=(noise[:, lo:hi] if (first and noise is not None) else None),
-                                               **extra, **sampler_kwargs)
+                                               **extra, **counter, **sampler_kwargs)
                     run.on_step = lambda k, i, pos: gather(k, i, pos, run.ws.nan_flag)
                     run.advance(run.remaining())
                     _, traj = run.finish()

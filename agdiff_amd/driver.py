@@ -13,6 +13,9 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
 --save-traj) and the merged `samples_all.npz`, written by rank 0 after a barrier.
 
+`--noise counter` draws every conformer's pos_init and noise from the counter-based generator under `--seed` and the conformer's
+stream id (`stream_id`): the same numbers whatever --max-atoms, the packing, a --resume or the number of ranks.
+
     python -m agdiff_amd.driver --ckpt ckpt.pt --testset test.npz --out out_dir [--n-steps 5000]
     torchrun --nproc-per-node 8 -m agdiff_amd.driver ...      (each packed batch is sharded over the ranks by graph
                                                                ranges; one RCCL all-gather of positions per step)
@@ -55,6 +58,35 @@ def load_testset(path):
     return mols
 
 
+def stream_id(molecule_index, conformer_index, attempt=0):
+    """The 64-bit name of one conformer's random stream (--noise counter; include/agdiff_hip.h: agdiff_counter_noise):
+    molecule_index << 32 | attempt << 24 | conformer_index.  molecule_index: the molecule's `index` field, which also names its
+    output (pos_gen_<index>); conformer_index: the position within the molecule's repeat, below 2^24; attempt: 0 for the first
+    sampling pass, + 1 for every NaN retry, below 256.  Takes ints or numpy arrays."""
+    m, c, a = (np.asarray(x, dtype=np.int64) for x in (molecule_index, conformer_index, attempt))
+    if np.any(m < 0) or np.any(m >= 1 << 31):
+        raise ValueError("molecule index outside [0, 2^31)")
+    if np.any(c < 0) or np.any(c >= 1 << 24):
+        raise ValueError("conformer index outside [0, 2^24)")
+    if np.any(a < 0) or np.any(a >= 256):
+        raise ValueError("attempt outside [0, 256)")
+    out = (m << 32) | (a << 24) | c
+    return int(out) if out.ndim == 0 else out
+
+
+def split_stream_id(sid):
+    """(molecule_index, conformer_index, attempt) of a stream id (ints or numpy arrays)."""
+    s = np.asarray(sid, dtype=np.int64)
+    parts = (s >> 32, s & 0xFFFFFF, (s >> 24) & 0xFF)
+    return tuple(int(p) for p in parts) if s.ndim == 0 else parts
+
+
+def with_attempt(stream_ids, attempt):
+    """The same conformers' ids with the attempt field set to `attempt`."""
+    m, c, _ = split_stream_id(np.asarray(stream_ids, dtype=np.int64))
+    return stream_id(m, c, attempt)
+
+
 def sharded_capacity(max_atoms, world):
     """Atoms of one global batch that `world` ranks share by contiguous graph ranges (dist.shard_graphs balances EDGES, so the
     ranks' atom counts differ by a few per cent: profiles/r05_shard_balance.json): 3 % below max_atoms x world, so that no rank's
@@ -92,9 +124,11 @@ def plan_batches(mols, confs_of, max_atoms):
 
 
 def pack_batch(mols, confs_of):
-    """repeat_data (utils/misc.py:88-90) for every molecule of the batch, concatenated."""
+    """repeat_data (utils/misc.py:88-90) for every molecule of the batch, concatenated.  When every molecule carries its `index`
+    (load_testset), `stream_ids` [num_graphs] names each graph's random stream (stream_id, attempt 0): the ids travel with the
+    graphs through subset_batch and dist.shard_of."""
     from .synth import repeat_molecule
-    ats, rs, cs, ts, bs, spans = [], [], [], [], [], []
+    ats, rs, cs, ts, bs, spans, ids = [], [], [], [], [], [], []
     node_off, g_off = 0, 0
     for m in mols:
         g = confs_of(m["num_refs"])
@@ -103,10 +137,15 @@ def pack_batch(mols, confs_of):
                                         node_off, g_off)
         ats.append(a); rs.append(r); cs.append(c); ts.append(t); bs.append(b)
         spans.append((node_off, n, g))
+        if isinstance(m, dict) and m.get("index") is not None:
+            ids.append(stream_id(int(m["index"]), np.arange(g, dtype=np.int64)))
         node_off += n * g
         g_off += g
-    return dict(atom_type=np.concatenate(ats), bond_index=np.stack([np.concatenate(rs), np.concatenate(cs)]),
-                bond_type=np.concatenate(ts), batch=np.concatenate(bs), num_graphs=g_off, spans=spans)
+    out = dict(atom_type=np.concatenate(ats), bond_index=np.stack([np.concatenate(rs), np.concatenate(cs)]),
+               bond_type=np.concatenate(ts), batch=np.concatenate(bs), num_graphs=g_off, spans=spans)
+    if len(ids) == len(mols):
+        out["stream_ids"] = np.concatenate(ids) if ids else np.zeros(0, dtype=np.int64)
+    return out
 
 
 def prepare_batch(model, bmols, confs_of, rank=0, world=1):
@@ -159,18 +198,23 @@ def _prepare_in_worker(bmols, confs, rank, world, topo_opts):
 
 
 def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_retry=2, log=print, pos_init=None,
-                 noise=None, topology=None):
+                 noise=None, topology=None, counter_seed=None):
     """test.py:143-181 for every molecule of a packed batch: a molecule in which a NaN appeared is sampled again
     (fresh pos_init) with clip_local=20, at most `max_retry` attempts in all, and dropped after that; the molecules
     packed with it keep their first result -- graphs are independent on the whole path, and the update kernel flags
     NaNs per graph (agdiff_ws_t.nan_flag).  Returns (pos [N,3] cpu, traj [steps,N,3] cpu or None, ok [num molecules]
     bool); rows of failed molecules are NaN.  `pos_init` [N,3] / `noise` [steps,N,3] replace the first attempt's
     random draws (parity tests).  `topology`: the batch's BatchTopology prepared ahead (prepare_batch; first attempt only).
-    Models without begin_sampling (test stubs) take the reference's whole-batch retry."""
+    Models without begin_sampling (test stubs) take the reference's whole-batch retry.
+    `counter_seed` (--noise counter): pos_init and the steps' noise come from the counter-based generator with this key and
+    the batch's `stream_ids` instead of torch's generator -- a conformer's draws then depend on (seed, molecule index,
+    conformer, attempt) alone.  A NaN retry draws with attempt + 1; a split-bf16 re-run of a range-only fault keeps its attempt
+    (the same draws in wider arithmetic)."""
     import torch
     T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
     spans = packed["spans"]
     n_mol = len(spans)
+    _check_counter(model, packed, counter_seed)
     if not hasattr(model, "begin_sampling"):
         at, bi, bt, ba = T(packed["atom_type"]), T(packed["bond_index"]), T(packed["bond_type"]), T(packed["batch"])
         clip_local = None
@@ -202,12 +246,18 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
         todo, clip_local, wide, tries = passes.pop(0)
         sub = packed if len(todo) == n_mol else subset_batch(packed, todo)
         at, bi, bt, ba = T(sub["atom_type"]), T(sub["bond_index"]), T(sub["bond_type"]), T(sub["batch"])
-        p0 = pos_init.to(device) if (first and pos_init is not None) else torch.randn(at.shape[0], 3).to(device)
+        counter = _counter_kwargs(sub, counter_seed, tries)
+        if first and pos_init is not None:
+            p0 = pos_init.to(device)
+        elif counter:
+            p0 = model.counter_normals(sub["batch"], counter["stream_ids"], counter_seed, [-1])[0]
+        else:
+            p0 = torch.randn(at.shape[0], 3).to(device)
         with _arithmetic(model, wide):
             extra = {"topology": topology} if (topology is not None and sub is packed) else {}
             run = model.begin_sampling(at, p0, bi, bt, ba, sub["num_graphs"], False, clip_local=clip_local,
                                        save_traj=save_traj, raise_on_nan=False,
-                                       noise=(noise if first else None), **extra, **sampler_kwargs)
+                                       noise=(noise if first else None), **extra, **counter, **sampler_kwargs)
             topology = None                    # (moved to the device and owned by the run now)
             run.advance(run.remaining())
             pos, traj = run.finish()
@@ -261,6 +311,25 @@ def _sort_results(todo, sub_spans, spans, bad_graph, out_of_range, wide, ok, pos
     return nan_failed, range_failed
 
 
+def _check_counter(model, packed, counter_seed):
+    """--noise counter needs the batch's stream ids (pack_batch: every molecule with its `index`) and a model that draws from
+    the counter-based generator."""
+    if counter_seed is None:
+        return
+    if packed.get("stream_ids") is None:
+        raise ValueError("counter noise: the packed batch carries no stream_ids (every molecule needs its 'index')")
+    if not (hasattr(model, "begin_sampling") and hasattr(model, "counter_normals")):
+        raise ValueError("counter noise: the model has no counter-based generator (begin_sampling / counter_normals)")
+
+
+def _counter_kwargs(part, counter_seed, attempt):
+    """begin_sampling's keyword arguments for counter noise on `part` (a packed batch, a subset or a rank's range of one) in
+    sampling pass `attempt` ({} in the default mode)."""
+    if counter_seed is None:
+        return {}
+    return dict(noise_mode="counter", noise_seed=int(counter_seed), stream_ids=with_attempt(part["stream_ids"], attempt))
+
+
 def _arithmetic(model, wide):
     """`wide`: the model in split-bf16 for both branches (fp32's exponent range) for the duration of one attempt."""
     import contextlib
@@ -271,7 +340,7 @@ def _arithmetic(model, wide):
 
 def subset_batch(packed, slots):
     """The packed batch restricted to the molecule slots `slots` (re-based node / graph ids)."""
-    keep_nodes, spans, batch = [], [], []
+    keep_nodes, spans, batch, keep_graphs = [], [], [], []
     node_off = g_off = 0
     shift = np.zeros(packed["atom_type"].shape[0], dtype=np.int64)
     gfirst = np.concatenate([[0], np.cumsum([g for (_, _, g) in packed["spans"]])])
@@ -279,6 +348,7 @@ def subset_batch(packed, slots):
         off, n, g = packed["spans"][s]
         idx = np.arange(off, off + n * g)
         keep_nodes.append(idx)
+        keep_graphs.append(np.arange(gfirst[s], gfirst[s] + g))
         shift[idx] = node_off - off
         batch.append(packed["batch"][idx] - gfirst[s] + g_off)
         spans.append((node_off, n, g))
@@ -289,8 +359,11 @@ def subset_batch(packed, slots):
     mask[keep] = True
     bi = packed["bond_index"]
     esel = mask[bi[0]]
-    return dict(atom_type=packed["atom_type"][keep], bond_index=bi[:, esel] + shift[bi[0][esel]][None, :],
-                bond_type=packed["bond_type"][esel], batch=np.concatenate(batch), num_graphs=g_off, spans=spans)
+    sub = dict(atom_type=packed["atom_type"][keep], bond_index=bi[:, esel] + shift[bi[0][esel]][None, :],
+               bond_type=packed["bond_type"][esel], batch=np.concatenate(batch), num_graphs=g_off, spans=spans)
+    if packed.get("stream_ids") is not None:
+        sub["stream_ids"] = np.asarray(packed["stream_ids"])[np.concatenate(keep_graphs).astype(np.int64)]
+    return sub
 
 
 def _done_indices(out_dir):
@@ -331,9 +404,14 @@ def merge_outputs(out_dir):
 
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
-            rank=0, world=1, shard=False, log=print):
+            rank=0, world=1, shard=False, log=print, noise="default", seed=2021):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
-    dict on rank 0 (None elsewhere)."""
+    dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
+    generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
+    draws whatever `max_atoms`, the plan, a resume or the number of ranks put beside it; "default": torch's generator."""
+    if noise not in ("default", "counter"):
+        raise ValueError("noise must be 'default' or 'counter'")
+    counter_seed = int(seed) if noise == "counter" else None
     import torch.distributed as dist
     os.makedirs(out_dir, exist_ok=True)
     done = set()
@@ -390,7 +468,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     fut = submit(mine[0], first=True) if mine else None
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world)
+                                world, counter_seed)
     finally:
         if worker is not None:
             worker.close()
@@ -398,7 +476,8 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
             pool.shutdown(wait=True)
 
 
-def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world):
+def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
+                     counter_seed=None):
     import torch.distributed as dist
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
@@ -420,11 +499,12 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
         if shard:
             from .dist import sample_batch_sharded
             pos, traj, ok = sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log,
-                                                 topology=topology)
+                                                 topology=topology, counter_seed=counter_seed)
             if rank != 0:
                 continue
         else:
-            pos, traj, ok = sample_batch(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log, topology=topology)
+            pos, traj, ok = sample_batch(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log, topology=topology,
+                                         counter_seed=counter_seed)
         if not ok.any():
             log("batch %d: every molecule failed twice (NaN); skipped: %s" % (bidx, [m["name"] for m in bmols]))
             continue
@@ -470,6 +550,11 @@ def main(argv=None):
                          "amortised and the node features still live in L2 / MALL; 196,608 = 3 full rounds of the node kernels' "
                          "256 x 16 x 16-node workgroups; --save-traj keeps n_steps x atoms x 12 bytes)")
     ap.add_argument("--seed", type=int, default=2021)
+    ap.add_argument("--noise", default="default", choices=["default", "counter"],
+                    help="'counter': pos_init and the steps' noise from the counter-based generator (Philox4x32-10 keyed by --seed, "
+                         "counter = atom, step, conformer stream id): 'molecule i, conformer c, seed s' draws the same numbers whatever "
+                         "--max-atoms, the packing, a --resume or the number of ranks; 'default': torch's generator seeded with "
+                         "--seed + rank, drawn over the packed batch")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
     ap.add_argument("--dist-mode", default="shard", choices=["shard", "batches"],
                     help="with several ranks: 'shard' = every packed batch (max-atoms x world atoms) is split into "
@@ -511,7 +596,8 @@ def main(argv=None):
     kw = dict(n_steps=args.n_steps, step_lr=1e-6, w_global=args.w_global, global_start_sigma=args.global_start_sigma,
               clip=args.clip)
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
-            resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"))
+            resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
+            seed=args.seed)
     if own_pg:
         dist.destroy_process_group()
 

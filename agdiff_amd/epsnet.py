@@ -403,6 +403,40 @@ class DualEncoderEpsNetwork(nn.Module):
                              group_targets=getattr(self, "group_targets", None),
                              radius_column=bool(self.tuning.get("group_radius_column", 1)))
 
+    def counter_normals(self, batch_or_topology, stream_ids, seed, steps):
+        """Standard normals [len(steps), N, 3] (float32, on the module's device) from the counter-based generator
+        (include/agdiff_hip.h: agdiff_counter_noise): row s, atom a = a pure function of (seed, stream_ids[graph of a], index of a
+        inside its graph, steps[s]) -- independent of the batch the graph is packed into.  `batch_or_topology`: the batch's
+        BatchTopology, or its `batch` vector [N] (graph id per node, sorted); `stream_ids` int64 [num_graphs], non-negative
+        (driver.stream_id); `steps`: schedule indices (the values of LangevinRun.steps), -1 = the draw reserved for the initial
+        positions: `model.counter_normals(batch, ids, seed, [-1])[0]` stands where scripts/test.py:146 has
+        torch.randn(batch.num_nodes, 3)."""
+        lib = self._require_gpu()
+        dev = self._device()
+        ids = _stream_ids_tensor(stream_ids)
+        G = int(ids.numel())
+        if isinstance(batch_or_topology, BatchTopology):
+            N, graph_ptr = batch_or_topology.N, batch_or_topology.graph_ptr
+            if batch_or_topology.G != G:
+                raise ValueError("stream_ids has %d entries, the batch has %d graphs" % (G, batch_or_topology.G))
+        else:
+            ba = torch.as_tensor(batch_or_topology).detach().reshape(-1).cpu().long()
+            N = int(ba.numel())
+            if N == 0 or G == 0:
+                raise ValueError("empty batch")
+            if bool((ba[1:] < ba[:-1]).any()) or int(ba[0]) < 0 or int(ba[-1]) >= G:
+                raise ValueError("batch must be sorted graph ids in [0, len(stream_ids))")
+            graph_ptr = torch.cat([torch.zeros(1, dtype=torch.long), torch.bincount(ba, minlength=G).cumsum(0)]).to(torch.int32)
+        st = torch.as_tensor(np.asarray(steps.detach().cpu()) if torch.is_tensor(steps) else np.asarray(list(steps), dtype=np.int64)).reshape(-1).long()
+        if st.numel() and (int(st.min()) < -1 or int(st.max()) >= 0xFFFFFFFF):
+            raise ValueError("steps must lie in [0, 2^32 - 1), or be -1 (the initial positions)")
+        # (-1 and the indices from 2^31 on as the int32 bit patterns of their unsigned counter words)
+        st = torch.where(st >= 2 ** 31, st - 2 ** 32, st).to(torch.int32)
+        graph_ptr = graph_ptr.to(dev).contiguous()
+        head = _lib.Topo()                    # (agdiff_counter_noise reads these three fields only)
+        head.num_nodes, head.num_graphs, head.graph_ptr = N, G, graph_ptr.data_ptr()
+        return _counter_fill(lib, head, N, ids.to(dev).contiguous(), seed, st.to(dev).contiguous())
+
     def _batch(self, atom_type, bond_index, bond_type, batch, num_graphs, extend_order, topology=None):
         """Static topology + workspace of this call's batch (kept on the module afterwards so that
         tests and tools can inspect the device buffers; never reused across calls)."""
@@ -600,7 +634,12 @@ class DualEncoderEpsNetwork(nn.Module):
                            reference's draws but another consumption of the Philox stream;
                            "per_step": one torch.randn_like(pos) per step, exactly the reference's call (dualenc.py:529):
                            with equal seeds and equal generator state the SAME normals as the reference draws on this
-                           device, hence seed-for-seed comparable runs (one small launch more per step)
+                           device, hence seed-for-seed comparable runs (one small launch more per step);
+                           "counter": with the keyword-only `noise_seed` (int) and `stream_ids` (int64 [num_graphs]), the normals
+                           of the step with schedule index i are agdiff_counter_noise(noise_seed, stream id of the atom's graph,
+                           atom index inside the graph, i), filled 128 steps per launch: the same numbers for a conformer
+                           wherever it is packed, whatever ran before it and however the batch is sharded
+                           (model.counter_normals gives the matching pos_init; no step graphs in this mode)
           traj_overlap_min_bytes  the trajectory goes to the host while the run samples when a poll interval's chunk
                            (nan_check_every x N x 12 B) is at least this large (default 16 MiB); else one copy at the end
         """
@@ -620,6 +659,31 @@ class DualEncoderEpsNetwork(nn.Module):
                            extend_radius=extend_radius, **kwargs)
 
 
+def _stream_ids_tensor(stream_ids):
+    """The graphs' 64-bit stream ids as a host int64 vector.  Arrays and tensors must BE int64 (ids built in a narrower type
+    have lost their molecule field already); the sign bit stays clear (driver.stream_id)."""
+    if torch.is_tensor(stream_ids):
+        ids = stream_ids.detach().cpu()
+    elif isinstance(stream_ids, np.ndarray):
+        ids = torch.from_numpy(np.ascontiguousarray(stream_ids))
+    else:
+        ids = torch.tensor([int(s) for s in stream_ids], dtype=torch.int64)
+    if ids.dtype != torch.int64 or ids.dim() != 1:
+        raise ValueError("stream_ids must be an int64 vector with one entry per graph")
+    if ids.numel() and int(ids.min()) < 0:
+        raise ValueError("stream ids must be non-negative")
+    return ids.contiguous()
+
+
+def _counter_fill(lib, topo_struct, N, ids_dev, seed, steps_dev):
+    """agdiff_counter_noise for the rows `steps_dev` (int32, device) of the batch `topo_struct` describes: [S, N, 3] on the device."""
+    S = int(steps_dev.numel())
+    out = torch.empty((S, N, 3), dtype=torch.float32, device=ids_dev.device)
+    _lib.check(lib.agdiff_counter_noise(ctypes.byref(topo_struct), _lib.ptr(ids_dev), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                        _lib.ptr(steps_dev), S, _lib.ptr(out), _lib.stream_ptr()), "agdiff_counter_noise")
+    return out
+
+
 class LangevinRun:
     """The denoising loop of dualenc.py:478-545 as an object: `advance(m)` enqueues the next m steps on
     the current stream with no host synchronisation except the periodic NaN-flag poll."""
@@ -628,7 +692,11 @@ class LangevinRun:
                  n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global, noise=None,
                  save_traj=True, skip_discarded_global=True, nan_check_every=64, step_indices=None, on_step=None,
                  extend_radius=True, raise_on_nan=True, noise_mode="chunked", traj_overlap_min_bytes=16 << 20, topology=None,
-                 **_ignored):
+                 noise_seed=None, stream_ids=None, **_ignored):
+        if noise_mode not in ("chunked", "per_step", "counter"):
+            raise ValueError("noise_mode must be 'chunked', 'per_step' or 'counter'")
+        if noise_mode == "counter" and (noise_seed is None or stream_ids is None):
+            raise ValueError("noise_mode='counter' needs noise_seed (int) and stream_ids (int64 [num_graphs])")
         self.model, self.lib = model, _lib.load()
         dev = model._device()
         self.sigmas = ((1.0 - model.alphas).sqrt() / model.alphas.sqrt()).detach().cpu()
@@ -658,9 +726,17 @@ class LangevinRun:
         self.step_lr, self.global_start_sigma = step_lr, global_start_sigma
         self.skip_discarded, self.nan_every = bool(skip_discarded_global), int(nan_check_every)
         self.raise_on_nan = bool(raise_on_nan)
-        if noise_mode not in ("chunked", "per_step"):
-            raise ValueError("noise_mode must be 'chunked' or 'per_step'")
         self.noise_mode = noise_mode
+        if noise_mode == "counter":
+            # the normals of step k are agdiff_counter_noise(noise_seed, stream_ids[graph], atom in graph, self.steps[k]): the
+            # schedule index, not k, so a run over step_indices or one continued later draws the same numbers
+            ids = _stream_ids_tensor(stream_ids)
+            if ids.numel() != self.topo.G:
+                raise ValueError("stream_ids has %d entries, the batch has %d graphs" % (ids.numel(), self.topo.G))
+            if self.steps and not (0 <= min(self.steps) and max(self.steps) < 2 ** 31):
+                raise ValueError("noise_mode='counter': schedule indices must lie in [0, 2^31)")
+            self.noise_seed, self.stream_ids = int(noise_seed), ids.to(dev).contiguous()
+            self._steps_dev = torch.tensor(self.steps, dtype=torch.int32, device=dev)
         self.k = 0
         self.range_graphs = set()              # graphs taken out of the run because they left the split-fp16 range (check_nan)
         self.ws.nan_flag.zero_()
@@ -736,7 +812,11 @@ class LangevinRun:
                 self._nz[:min(chunk, len(self.steps) - k)].normal_()
             return self._nz[k - self._nz_base]
         if self._nz is None or k >= self._nz_base + self._nz.shape[0]:
-            self._nz = torch.randn((min(chunk, len(self.steps) - k), N, 3), dtype=torch.float32, device=dev)
+            rows = min(chunk, len(self.steps) - k)
+            if self.noise_mode == "counter":       # one launch for the chunk's rows (no step graphs in this mode: __init__)
+                self._nz = _counter_fill(self.lib, self.topo.struct, N, self.stream_ids, self.noise_seed, self._steps_dev[k:k + rows])
+            else:
+                self._nz = torch.randn((rows, N, 3), dtype=torch.float32, device=dev)
             self._nz_base = k
         return self._nz[k - self._nz_base]
 

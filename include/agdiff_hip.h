@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define AGDIFF_ABI_VERSION 47
+#define AGDIFF_ABI_VERSION 48
 #define AGDIFF_HIDDEN 128          /* config.hidden_dim; InteractionBlock.lin hard-codes 256 = 2*128 (schnet.py:190) */
 #define AGDIFF_MAX_CONVS 8         /* >= config.num_convs (6) */
 #define AGDIFF_MAX_CONVS_LOCAL 8   /* >= config.num_convs_local (4) */
@@ -689,6 +689,22 @@ int agdiff_profile_cfconv_read(double* total_ms, int64_t* launches);
 /* eq_transform x2, clip_norm, Langevin update, NaN check, center_pos, clamp
  * (geometry.py:9-17; dualenc.py:506-545, 581-589) from ws->l_inv / ws->e_inv_global. */
 int agdiff_langevin_update(const agdiff_topo_t* topo, const agdiff_ws_t* ws, const agdiff_step_args_t* a, void* stream);
+
+/* Standard normals of the sampler -- noise = torch.randn_like(pos) of every denoising step (dualenc.py:529) and
+ * pos_init = torch.randn(batch.num_nodes, 3) (scripts/test.py:146) -- from a COUNTER-BASED generator instead of a generator's
+ * running state: out[s][a][0..2] is a pure function of (seed, stream_id[graph of atom a], index of a inside its graph, steps[s]),
+ * so a conformer's draws do not depend on where it sits in the packed batch, on what is packed beside it or on how the batch is
+ * cut over ranks.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key bumped by 0x9E3779B9 / 0xBB67AE85 per round) with
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (atom index inside its graph, steps[s], stream id low word, stream id high word);
+ * steps[s] = the schedule index i of the step (the diffusion timestep the loop visits, not its loop counter), -1
+ * (= 0xFFFFFFFF) is reserved for the initial positions.  A 32-bit output x gives u = ((x >> 8) + 0.5) 2^-24 in (0, 1); with
+ * r(u) = sqrt(-2 ln u): out[..][0] = r(u0) cos 2 pi u1, [1] = r(u0) sin 2 pi u1, [2] = r(u2) cos 2 pi u3 (Box-Muller; the fourth
+ * normal is dropped): every value finite, |z| <= 5.887.  Reads topo->num_nodes, num_graphs, graph_ptr only.  One launch for all
+ * num_steps rows (the loop fills 128 steps at a time); the grid covers rows x atoms whatever the molecules' sizes. */
+int agdiff_counter_noise(const agdiff_topo_t* topo, const int64_t* stream_id /* [G] */, uint64_t seed,
+                         const int32_t* steps /* [S]: the counter word c1 of every row */, int32_t num_steps,
+                         float* out /* [S][N][3] */, void* stream);
 
 /* pos_perturbed = pos + pos_noise * sqrt(1 - a) / sqrt(a) with a = alpha_graph[graph of the atom]
  * (get_loss_diffusion, dualenc.py:306-312; alpha_graph[G] = alphas.index_select(0, time_step)). */
