@@ -139,6 +139,287 @@ __global__ void __launch_bounds__(64) k_matrix_minima(const float* __restrict__ 
   if (lane == 0) (blockIdx.y == 0 ? row_min : col_min)[i] = v;
 }
 
+// ---- conformer ensembles (the step after the sampler): gen x gen RMSD over the upper triangle with a fused threshold
+// bit-matrix, the greedy leader prune over that matrix, and a Kabsch alignment that writes coordinates ----------------
+
+// tile (ti <= tj) of linear block b in the row-major walk of the upper triangle of a T x T tile grid
+__device__ __forceinline__ void ag_triangle_tile(long long b, int T, int& ti, int& tj) {
+  const double w = 2.0 * T + 1.0;
+  int r = (int)((w - sqrt(w * w - 8.0 * (double)b)) * 0.5);
+  r = r < 0 ? 0 : (r > T - 1 ? T - 1 : r);
+  // first block of tile row r: r T - r (r - 1) / 2 (the square root may be one off either way)
+  while (r > 0 && (long long)r * T - (long long)r * (r - 1) / 2 > b) --r;
+  while (r < T - 1 && (long long)(r + 1) * T - (long long)(r + 1) * r / 2 <= b) ++r;
+  ti = r;
+  tj = r + (int)(b - ((long long)r * T - (long long)r * (r - 1) / 2));
+}
+
+// 16 x 16 pairs per workgroup, upper-triangular tiles only: thread (ty, tx) = (conformer i0 + ty, conformer j0 + tx), the pair
+// arithmetic of k_rmsd_matrix with x = conformer i, y = conformer j, computed once for i < j and mirrored through LDS.
+// bits: rows of 16-bit pieces (piece w of row i = columns 16 w .. 16 w + 15), row pitch `pitch` bytes; every piece has ONE
+// writer, the tile that owns it -- (ti, tj) writes piece tj of its rows i0.. and piece ti of the rows j0.., a diagonal tile
+// its own pieces once and the zero pieces that pad its rows up to the pitch.
+__global__ void __launch_bounds__(256) k_rmsd_self(const float* __restrict__ cen, const int32_t* __restrict__ perms, int G, int m,
+                                                   int P, int T, float thresh, float* __restrict__ out,
+                                                   uint16_t* __restrict__ bits, int pitch) {
+  const int stride = 3 * m + 1;
+  float* srow = ag_eval_smem;                       // conformers i0 .. i0 + 15
+  float* scol = ag_eval_smem + 16 * stride;         // conformers j0 .. j0 + 15
+  float* sval = ag_eval_smem + 32 * stride;         // [16][17] values, then [16][17] flags
+  float* sflag = sval + 16 * 17;
+  int ti, tj;
+  ag_triangle_tile((long long)blockIdx.x, T, ti, tj);
+  const int i0 = ti * 16, j0 = tj * 16;
+  const bool diag = ti == tj;
+  for (int t = threadIdx.x; t < 16 * stride; t += 256) {
+    const int c = t / stride, o = t % stride;
+    srow[t] = (i0 + c < G) ? cen[(size_t)(i0 + c) * stride + o] : 0.0f;
+    scol[t] = (j0 + c < G) ? cen[(size_t)(j0 + c) * stride + o] : 0.0f;
+  }
+  __syncthreads();
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  const bool valid = i0 + ty < G && j0 + tx < G;
+  float v = 0.0f;
+  if (valid && (!diag || ty < tx)) {
+    const float* x = srow + ty * stride;
+    const float* y = scol + tx * stride;
+    double gsum = 0.0;
+    for (int k = 0; k < m; ++k) {
+      const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
+      const double y0 = y[3 * k], y1 = y[3 * k + 1], y2 = y[3 * k + 2];
+      gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (y0 * y0 + y1 * y1 + y2 * y2);
+    }
+    double best = 1e300;
+    for (int p = 0; p < (perms ? P : 1); ++p) {
+      const int32_t* pm = perms ? perms + (size_t)p * m : nullptr;
+      double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int k = 0; k < m; ++k) {
+        const int kr = pm ? pm[k] : k;
+        const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
+        const double y0 = y[3 * kr], y1 = y[3 * kr + 1], y2 = y[3 * kr + 2];
+        S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
+        S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
+        S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
+      }
+      const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+      const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
+                            Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
+                            -Sxx + Syy - Szz, Syz + Szy,
+                            -Sxx - Syy + Szz};
+      best = fmin(best, (gsum - 2.0 * ag_lambda_max4(K)) / m);
+    }
+    v = (float)sqrt(fmax(best, 0.0));
+  }
+  // the threshold is taken on the fp32 value as stored, so that bits == (out <= thresh) exactly
+  const float f = (valid && v <= thresh) ? 1.0f : 0.0f;
+  if (!diag || ty <= tx) { sval[ty * 17 + tx] = v; sflag[ty * 17 + tx] = f; }
+  if (diag && ty < tx) { sval[tx * 17 + ty] = v; sflag[tx * 17 + ty] = f; }      // symmetrised in LDS: the tile is written once
+  __syncthreads();
+  if (out) {
+    if (valid) out[(size_t)(i0 + ty) * G + j0 + tx] = sval[ty * 17 + tx];
+    if (!diag && j0 + ty < G && i0 + tx < G) out[(size_t)(j0 + ty) * G + i0 + tx] = sval[tx * 17 + ty];
+  }
+  if (bits) {
+    const int t = threadIdx.x;
+    if (t < 16) {                                   // piece tj of row i0 + t
+      if (i0 + t < G) {
+        unsigned w = 0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) w |= (sflag[t * 17 + c] != 0.0f ? 1u : 0u) << c;
+        bits[(size_t)(i0 + t) * (pitch >> 1) + tj] = (uint16_t)w;
+      }
+    } else if (t < 32) {                            // piece ti of row j0 + (t - 16): the transposed flags
+      const int r = t - 16;
+      if (!diag && j0 + r < G) {
+        unsigned w = 0;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) w |= (sflag[c * 17 + r] != 0.0f ? 1u : 0u) << c;
+        bits[(size_t)(j0 + r) * (pitch >> 1) + ti] = (uint16_t)w;
+      }
+    } else if (diag && t < 96) {                    // the pad pieces of the rows i0 .. i0 + 15 (at most three per row)
+      const int r = (t - 32) & 15, w = T + ((t - 32) >> 4);
+      if (i0 + r < G && w < (pitch >> 1)) bits[(size_t)(i0 + r) * (pitch >> 1) + w] = 0;
+    }
+  }
+}
+
+// Greedy leader prune over the threshold bit-matrix, in conformer order: ONE wave.  Lane l holds columns 64 l .. 64 l + 63 of
+// the kept set and of every row as one 64-bit word.  The address of row i does not depend on what became of row i - 1, so
+// AG_PRUNE_DEPTH rows are loaded ahead of the sequential walk.  leader / count are staged in LDS and written once, coalesced.
+#define AG_PRUNE_DEPTH 16
+__global__ void __launch_bounds__(64) k_leader_prune(const uint64_t* __restrict__ bits, int G, int words, int32_t* __restrict__ keep,
+                                                     int32_t* __restrict__ leader, int32_t* __restrict__ count,
+                                                     int32_t* __restrict__ n_kept) {
+  __shared__ int32_t s_leader[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ int32_t s_count[AGDIFF_PRUNE_MAX_CONFS];
+  const int lane = threadIdx.x;
+  uint64_t kept = 0;
+  uint64_t cur[AG_PRUNE_DEPTH], nxt[AG_PRUNE_DEPTH];
+#pragma unroll
+  for (int d = 0; d < AG_PRUNE_DEPTH; ++d) cur[d] = (d < G && lane < words) ? bits[(size_t)d * words + lane] : 0;
+  for (int base = 0; base < G; base += AG_PRUNE_DEPTH) {
+#pragma unroll
+    for (int d = 0; d < AG_PRUNE_DEPTH; ++d) {
+      const int r = base + AG_PRUNE_DEPTH + d;
+      nxt[d] = (r < G && lane < words) ? bits[(size_t)r * words + lane] : 0;
+    }
+#pragma unroll
+    for (int d = 0; d < AG_PRUNE_DEPTH; ++d) {
+      const int i = base + d;
+      if (i < G) {                                  // (wave-uniform)
+        const uint64_t hit = cur[d] & kept;         // kept holds only j < i
+        const unsigned long long any = __ballot(hit != 0);
+        if (any == 0) {
+          if (lane == (i >> 6)) kept |= 1ull << (i & 63);
+          if (lane == 0) { s_leader[i] = i; s_count[i] = 1; }
+        } else {
+          const int first = __ffsll((long long)any) - 1;
+          if (lane == first) {
+            const int l = first * 64 + __ffsll((long long)hit) - 1;      // the smallest kept j with bit (i, j)
+            s_leader[i] = l;
+            s_count[l] += 1;
+            s_count[i] = 0;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < AG_PRUNE_DEPTH; ++d) cur[d] = nxt[d];
+  }
+  __syncthreads();
+  for (int i = lane; i < G; i += 64) {
+    const int l = s_leader[i];
+    leader[i] = l;
+    keep[i] = l == i ? 1 : 0;
+    count[i] = s_count[i];
+  }
+  int k = __popcll(kept);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o);
+  if (lane == 0) n_kept[0] = k;
+}
+
+// eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_lambda_max4) by the same cyclic Jacobi sweeps, with
+// the rotations accumulated: returns the largest eigenvalue and its unit eigenvector q
+__device__ double ag_eigvec_max4(const double (&k)[10], double (&q)[4]) {
+  double A[4][4] = {{k[0], k[1], k[2], k[3]}, {k[1], k[4], k[5], k[6]}, {k[2], k[5], k[7], k[8]}, {k[3], k[6], k[8], k[9]}};
+  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    double off = 0.0;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int q_ = p + 1; q_ < 4; ++q_) off += A[p][q_] * A[p][q_];
+    if (off < 1e-30) break;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int q_ = p + 1; q_ < 4; ++q_) {
+        const double apq = A[p][q_];
+        if (apq == 0.0) continue;
+        const double theta = (A[q_][q_] - A[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double arp = A[r][p], arq = A[r][q_];
+          A[r][p] = c * arp - s * arq;
+          A[r][q_] = s * arp + c * arq;
+          const double vrp = V[r][p], vrq = V[r][q_];
+          V[r][p] = c * vrp - s * vrq;
+          V[r][q_] = s * vrp + c * vrq;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double apr = A[p][r], aqr = A[q_][r];
+          A[p][r] = c * apr - s * aqr;
+          A[q_][r] = s * apr + c * aqr;
+        }
+      }
+    }
+  }
+  double lam = A[0][0];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) q[r] = V[r][0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    const bool up = A[j][j] > lam;
+    lam = up ? A[j][j] : lam;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) q[r] = up ? V[r][j] : q[r];
+  }
+  const double nrm = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) q[r] *= nrm;
+  return lam;
+}
+
+// one wave per conformer, shaped like k_center_selected: centroids and the cross-covariance over the selected atoms in fp64
+// (reduced across lanes, so every lane solves the same 4x4 problem), Horn's quaternion of lambda_max -> a proper rotation R,
+// out = R (x - c_x) + c_target for ALL n atoms; rmsd = the identity-mapping RMSD of the stored coordinates over the selection
+__global__ void __launch_bounds__(64) k_align_conformers(const float* __restrict__ pos, const int32_t* __restrict__ idx,
+                                                         const float* __restrict__ target, int n, int m, float* __restrict__ out,
+                                                         float* __restrict__ rmsd) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  double c[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = lane; k < m; k += 64) {
+    const int a = idx[k];
+    c[0] += p[3 * a]; c[1] += p[3 * a + 1]; c[2] += p[3 * a + 2];
+    c[3] += target[3 * a]; c[4] += target[3 * a + 1]; c[5] += target[3 * a + 2];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int e = 0; e < 6; ++e) c[e] += __shfl_xor(c[e], o);
+#pragma unroll
+  for (int e = 0; e < 6; ++e) c[e] /= m;
+  double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = lane; k < m; k += 64) {
+    const int a = idx[k];
+    const double x0 = p[3 * a] - c[0], x1 = p[3 * a + 1] - c[1], x2 = p[3 * a + 2] - c[2];
+    const double y0 = target[3 * a] - c[3], y1 = target[3 * a + 1] - c[4], y2 = target[3 * a + 2] - c[5];
+    S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
+    S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
+    S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int e = 0; e < 9; ++e) S[e] += __shfl_xor(S[e], o);
+  const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+  const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
+                        Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
+                        -Sxx + Syy - Szz, Syz + Szy,
+                        -Sxx - Syy + Szz};
+  double q[4];
+  ag_eigvec_max4(K, q);
+  const double q0 = q[0], qx = q[1], qy = q[2], qz = q[3];
+  const double R[9] = {q0 * q0 + qx * qx - qy * qy - qz * qz, 2.0 * (qx * qy - q0 * qz), 2.0 * (qx * qz + q0 * qy),
+                       2.0 * (qy * qx + q0 * qz), q0 * q0 - qx * qx + qy * qy - qz * qz, 2.0 * (qy * qz - q0 * qx),
+                       2.0 * (qz * qx - q0 * qy), 2.0 * (qz * qy + q0 * qx), q0 * q0 - qx * qx - qy * qy + qz * qz};
+  float* o = out + (size_t)g * n * 3;
+  for (int a = lane; a < n; a += 64) {
+    const double x0 = p[3 * a] - c[0], x1 = p[3 * a + 1] - c[1], x2 = p[3 * a + 2] - c[2];
+    o[3 * a] = (float)(R[0] * x0 + R[1] * x1 + R[2] * x2 + c[3]);
+    o[3 * a + 1] = (float)(R[3] * x0 + R[4] * x1 + R[5] * x2 + c[4]);
+    o[3 * a + 2] = (float)(R[6] * x0 + R[7] * x1 + R[8] * x2 + c[5]);
+  }
+  if (!rmsd) return;
+  double d2 = 0.0;
+  for (int k = lane; k < m; k += 64) {            // (another lane stored atom idx[k]: recomputed here, rounded as it was stored)
+    const int a = idx[k];
+    const double x0 = p[3 * a] - c[0], x1 = p[3 * a + 1] - c[1], x2 = p[3 * a + 2] - c[2];
+    const double e0 = (double)(float)(R[0] * x0 + R[1] * x1 + R[2] * x2 + c[3]) - target[3 * a];
+    const double e1 = (double)(float)(R[3] * x0 + R[4] * x1 + R[5] * x2 + c[4]) - target[3 * a + 1];
+    const double e2 = (double)(float)(R[6] * x0 + R[7] * x1 + R[8] * x2 + c[5]) - target[3 * a + 2];
+    d2 += e0 * e0 + e1 * e1 + e2 * e2;
+  }
+#pragma unroll
+  for (int o_ = 32; o_ > 0; o_ >>= 1) d2 += __shfl_xor(d2, o_);
+  if (lane == 0) rmsd[g] = (float)sqrt(d2 / m);
+}
+
 }  // namespace
 
 extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
@@ -168,6 +449,46 @@ extern "C" int agdiff_matrix_minima(const float* mat, int32_t R, int32_t G, floa
   if (!mat || !row_min || !col_min || R <= 0 || G <= 0) return AGDIFF_ERR_ARG;
   const int mx = R > G ? R : G;
   k_matrix_minima<<<dim3((unsigned)mx, 2), dim3(64), 0, (hipStream_t)stream>>>(mat, R, G, row_min, col_min);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_rmsd_self(const float* pos, const int32_t* atom_idx, const int32_t* perms, int32_t G, int32_t n, int32_t m,
+                                int32_t P, float thresh, float* scratch, float* out, uint64_t* bits, void* stream) {
+  if (!pos || !atom_idx || !scratch || (!out && !bits) || G < 0 || n <= 0 || m <= 0 || m > n || (perms && P <= 0)) return AGDIFF_ERR_ARG;
+  if (bits && (!(thresh >= 0.0f) || ((uintptr_t)bits & 7))) return AGDIFF_ERR_ARG;
+  if (m > AGDIFF_RMSD_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) return AGDIFF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  k_center_selected<<<dim3((unsigned)G), dim3(64), 0, st>>>(pos, atom_idx, n, m, scratch);
+  AG_CHECK_LAUNCH();
+  const int64_t T = ((int64_t)G + 15) / 16;
+  const int64_t tiles = T * (T + 1) / 2;
+  if (tiles > 0x7fffffffll) return AGDIFF_ERR_LIMIT;
+  const auto smem_for = [](int mm) { return ((size_t)2 * 16 * (3 * mm + 1) + 2 * 16 * 17) * sizeof(float); };
+  static std::atomic<uint64_t> attr_done{0};
+  if (smem_for(m) > 48 * 1024 && !ag_allow_big_lds(attr_done, smem_for(AGDIFF_RMSD_MAX_ATOMS), k_rmsd_self)) return AGDIFF_ERR_LAUNCH;
+  const int pitch = (int)((T * 2 + 7) / 8 * 8);
+  k_rmsd_self<<<dim3((unsigned)tiles), dim3(256), smem_for(m), st>>>(scratch, perms, G, m, P, (int)T, thresh, out, (uint16_t*)bits, pitch);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* keep, int32_t* leader, int32_t* count, int32_t* n_kept,
+                                   void* stream) {
+  if (!bits || !keep || !leader || !count || !n_kept || G < 0 || ((uintptr_t)bits & 7)) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  const int words = (((G + 15) / 16) * 2 + 7) / 8;        // 64-bit words per row = the row pitch of agdiff_rmsd_self / 8
+  k_leader_prune<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(bits, G, words, keep, leader, count, n_kept);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_align_conformers(const float* pos, const int32_t* atom_idx, const float* target, int32_t G, int32_t n, int32_t m,
+                                       float* out, float* rmsd, void* stream) {
+  if (!pos || !atom_idx || !target || !out || G < 0 || n <= 0 || m <= 0 || m > n) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_align_conformers<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, atom_idx, target, n, m, out, rmsd);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -11,7 +11,7 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 (bond graph; already extended to order 3 like `AddHigherOrderEdges` does unless --extend-order),
 `num_refs_i` scalar, `name_i` string.  Output: `samples_<first>_<last>.npz` per batch (named by the molecule
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
---save-traj) and the merged `samples_all.npz`, written by rank 0 after a barrier.
+--save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T) and the merged `samples_all.npz`, written by rank 0 after a barrier.
 
 `--noise counter` draws every conformer's pos_init and noise from the counter-based generator under `--seed` and the conformer's
 stream id (`stream_id`): the same numbers whatever --max-atoms, the packing, a --resume or the number of ranks.
@@ -404,13 +404,20 @@ def merge_outputs(out_dir):
 
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
-            rank=0, world=1, shard=False, log=print, noise="default", seed=2021):
+            rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
-    draws whatever `max_atoms`, the plan, a resume or the number of ranks put beside it; "default": torch's generator."""
+    draws whatever `max_atoms`, the plan, a resume or the number of ranks put beside it; "default": torch's generator.
+    prune_rms=T (Angstrom, >= 0): every saved molecule also gets `kept_<i>` int32 [K] -- the conformers RDKit's pruneRmsThresh rule
+    keeps at T, indices into `pos_gen_<i>` -- and `cluster_<i>` int32 [G], the kept conformer each one belongs to
+    (agdiff_amd.ensemble.prune_conformers on the GPU, symmetry-aware through the molecule's bonds; at most
+    AGDIFF_PRUNE_MAX_CONFS conformers per molecule).  `pos_gen_<i>` holds all conformers either way.  One molecule at a time, after
+    the batch's retries have settled, by the rank that writes the batch's file: a few launches next to seconds of sampling."""
     if noise not in ("default", "counter"):
         raise ValueError("noise must be 'default' or 'counter'")
+    if prune_rms is not None and not float(prune_rms) >= 0.0:
+        raise ValueError("prune_rms must be >= 0 (an RMSD threshold in Angstrom) or None")
     counter_seed = int(seed) if noise == "counter" else None
     import torch.distributed as dist
     os.makedirs(out_dir, exist_ok=True)
@@ -468,7 +475,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     fut = submit(mine[0], first=True) if mine else None
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world, counter_seed)
+                                world, counter_seed, prune_rms)
     finally:
         if worker is not None:
             worker.close()
@@ -477,7 +484,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None):
+                     counter_seed=None, prune_rms=None):
     import torch.distributed as dist
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
@@ -515,6 +522,12 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 continue
             out["pos_gen_%d" % m["index"]] = pos[off:off + n * g].numpy().reshape(g, n, 3)
             out["name_%d" % m["index"]] = np.str_(m["name"])
+            if prune_rms is not None:
+                from .ensemble import prune_conformers
+                res = prune_conformers(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
+                                            edge_type=m["edge_type"]), float(prune_rms), align=False, device=device)
+                out["kept_%d" % m["index"]] = res["kept"].cpu().numpy()
+                out["cluster_%d" % m["index"]] = res["leader"].cpu().numpy()
             if traj is not None:
                 out["traj_%d" % m["index"]] = traj[:, off:off + n * g].numpy().reshape(traj.shape[0], g, n, 3)
         _save_npz_atomic(_batch_path(out_dir, bmols), out)
@@ -555,6 +568,9 @@ def main(argv=None):
                          "counter = atom, step, conformer stream id): 'molecule i, conformer c, seed s' draws the same numbers whatever "
                          "--max-atoms, the packing, a --resume or the number of ranks; 'default': torch's generator seeded with "
                          "--seed + rank, drawn over the packed batch")
+    ap.add_argument("--prune-rms", type=float, default=None,
+                    help="also save, per molecule, which conformers RDKit's pruneRmsThresh rule keeps at this heavy-atom RMSD "
+                         "(Angstrom; symmetry-aware): kept_<i> and cluster_<i> next to pos_gen_<i>, which still holds them all")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
     ap.add_argument("--dist-mode", default="shard", choices=["shard", "batches"],
                     help="with several ranks: 'shard' = every packed batch (max-atoms x world atoms) is split into "
@@ -597,7 +613,7 @@ def main(argv=None):
               clip=args.clip)
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
-            seed=args.seed)
+            seed=args.seed, prune_rms=args.prune_rms)
     if own_pg:
         dist.destroy_process_group()
 

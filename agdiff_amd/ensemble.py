@@ -1,0 +1,195 @@
+"""Conformer ensembles -- the step after the sampler: prune the 2 x num_refs raw conformers of a molecule to the ones that
+differ (RDKit's EmbedMultipleConfs(pruneRmsThresh=...) rule) and superpose what is kept (AlignMolConformers).
+
+Everything runs on the GPU (csrc/eval.hip), and there is no CPU fallback:
+    agdiff_rmsd_self         gen x gen symmetry-aware RMSD, every pair once (upper-triangular tiles), with the adjacency
+                             under the threshold as a bit-matrix
+    agdiff_leader_prune      the greedy leader walk over that bit-matrix, in conformer order
+    agdiff_align_conformers  Kabsch superposition that writes coordinates
+
+Items are the plain dicts of agdiff_amd.evaluation: atom_type [n], pos_gen [G*n, 3] or [G, n, 3], and optionally the bonds
+(bond_index + bond_type, or edge_index + edge_type) or perms [P, m] -- with them the RMSD is the minimum over the molecule's
+heavy-atom self-matches (GetBestRMS), without them the identity mapping only.  Hydrogens take no part in the RMSD and ride
+along in the alignment.
+
+    python -m agdiff_amd.ensemble --samples out/samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
+"""
+import numpy as np
+
+from . import _lib
+from .evaluation import _as_conformers, selection_of
+
+MAX_CONFS = _lib.DEFINES["AGDIFF_PRUNE_MAX_CONFS"]
+
+
+def bits_pitch(G):
+    """Bytes per row of the threshold bit-matrix of G conformers: 16-bit pieces, rounded up to 8 bytes."""
+    return ((((G + 15) // 16) * 2 + 7) // 8) * 8
+
+
+def _check_threshold(threshold):
+    t = float(threshold)
+    if not t >= 0.0:
+        raise ValueError("the RMSD threshold must be >= 0 (got %r)" % (threshold,))
+    return t
+
+
+def _self_rmsd(item, device, threshold=None, want_out=True):
+    """(gen [G, n, 3] on the device, heavy index tensor, out [G, G] or None, bits int64 [G, pitch / 8] or None)"""
+    import torch
+    lib = _lib.load()
+    at, heavy, pa = selection_of(item)
+    n, m = at.shape[0], int(heavy.size)
+    gen = _as_conformers(item["pos_gen"], n).to(device).contiguous()
+    G = gen.shape[0]
+    idx = torch.from_numpy(heavy).to(device)
+    P, pt = 0, None
+    if pa is not None:
+        P, pt = pa.shape[0], torch.from_numpy(pa).to(device)
+    out = torch.empty((G, G), dtype=torch.float32, device=device) if want_out else None
+    bits = None
+    if threshold is not None:
+        bits = torch.empty((G, bits_pitch(G) // 8), dtype=torch.int64, device=device)
+    scratch = torch.empty(max(G, 1) * (3 * m + 1), dtype=torch.float32, device=device)
+    with torch.cuda.device(gen.device):
+        _lib.check(lib.agdiff_rmsd_self(_lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), G, n, m, P,
+                                        0.0 if threshold is None else threshold, _lib.ptr(scratch), _lib.ptr(out),
+                                        _lib.ptr(bits), _lib.stream_ptr()), "agdiff_rmsd_self")
+    return gen, idx, out, bits
+
+
+def self_rmsd_matrix(item, device="cuda"):
+    """The [G, G] matrix of best RMSDs between the item's generated conformers (float32 tensor on `device`): what
+    evaluation.get_rmsd_confusion_matrix gives with pos_ref = pos_gen, each pair computed once -- exactly symmetric, zero
+    diagonal.  The mirror is exact when the mappings form a group (heavy_atom_automorphisms does; so must `perms`)."""
+    return _self_rmsd(item, device)[2]
+
+
+def threshold_bits(item, threshold, device="cuda"):
+    """(out [G, G], adjacency bool [G, 8 * pitch]): the matrix and the kernel's packed `out <= threshold`, unpacked (columns
+    from G on are padding)."""
+    t = _check_threshold(threshold)
+    gen, _, out, bits = _self_rmsd(item, device, threshold=t)
+    return out, unpack_bits(bits, gen.shape[0])
+
+
+def unpack_bits(bits, G):
+    """bool [G, 8 * pitch] from the packed rows (int64 [G, pitch / 8]; little-endian: bit c of byte b = column 8 b + c)."""
+    import torch
+    by = bits.view(torch.uint8).reshape(G, -1).to(torch.int32)
+    sh = torch.arange(8, device=bits.device, dtype=torch.int32)
+    return ((by[:, :, None] >> sh[None, None, :]) & 1).reshape(G, -1).bool()
+
+
+def leader_prune(bits, G):
+    """agdiff_leader_prune on a packed bit-matrix (int64 [G, pitch / 8] on the GPU): (keep, leader, count, n_kept) int32.
+    More than AGDIFF_PRUNE_MAX_CONFS conformers: AgdiffLimitError."""
+    import torch
+    lib = _lib.load()
+    dev = bits.device
+    keep, leader, count = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(3))
+    n_kept = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.agdiff_leader_prune(_lib.ptr(bits), G, _lib.ptr(keep), _lib.ptr(leader), _lib.ptr(count),
+                                           _lib.ptr(n_kept), _lib.stream_ptr()), "agdiff_leader_prune")
+    return keep, leader, count, n_kept
+
+
+def _align(pos, idx, target):
+    import torch
+    lib = _lib.load()
+    G, n = pos.shape[0], pos.shape[1]
+    out = torch.empty_like(pos)
+    rmsd = torch.empty(G, dtype=torch.float32, device=pos.device)
+    with torch.cuda.device(pos.device):
+        _lib.check(lib.agdiff_align_conformers(_lib.ptr(pos), _lib.ptr(idx), _lib.ptr(target), G, n, int(idx.shape[0]),
+                                               _lib.ptr(out), _lib.ptr(rmsd), _lib.stream_ptr()), "agdiff_align_conformers")
+    return out, rmsd
+
+
+def align_conformers(pos, atom_type, target, device="cuda"):
+    """Superpose every conformer of pos [G, n, 3] (or [G*n, 3]) on target [n, 3] over the heavy atoms, atoms keeping their
+    labels (rdkit AlignMolConformers): proper rotation + translation, applied to all atoms.  Returns (aligned [G, n, 3],
+    rmsd [G]: the heavy-atom RMSD to the target after alignment) as float32 tensors on `device`."""
+    import torch
+    at = np.asarray(atom_type).reshape(-1)
+    n = at.shape[0]
+    heavy = np.nonzero(at != 1)[0].astype(np.int32)
+    if heavy.size == 0:
+        raise ValueError("molecule without heavy atoms")
+    p = _as_conformers(pos, n).to(device).contiguous()
+    t = _as_conformers(target, n).to(device).contiguous()
+    if t.shape[0] != 1:
+        raise ValueError("target must be one conformer [n, 3]")
+    return _align(p, torch.from_numpy(heavy).to(device), t[0])
+
+
+def prune_conformers(item, threshold, align=True, device="cuda"):
+    """RDKit's pruneRmsThresh rule over the item's generated conformers, in their order: a conformer is kept iff its best RMSD
+    to every conformer kept before it is above `threshold`; a dropped one belongs to the first kept conformer within the
+    threshold.  Returns a dict of tensors on `device`:
+        kept   int32 [K]  indices of the kept conformers, ascending
+        leader int32 [G]  for every conformer the kept conformer it belongs to (itself when kept)
+        count  int32 [K]  size of each kept conformer's cluster (itself included)
+        pos    [K, n, 3]  the kept conformers; with align=True superposed on the first of them over the heavy atoms (that one
+                          is returned as it is, bit for bit)
+    At most AGDIFF_PRUNE_MAX_CONFS conformers."""
+    import torch
+    t = _check_threshold(threshold)
+    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    gen = _as_conformers(item["pos_gen"], n)
+    G = gen.shape[0]
+    if G == 0:
+        raise ValueError("no conformers to prune")
+    if G > MAX_CONFS:
+        raise _lib.AgdiffLimitError("prune_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
+    gen, idx, _, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
+    keep, leader, count, _ = leader_prune(bits, G)
+    kept = torch.nonzero(keep, as_tuple=False).reshape(-1)
+    pos = gen[kept]
+    if align and pos.shape[0] > 0:
+        first = pos[0].clone()
+        pos, _ = _align(pos, idx, first)
+        pos[0] = first
+    return {"kept": kept.to(torch.int32), "leader": leader, "count": count[kept], "pos": pos}
+
+
+def main(argv=None):
+    """python -m agdiff_amd.ensemble --samples samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
+    Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
+    symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
+    (+ `name_<i>`)."""
+    import argparse
+    from .driver import load_testset
+    ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--samples", required=True)
+    ap.add_argument("--testset", required=True)
+    ap.add_argument("--prune-rms", type=float, required=True, help="RMSD threshold in Angstrom (heavy atoms)")
+    ap.add_argument("--align", action="store_true", help="superpose the kept conformers on the first of them")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    _check_threshold(args.prune_rms)
+    zs = np.load(args.samples)
+    out, total, left = {}, 0, 0
+    for mol in load_testset(args.testset):
+        i = mol["index"]
+        if "pos_gen_%d" % i not in zs.files:
+            continue
+        item = {"atom_type": mol["atom_type"], "pos_gen": zs["pos_gen_%d" % i], "edge_index": mol["edge_index"],
+                "edge_type": mol["edge_type"]}
+        res = prune_conformers(item, args.prune_rms, align=args.align, device=args.device)
+        out["pos_%d" % i] = res["pos"].cpu().numpy()
+        out["kept_%d" % i] = res["kept"].cpu().numpy()
+        out["cluster_%d" % i] = res["leader"].cpu().numpy()
+        out["count_%d" % i] = res["count"].cpu().numpy()
+        out["name_%d" % i] = np.str_(mol["name"])
+        total += int(res["leader"].shape[0])
+        left += int(res["kept"].shape[0])
+    np.savez_compressed(args.out, **out)
+    print("pruned %d conformers to %d at %.3f A" % (total, left, args.prune_rms))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -130,21 +130,16 @@ def heavy_atom_automorphisms(atom_type, bond_index, bond_type, max_perms=65536):
     return out
 
 
-def get_rmsd_confusion_matrix(data, useFF=False, device="cuda"):
-    """covmat.py:16-35.  Returns a float32 torch tensor [num_ref, num_gen] on `device`."""
-    import torch
-    if useFF:
-        raise NotImplementedError("MMFF relaxation needs rdkit (covmat.py:27-29); not available here")
-    lib = _lib.load()
+def selection_of(data):
+    """What the RMSD of one item runs over (shared with agdiff_amd.ensemble): (atom_type [n], heavy-atom indices int32 [m],
+    atom mappings int32 [P, m] or None).  The mappings are the item's `perms`, or -- when it carries its bonds (bond_index +
+    bond_type, or edge_index + edge_type) -- the molecule's own symmetry as GetBestRMS finds it (heavy_atom_automorphisms);
+    None = the identity only."""
     at = np.asarray(data["atom_type"]).reshape(-1)
-    n = at.shape[0]
-    ref = _as_conformers(data["pos_ref"], n).to(device).contiguous()
-    gen = _as_conformers(data["pos_gen"], n).to(device).contiguous()
     heavy = np.nonzero(at != 1)[0].astype(np.int32)
     if heavy.size == 0:
         raise ValueError("molecule without heavy atoms")
     m = int(heavy.size)
-    idx = torch.from_numpy(heavy).to(device)
     get = (lambda k: data.get(k)) if isinstance(data, dict) else (lambda k: getattr(data, k, None))
     perms = get("perms")
     if perms is None:       # the molecule's own symmetry, as GetBestRMS finds it, when the item carries its bonds
@@ -152,11 +147,28 @@ def get_rmsd_confusion_matrix(data, useFF=False, device="cuda"):
         b_typ = get("bond_type") if get("bond_type") is not None else get("edge_type")
         if b_idx is not None and b_typ is not None:
             perms = heavy_atom_automorphisms(at, b_idx, b_typ)
+    if perms is None:
+        return at, heavy, None
+    pa = np.ascontiguousarray(np.asarray(perms, dtype=np.int32).reshape(-1, m))
+    if pa.min() < 0 or pa.max() >= m or not all(np.array_equal(np.sort(r), np.arange(m)) for r in pa):
+        raise ValueError("perms must hold permutations of the %d heavy atoms" % m)
+    return at, heavy, pa
+
+
+def get_rmsd_confusion_matrix(data, useFF=False, device="cuda"):
+    """covmat.py:16-35.  Returns a float32 torch tensor [num_ref, num_gen] on `device`."""
+    import torch
+    if useFF:
+        raise NotImplementedError("MMFF relaxation needs rdkit (covmat.py:27-29); not available here")
+    lib = _lib.load()
+    n = np.asarray(data["atom_type"]).reshape(-1).shape[0]
+    ref = _as_conformers(data["pos_ref"], n).to(device).contiguous()
+    gen = _as_conformers(data["pos_gen"], n).to(device).contiguous()
+    _, heavy, pa = selection_of(data)
+    m = int(heavy.size)
+    idx = torch.from_numpy(heavy).to(device)
     P, pt = 0, None
-    if perms is not None:
-        pa = np.ascontiguousarray(np.asarray(perms, dtype=np.int32).reshape(-1, m))
-        if pa.min() < 0 or pa.max() >= m or not all(np.array_equal(np.sort(r), np.arange(m)) for r in pa):
-            raise ValueError("perms must hold permutations of the %d heavy atoms" % m)
+    if pa is not None:
         P, pt = pa.shape[0], torch.from_numpy(pa).to(device)
     R, G = ref.shape[0], gen.shape[0]
     out = torch.empty((R, G), dtype=torch.float32, device=device)

@@ -39,7 +39,8 @@ extern "C" {
 #define AGDIFF_RADIUS_CAP 33       /* max_num_neighbors + 1 (torch_cluster.radius_graph, common.py:217) */
 #define AGDIFF_TILE 16             /* edges / nodes per MFMA tile */
 #define AGDIFF_MAX_CHUNK_TILES 8   /* most tiles one wave walks per chunk in the fused CFConv kernel (128 edges) */
-#define AGDIFF_RMSD_MAX_ATOMS 256  /* most (heavy) atoms per conformer in agdiff_rmsd_matrix */
+#define AGDIFF_RMSD_MAX_ATOMS 256  /* most (heavy) atoms per conformer in agdiff_rmsd_matrix / agdiff_rmsd_self */
+#define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
 #define AGDIFF_POLY_MAX_KT 4       /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
 #define AGDIFF_POLY_MAX_SLOTS 16   /* most local edge types with filter polynomials; the first sets that fit stay in LDS next to the
@@ -740,6 +741,43 @@ int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t
 /* Row and column minima of a confusion matrix [R][G] (covmat.py:135-136: rmsd_ref_min = min over generated,
  * rmsd_gen_min = min over references): row_min [R], col_min [G]. */
 int agdiff_matrix_minima(const float* mat, int32_t R, int32_t G, float* row_min, float* col_min, void* stream);
+
+/* ---- conformer ensembles (after the sampler): prune near-duplicates by symmetry-aware RMSD, superpose the rest ------
+ * What rdkit's EmbedMultipleConfs(pruneRmsThresh=...) / AlignMolConformers do with a conformer set, for the 2 x num_refs
+ * conformers per molecule that scripts/test.py:135-141 samples.  Three calls, no atomics, deterministic bit for bit.
+ *
+ * agdiff_rmsd_self: the G x G matrix of agdiff_rmsd_matrix(pos, pos) computed ONCE per pair.  For i < j the value is that
+ * call's quantity with x = conformer i, y = conformer j (mapping p pairs atom atom_idx[k] of i with atom
+ * atom_idx[perms[p][k]] of j), stored at [i][j] and mirrored to [j][i]; the diagonal is 0.  The mirror is the true
+ * [j][i] value when `perms` is closed under inversion -- a group, as heavy_atom_automorphisms returns -- or null.
+ * The launch covers the T (T + 1) / 2 upper-triangular 16 x 16 tiles only, T = ceil(G / 16).
+ *   pos [G][n][3], atom_idx [m] (m <= AGDIFF_RMSD_MAX_ATOMS), perms [P][m] or null
+ *   scratch [G * (3 m + 1)] floats     centred coordinates (written by the call)
+ *   out [G][G] or null                 exactly symmetric
+ *   bits or null                       the adjacency under `thresh` (>= 0): bit (i, j) = out[i][j] <= thresh, taken on the
+ *                                      fp32 value as stored; diagonal set; bits of columns >= G zero.  Rows of 16-bit pieces,
+ *                                      piece w of row i = columns 16 w .. 16 w + 15 (bit c = column 16 w + c), row pitch
+ *                                      = 2 T bytes rounded up to 8; G rows; 8-byte aligned.  Read as little-endian 64-bit
+ *                                      words, word l of a row holds columns 64 l .. 64 l + 63.
+ * At least one of out / bits must be given. */
+int agdiff_rmsd_self(const float* pos, const int32_t* atom_idx, const int32_t* perms, int32_t G, int32_t n, int32_t m,
+                     int32_t P, float thresh, float* scratch, float* out, uint64_t* bits, void* stream);
+
+/* The greedy leader algorithm in conformer order (pruneRmsThresh) over `bits` in the layout above: conformer i is kept iff
+ * no KEPT j < i has bit (i, j); otherwise leader[i] is the smallest such j.  keep [G] (1 / 0), leader [G] (= i for a kept
+ * conformer), count [G] (conformers led by i, itself included; 0 for a dropped one), n_kept [1].  One wave walks the rows in
+ * order with the next rows already in flight.  G <= AGDIFF_PRUNE_MAX_CONFS, else AGDIFF_ERR_LIMIT. */
+int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* keep, int32_t* leader, int32_t* count, int32_t* n_kept,
+                        void* stream);
+
+/* Rigid superposition (rdkit AlignMolConformers: atoms keep their labels, identity mapping): for each conformer the proper
+ * rotation R and translation that minimise the RMSD to `target` over the atoms `atom_idx` (Horn's quaternion, fp64), applied
+ * to ALL n atoms: out = R (x - c_x) + c_target, so hydrogens ride along.  No reflection: a mirror image stays apart.  When
+ * the best rotation is not unique (collinear atoms) one of the maximisers is taken.
+ *   pos [G][n][3], atom_idx [m], target [n][3], out [G][n][3] (not overlapping pos),
+ *   rmsd [G] or null: the RMSD over atom_idx between out, as stored, and target */
+int agdiff_align_conformers(const float* pos, const int32_t* atom_idx, const float* target, int32_t G, int32_t n, int32_t m,
+                            float* out, float* rmsd, void* stream);
 
 #ifdef __cplusplus
 }
