@@ -420,6 +420,152 @@ __global__ void __launch_bounds__(64) k_align_conformers(const float* __restrict
   if (lane == 0) rmsd[g] = (float)sqrt(d2 / m);
 }
 
+// ---- handedness: the sampler cannot tell a molecule from its mirror image (the score network sees distances only), so the RMSD
+// to the mirror image, the parity of the stereocentres and the inversion of a wrong-handed conformer live here ----------------
+
+// ag_lambda_max4's sweeps, statement for statement, returning BOTH extreme diagonal entries.  K is linear in the cross-covariance
+// S and inverting one conformer through its centroid turns S into -S, so lambda_max(K(-S)) = -lambda_min(K(S)): the best fit of
+// the mirror image comes out of the diagonalisation the proper fit already pays for.
+__device__ void ag_lambda_ext4(const double (&k)[10], double& lmax, double& lmin) {
+  double A[4][4] = {{k[0], k[1], k[2], k[3]}, {k[1], k[4], k[5], k[6]}, {k[2], k[5], k[7], k[8]}, {k[3], k[6], k[8], k[9]}};
+  for (int sweep = 0; sweep < 12; ++sweep) {
+    double off = 0.0;
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
+    if (off < 1e-30) break;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < 4; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {           // columns p, q
+          const double arp = A[r][p], arq = A[r][q];
+          A[r][p] = c * arp - s * arq;
+          A[r][q] = s * arp + c * arq;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {           // rows p, q
+          const double apr = A[p][r], aqr = A[q][r];
+          A[p][r] = c * apr - s * aqr;
+          A[q][r] = s * apr + c * aqr;
+        }
+      }
+    }
+  }
+  lmax = fmax(fmax(A[0][0], A[1][1]), fmax(A[2][2], A[3][3]));
+  lmin = fmin(fmin(A[0][0], A[1][1]), fmin(A[2][2], A[3][3]));
+}
+
+// k_rmsd_matrix with a second result: out_proper is that kernel's value, out_mirror the same quantity for the generated
+// conformer inverted through its centroid, minimised over the same mappings
+__global__ void __launch_bounds__(256) k_rmsd_matrix_hands(const float* __restrict__ cref, const float* __restrict__ cgen,
+                                                           const int32_t* __restrict__ perms, int R, int G, int m, int P,
+                                                           float* __restrict__ out_proper, float* __restrict__ out_mirror) {
+  const int stride = 3 * m + 1;
+  float* sref = ag_eval_smem;
+  float* sgen = ag_eval_smem + 16 * stride;
+  const int j0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
+  for (int t = threadIdx.x; t < 16 * stride; t += 256) {
+    const int c = t / stride, o = t % stride;
+    sref[t] = (j0 + c < R) ? cref[(size_t)(j0 + c) * stride + o] : 0.0f;
+    sgen[t] = (i0 + c < G) ? cgen[(size_t)(i0 + c) * stride + o] : 0.0f;
+  }
+  __syncthreads();
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  if (j0 + ty >= R || i0 + tx >= G) return;
+  const float* y = sref + ty * stride;      // reference
+  const float* x = sgen + tx * stride;      // generated (probe)
+  double gsum = 0.0;
+  for (int k = 0; k < m; ++k) {
+    const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
+    const double y0 = y[3 * k], y1 = y[3 * k + 1], y2 = y[3 * k + 2];
+    gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (y0 * y0 + y1 * y1 + y2 * y2);
+  }
+  double best = 1e300, best_mirror = 1e300;
+  for (int p = 0; p < (perms ? P : 1); ++p) {
+    const int32_t* pm = perms ? perms + (size_t)p * m : nullptr;
+    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < m; ++k) {
+      const int kr = pm ? pm[k] : k;
+      const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
+      const double y0 = y[3 * kr], y1 = y[3 * kr + 1], y2 = y[3 * kr + 2];
+      S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
+      S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
+      S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
+    }
+    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+    const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
+                          Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
+                          -Sxx + Syy - Szz, Syz + Szy,
+                          -Sxx - Syy + Szz};
+    double lmax, lmin;
+    ag_lambda_ext4(K, lmax, lmin);
+    const double msd = (gsum - 2.0 * lmax) / m;
+    best = fmin(best, msd);
+    best_mirror = fmin(best_mirror, (gsum + 2.0 * lmin) / m);
+  }
+  const size_t at = (size_t)(j0 + ty) * G + i0 + tx;
+  out_proper[at] = (float)sqrt(fmax(best, 0.0));
+  out_mirror[at] = (float)sqrt(fmax(best_mirror, 0.0));
+}
+
+// one wave per conformer, lanes over the stereocentres (strided past 64): the signed volume of each centre's four neighbours in
+// fp64, its sign against the target, and the three "some checked centre ..." facts combined across the wave by ballot.
+// A quad that names an atom outside [0, n) counts as a flat centre (volume 0) and reads nothing.
+__global__ void __launch_bounds__(64) k_chiral_verdict(const float* __restrict__ pos, const int32_t* __restrict__ quads,
+                                                       const int8_t* __restrict__ target, int n, int C, float* __restrict__ vol,
+                                                       int32_t* __restrict__ verdict) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  bool match = false, inverted = false, flat = false;
+  for (int c = lane; c < C; c += 64) {
+    const int a = quads[4 * c], b = quads[4 * c + 1], d = quads[4 * c + 2], e = quads[4 * c + 3];
+    double v = 0.0;
+    if ((unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n && (unsigned)d < (unsigned)n && (unsigned)e < (unsigned)n) {
+      const double ax = p[3 * a], ay = p[3 * a + 1], az = p[3 * a + 2];
+      const double ux = p[3 * b] - ax, uy = p[3 * b + 1] - ay, uz = p[3 * b + 2] - az;
+      const double vx = p[3 * d] - ax, vy = p[3 * d + 1] - ay, vz = p[3 * d + 2] - az;
+      const double wx = p[3 * e] - ax, wy = p[3 * e + 1] - ay, wz = p[3 * e + 2] - az;
+      v = ux * (vy * wz - vz * wy) + uy * (vz * wx - vx * wz) + uz * (vx * wy - vy * wx);
+    }
+    if (vol) vol[(size_t)g * C + c] = (float)v;
+    const int parity = (v > 0.0 && v <= 1.79769313486231570e308) ? 1 : ((v < 0.0 && v >= -1.79769313486231570e308) ? -1 : 0);
+    const int want = target[c];
+    if (want != 0) {
+      flat |= parity == 0;
+      match |= parity != 0 && parity == (want > 0 ? 1 : -1);
+      inverted |= parity != 0 && parity != (want > 0 ? 1 : -1);
+    }
+  }
+  const bool any_match = __ballot(match) != 0, any_inverted = __ballot(inverted) != 0, any_flat = __ballot(flat) != 0;
+  if (lane == 0) verdict[g] = (any_flat || (any_match && any_inverted)) ? 0 : (any_inverted ? -1 : 1);
+}
+
+// one wave per flagged conformer, reduced as in k_center_selected: the centroid of ALL n atoms in fp64, then every coordinate
+// inverted through it in place (each coordinate is read and written by the same lane); unflagged conformers are not touched
+__global__ void __launch_bounds__(64) k_mirror_conformers(float* __restrict__ pos, const int32_t* __restrict__ flags, int n) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  if (flags[g] == 0) return;                  // (wave-uniform)
+  float* p = pos + (size_t)g * n * 3;
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int a = lane; a < n; a += 64) { sx += p[3 * a]; sy += p[3 * a + 1]; sz += p[3 * a + 2]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+  const double cx2 = 2.0 * (sx / n), cy2 = 2.0 * (sy / n), cz2 = 2.0 * (sz / n);
+  for (int a = lane; a < n; a += 64) {
+    p[3 * a] = (float)(cx2 - (double)p[3 * a]);
+    p[3 * a + 1] = (float)(cy2 - (double)p[3 * a + 1]);
+    p[3 * a + 2] = (float)(cz2 - (double)p[3 * a + 2]);
+  }
+}
+
 }  // namespace
 
 extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
@@ -489,6 +635,49 @@ extern "C" int agdiff_align_conformers(const float* pos, const int32_t* atom_idx
   if (!pos || !atom_idx || !target || !out || G < 0 || n <= 0 || m <= 0 || m > n) return AGDIFF_ERR_ARG;
   if (G == 0) return AGDIFF_OK;
   k_align_conformers<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, atom_idx, target, n, m, out, rmsd);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_rmsd_matrix_hands(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
+                                        int32_t R, int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out_proper,
+                                        float* out_mirror, void* stream) {
+  if (!pos_ref || !pos_gen || !atom_idx || !scratch || !out_proper || !out_mirror || out_proper == out_mirror || R < 0 || G < 0 ||
+      n <= 0 || m <= 0 || m > n || (perms && P <= 0))
+    return AGDIFF_ERR_ARG;
+  if (m > AGDIFF_RMSD_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
+  if (R == 0 || G == 0) return AGDIFF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  float* cref = scratch;
+  float* cgen = scratch + (size_t)R * (3 * m + 1);
+  k_center_selected<<<dim3((unsigned)R), dim3(64), 0, st>>>(pos_ref, atom_idx, n, m, cref);
+  AG_CHECK_LAUNCH();
+  k_center_selected<<<dim3((unsigned)G), dim3(64), 0, st>>>(pos_gen, atom_idx, n, m, cgen);
+  AG_CHECK_LAUNCH();
+  const size_t smem = (size_t)2 * 16 * (3 * m + 1) * sizeof(float);
+  static std::atomic<uint64_t> attr_done{0};
+  if (smem > 48 * 1024 &&
+      !ag_allow_big_lds(attr_done, (size_t)2 * 16 * (3 * AGDIFF_RMSD_MAX_ATOMS + 1) * sizeof(float), k_rmsd_matrix_hands))
+    return AGDIFF_ERR_LAUNCH;
+  k_rmsd_matrix_hands<<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem, st>>>(cref, cgen, perms, R, G, m, P,
+                                                                                                          out_proper, out_mirror);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_chiral_verdict(const float* pos, const int32_t* quads, const int8_t* target, int32_t G, int32_t n, int32_t C,
+                                     float* vol, int32_t* verdict, void* stream) {
+  if (!pos || !verdict || G < 0 || n <= 0 || C < 0 || (C > 0 && (!quads || !target))) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_chiral_verdict<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, quads, target, n, C, vol, verdict);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_mirror_conformers(float* pos, const int32_t* flags, int32_t G, int32_t n, void* stream) {
+  if (!pos || !flags || G < 0 || n <= 0) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_mirror_conformers<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, flags, n);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

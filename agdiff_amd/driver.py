@@ -11,7 +11,8 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 (bond graph; already extended to order 3 like `AddHigherOrderEdges` does unless --extend-order),
 `num_refs_i` scalar, `name_i` string.  Output: `samples_<first>_<last>.npz` per batch (named by the molecule
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
---save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T) and the merged `samples_all.npz`, written by rank 0 after a barrier.
+--save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T; + `hand_<i>` [num_samples] with --fix-handedness, which needs
+`stereo_<i>` in the test set) and the merged `samples_all.npz`, written by rank 0 after a barrier.
 
 `--noise counter` draws every conformer's pos_init and noise from the counter-based generator under `--seed` and the conformer's
 stream id (`stream_id`): the same numbers whatever --max-atoms, the packing, a --resume or the number of ranks.
@@ -37,7 +38,8 @@ def num_confs(spec):
 
 
 def save_testset(path, molecules):
-    """molecules: list of dicts with atom_type, edge_index, edge_type, num_refs, name."""
+    """molecules: list of dicts with atom_type, edge_index, edge_type, num_refs, name; optionally stereo (int8 [n]: the target
+    parity at the stereocentres, 0 elsewhere -- agdiff_amd.stereo), saved as `stereo_<i>` when present."""
     out = {"count": np.int64(len(molecules))}
     for i, m in enumerate(molecules):
         out["atom_type_%d" % i] = np.asarray(m["atom_type"], dtype=np.int64)
@@ -45,6 +47,8 @@ def save_testset(path, molecules):
         out["edge_type_%d" % i] = np.asarray(m["edge_type"], dtype=np.int64)
         out["num_refs_%d" % i] = np.int64(m.get("num_refs", 1))
         out["name_%d" % i] = np.str_(m.get("name", "mol%d" % i))
+        if m.get("stereo") is not None:
+            out["stereo_%d" % i] = np.asarray(m["stereo"], dtype=np.int8)
     np.savez_compressed(path, **out)
 
 
@@ -55,6 +59,8 @@ def load_testset(path):
         mols.append(dict(atom_type=z["atom_type_%d" % i], edge_index=z["edge_index_%d" % i],
                          edge_type=z["edge_type_%d" % i], num_refs=int(z["num_refs_%d" % i]),
                          name=str(z["name_%d" % i]), index=i))
+        if "stereo_%d" % i in z.files:
+            mols[-1]["stereo"] = z["stereo_%d" % i]
     return mols
 
 
@@ -404,7 +410,8 @@ def merge_outputs(out_dir):
 
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
-            rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None):
+            rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
+            fix_handedness=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -413,11 +420,21 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     keeps at T, indices into `pos_gen_<i>` -- and `cluster_<i>` int32 [G], the kept conformer each one belongs to
     (agdiff_amd.ensemble.prune_conformers on the GPU, symmetry-aware through the molecule's bonds; at most
     AGDIFF_PRUNE_MAX_CONFS conformers per molecule).  `pos_gen_<i>` holds all conformers either way.  One molecule at a time, after
-    the batch's retries have settled, by the rank that writes the batch's file: a few launches next to seconds of sampling."""
+    the batch's retries have settled, by the rank that writes the batch's file: a few launches next to seconds of sampling.
+    fix_handedness=True: the sampler cannot tell a molecule from its mirror image, so every conformer's stereocentres are read
+    against the molecule's `stereo` tags (load_testset: `stereo_<i>`; a molecule without them is an error) and the mirror images
+    are inverted through their centroid (agdiff_amd.stereo.fix_handedness on the GPU) -- before the prune, which then compares
+    like with like.  `pos_gen_<i>` holds the mirrored conformers, `hand_<i>` int8 [G] the verdict before the fix: -1 was mirrored,
+    0 (a diastereomer or a flat centre) is left as sampled, +1 was right."""
     if noise not in ("default", "counter"):
         raise ValueError("noise must be 'default' or 'counter'")
     if prune_rms is not None and not float(prune_rms) >= 0.0:
         raise ValueError("prune_rms must be >= 0 (an RMSD threshold in Angstrom) or None")
+    if fix_handedness:
+        missing = [m["name"] for m in mols if m.get("stereo") is None]
+        if missing:
+            raise ValueError("fix_handedness needs `stereo_<i>` in the test set (python -m agdiff_amd.stereo adds it); missing for "
+                             "%d molecules: %s" % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
     counter_seed = int(seed) if noise == "counter" else None
     import torch.distributed as dist
     os.makedirs(out_dir, exist_ok=True)
@@ -475,7 +492,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     fut = submit(mine[0], first=True) if mine else None
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world, counter_seed, prune_rms)
+                                world, counter_seed, prune_rms, fix_handedness)
     finally:
         if worker is not None:
             worker.close()
@@ -484,8 +501,9 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None, prune_rms=None):
+                     counter_seed=None, prune_rms=None, fix_handedness=False):
     import torch.distributed as dist
+    mirrored = undecided = 0
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
         # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until here,
@@ -522,6 +540,16 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 continue
             out["pos_gen_%d" % m["index"]] = pos[off:off + n * g].numpy().reshape(g, n, 3)
             out["name_%d" % m["index"]] = np.str_(m["name"])
+            if fix_handedness:
+                import torch
+                from .stereo import fix_handedness as fix
+                on_gpu = torch.from_numpy(np.ascontiguousarray(out["pos_gen_%d" % m["index"]], dtype=np.float32)).to(device)
+                hand = fix(dict(atom_type=m["atom_type"], edge_index=m["edge_index"], edge_type=m["edge_type"], stereo=m["stereo"]),
+                           on_gpu).cpu().numpy().astype(np.int8)
+                out["pos_gen_%d" % m["index"]] = on_gpu.cpu().numpy()
+                out["hand_%d" % m["index"]] = hand
+                mirrored += int((hand < 0).sum())
+                undecided += int((hand == 0).sum())
             if prune_rms is not None:
                 from .ensemble import prune_conformers
                 res = prune_conformers(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
@@ -533,6 +561,9 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
         _save_npz_atomic(_batch_path(out_dir, bmols), out)
         log("rank %d: batch %d/%d (%d of %d molecules, %d conformers) saved" % (rank, bidx + 1, len(batches),
                                                                                int(ok.sum()), len(bmols), packed["num_graphs"]))
+    if fix_handedness and (rank == 0 or mirrored or undecided):       # (the ranks that wrote files)
+        log("rank %d: %d conformers were mirror images and were inverted; %d match neither hand (verdict 0) and stay as sampled"
+            % (rank, mirrored, undecided))
     if world > 1:
         dist.barrier()                       # every rank's batch files are on disk
     if SAMPLE_STATS["range_trips"]:
@@ -571,6 +602,10 @@ def main(argv=None):
     ap.add_argument("--prune-rms", type=float, default=None,
                     help="also save, per molecule, which conformers RDKit's pruneRmsThresh rule keeps at this heavy-atom RMSD "
                          "(Angstrom; symmetry-aware): kept_<i> and cluster_<i> next to pos_gen_<i>, which still holds them all")
+    ap.add_argument("--fix-handedness", action="store_true",
+                    help="invert the conformers that came out as the mirror image (the sampler cannot tell the hands apart): needs "
+                         "stereo_<i> in the test set (python -m agdiff_amd.stereo); pos_gen_<i> then holds the mirrored conformers and "
+                         "hand_<i> the verdict before the fix (-1 mirrored, 0 neither hand: left as sampled, +1 right)")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
     ap.add_argument("--dist-mode", default="shard", choices=["shard", "batches"],
                     help="with several ranks: 'shard' = every packed batch (max-atoms x world atoms) is split into "
@@ -613,7 +648,7 @@ def main(argv=None):
               clip=args.clip)
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
-            seed=args.seed, prune_rms=args.prune_rms)
+            seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness)
     if own_pg:
         dist.destroy_process_group()
 

@@ -12,7 +12,8 @@ Items are the plain dicts of agdiff_amd.evaluation: atom_type [n], pos_gen [G*n,
 heavy-atom self-matches (GetBestRMS), without them the identity mapping only.  Hydrogens take no part in the RMSD and ride
 along in the alignment.
 
-    python -m agdiff_amd.ensemble --samples out/samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
+    python -m agdiff_amd.ensemble --samples out/samples_all.npz --testset test.npz --prune-rms 0.5 [--align] [--fix-handedness]
+                                  --out pruned.npz
 """
 import numpy as np
 
@@ -124,7 +125,7 @@ def align_conformers(pos, atom_type, target, device="cuda"):
     return _align(p, torch.from_numpy(heavy).to(device), t[0])
 
 
-def prune_conformers(item, threshold, align=True, device="cuda"):
+def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False):
     """RDKit's pruneRmsThresh rule over the item's generated conformers, in their order: a conformer is kept iff its best RMSD
     to every conformer kept before it is above `threshold`; a dropped one belongs to the first kept conformer within the
     threshold.  Returns a dict of tensors on `device`:
@@ -133,6 +134,11 @@ def prune_conformers(item, threshold, align=True, device="cuda"):
         count  int32 [K]  size of each kept conformer's cluster (itself included)
         pos    [K, n, 3]  the kept conformers; with align=True superposed on the first of them over the heavy atoms (that one
                           is returned as it is, bit for bit)
+    fix_handedness=True (the item carries `stereo` and its bonds): the conformers that are the mirror image of the tagged molecule are
+    inverted through their centroid first (agdiff_amd.stereo.fix_handedness), so that the prune does not spend the kept set on two
+    families that can never superpose; the dict also gets
+        hand   int32 [G]  the verdict before the fix: -1 was mirrored, 0 matches neither hand and is left as it is, +1 was right
+    and `pos` holds the mirrored coordinates.
     At most AGDIFF_PRUNE_MAX_CONFS conformers."""
     import torch
     t = _check_threshold(threshold)
@@ -143,6 +149,11 @@ def prune_conformers(item, threshold, align=True, device="cuda"):
         raise ValueError("no conformers to prune")
     if G > MAX_CONFS:
         raise _lib.AgdiffLimitError("prune_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
+    hand = None
+    if fix_handedness:
+        from .stereo import fix_handedness as fix
+        gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
+        hand = fix(item, gen)
     gen, idx, _, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
     keep, leader, count, _ = leader_prune(bits, G)
     kept = torch.nonzero(keep, as_tuple=False).reshape(-1)
@@ -151,14 +162,18 @@ def prune_conformers(item, threshold, align=True, device="cuda"):
         first = pos[0].clone()
         pos, _ = _align(pos, idx, first)
         pos[0] = first
-    return {"kept": kept.to(torch.int32), "leader": leader, "count": count[kept], "pos": pos}
+    res = {"kept": kept.to(torch.int32), "leader": leader, "count": count[kept], "pos": pos}
+    if hand is not None:
+        res["hand"] = hand
+    return res
 
 
 def main(argv=None):
     """python -m agdiff_amd.ensemble --samples samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
     Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
     symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
-    (+ `name_<i>`)."""
+    (+ `name_<i>`).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
+    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix."""
     import argparse
     from .driver import load_testset
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -166,6 +181,7 @@ def main(argv=None):
     ap.add_argument("--testset", required=True)
     ap.add_argument("--prune-rms", type=float, required=True, help="RMSD threshold in Angstrom (heavy atoms)")
     ap.add_argument("--align", action="store_true", help="superpose the kept conformers on the first of them")
+    ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -178,12 +194,18 @@ def main(argv=None):
             continue
         item = {"atom_type": mol["atom_type"], "pos_gen": zs["pos_gen_%d" % i], "edge_index": mol["edge_index"],
                 "edge_type": mol["edge_type"]}
-        res = prune_conformers(item, args.prune_rms, align=args.align, device=args.device)
+        if args.fix_handedness:
+            if mol.get("stereo") is None:
+                raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
+            item["stereo"] = mol["stereo"]
+        res = prune_conformers(item, args.prune_rms, align=args.align, device=args.device, fix_handedness=args.fix_handedness)
         out["pos_%d" % i] = res["pos"].cpu().numpy()
         out["kept_%d" % i] = res["kept"].cpu().numpy()
         out["cluster_%d" % i] = res["leader"].cpu().numpy()
         out["count_%d" % i] = res["count"].cpu().numpy()
         out["name_%d" % i] = np.str_(mol["name"])
+        if "hand" in res:
+            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
         total += int(res["leader"].shape[0])
         left += int(res["kept"].shape[0])
     np.savez_compressed(args.out, **out)

@@ -155,8 +155,11 @@ def selection_of(data):
     return at, heavy, pa
 
 
-def get_rmsd_confusion_matrix(data, useFF=False, device="cuda"):
-    """covmat.py:16-35.  Returns a float32 torch tensor [num_ref, num_gen] on `device`."""
+def get_rmsd_confusion_matrix(data, useFF=False, device="cuda", hands=False):
+    """covmat.py:16-35.  Returns a float32 torch tensor [num_ref, num_gen] on `device`.
+    hands=True: (proper, mirror) -- `proper` is that matrix bit for bit, `mirror` the same quantity for every generated conformer's
+    mirror image (agdiff_rmsd_matrix_hands: one diagonalisation gives both).  The sampler draws either hand with equal
+    probability; min(proper, mirror) is what the run would score were handedness free."""
     import torch
     if useFF:
         raise NotImplementedError("MMFF relaxation needs rdkit (covmat.py:27-29); not available here")
@@ -173,6 +176,13 @@ def get_rmsd_confusion_matrix(data, useFF=False, device="cuda"):
     R, G = ref.shape[0], gen.shape[0]
     out = torch.empty((R, G), dtype=torch.float32, device=device)
     scratch = torch.empty((R + G) * (3 * m + 1), dtype=torch.float32, device=device)
+    if hands:
+        mirror = torch.empty((R, G), dtype=torch.float32, device=device)
+        with torch.cuda.device(out.device):
+            _lib.check(lib.agdiff_rmsd_matrix_hands(_lib.ptr(ref), _lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), R, G, n, m, P,
+                                                    _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(mirror), _lib.stream_ptr()),
+                       "agdiff_rmsd_matrix_hands")
+        return out, mirror
     with torch.cuda.device(out.device):
         _lib.check(lib.agdiff_rmsd_matrix(_lib.ptr(ref), _lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), R, G, n, m, P,
                                           _lib.ptr(scratch), _lib.ptr(out), _lib.stream_ptr()), "agdiff_rmsd_matrix")
@@ -228,10 +238,14 @@ def print_covmat_results(results, print_fn=print):
 
 
 class CovMatEvaluator(object):
-    """covmat.py:77-165.  `num_workers` is accepted and ignored: the confusion matrices come from the GPU."""
+    """covmat.py:77-165.  `num_workers` is accepted and ignored: the confusion matrices come from the GPU.
+    either_hand=True: the results also carry `either_hand`, the same five fields computed from min(proper, mirror) -- every
+    generated conformer scored as the better of itself and its mirror image (get_rmsd_confusion_matrix(hands=True)) -- and
+    `mirror_nearest`, per molecule the fraction of generated conformers whose nearest reference is reached through the mirror
+    image.  No stereo tags are needed: it shows what handedness costs a run.  `confusion_fn` must then return (proper, mirror)."""
 
     def __init__(self, num_workers=8, use_force_field=False, thresholds=np.arange(0.05, 3.05, 0.05), ratio=2,
-                 filter_disconnected=True, print_fn=print, confusion_fn=None):
+                 filter_disconnected=True, print_fn=print, confusion_fn=None, either_hand=False):
         if use_force_field:
             raise NotImplementedError("MMFF relaxation needs rdkit; not available here")
         self.num_workers = num_workers
@@ -242,6 +256,7 @@ class CovMatEvaluator(object):
         self.print_fn = print_fn
         # hook for callers that already hold the matrices (and for CPU tests of the filtering / reductions)
         self.confusion_fn = confusion_fn
+        self.either_hand = either_hand
 
     def __call__(self, packed_data_list, start_idx=0):
         filtered = []
@@ -260,8 +275,26 @@ class CovMatEvaluator(object):
         filtered = filtered[start_idx:]
         self.print_fn("Filtered: %d / %d" % (len(filtered), len(packed_data_list)))
         covr_scores, matr_scores, covp_scores, matp_scores = [], [], [], []
+        either, mirror_nearest = ([], [], [], []), []
         for data in filtered:
-            if self.confusion_fn is not None:
+            if self.either_hand:
+                if self.confusion_fn is not None:
+                    cm, cmm = (np.asarray(c) for c in self.confusion_fn(data))
+                    ref_min, gen_min, mir_min = cm.min(-1), cm.min(0), cmm.min(0)
+                    both = np.minimum(cm, cmm)
+                    e_ref_min, e_gen_min = both.min(-1), both.min(0)
+                else:
+                    import torch
+                    proper, mirror = get_rmsd_confusion_matrix(data, hands=True)
+                    rmin, gmin = matrix_minima(proper)
+                    _, mmin = matrix_minima(mirror)
+                    ermin, egmin = matrix_minima(torch.minimum(proper, mirror))
+                    ref_min, gen_min, mir_min = rmin.cpu().numpy(), gmin.cpu().numpy(), mmin.cpu().numpy()
+                    e_ref_min, e_gen_min = ermin.cpu().numpy(), egmin.cpu().numpy()
+                for acc, v in zip(either, scores_from_minima(e_ref_min, e_gen_min, self.thresholds)):
+                    acc.append(v)
+                mirror_nearest.append(float((mir_min < gen_min).mean()))
+            elif self.confusion_fn is not None:
                 cm = np.asarray(self.confusion_fn(data))
                 ref_min, gen_min = cm.min(-1), cm.min(0)
             else:
@@ -269,13 +302,18 @@ class CovMatEvaluator(object):
                 ref_min, gen_min = rmin.cpu().numpy(), gmin.cpu().numpy()
             covr, matr, covp, matp = scores_from_minima(ref_min, gen_min, self.thresholds)
             covr_scores.append(covr); matr_scores.append(matr); covp_scores.append(covp); matp_scores.append(matp)
-        return Config({
-            "CoverageR": np.vstack(covr_scores) if covr_scores else np.zeros((0, self.thresholds.shape[0])),
-            "MatchingR": np.array(matr_scores),
+        table = lambda covr, matr, covp, matp: {
+            "CoverageR": np.vstack(covr) if covr else np.zeros((0, self.thresholds.shape[0])),
+            "MatchingR": np.array(matr),
             "thresholds": self.thresholds,
-            "CoverageP": np.vstack(covp_scores) if covp_scores else np.zeros((0, self.thresholds.shape[0])),
-            "MatchingP": np.array(matp_scores),
-        })
+            "CoverageP": np.vstack(covp) if covp else np.zeros((0, self.thresholds.shape[0])),
+            "MatchingP": np.array(matp),
+        }
+        res = Config(table(covr_scores, matr_scores, covp_scores, matp_scores))
+        if self.either_hand:
+            res["either_hand"] = Config(table(*either))
+            res["mirror_nearest"] = np.array(mirror_nearest)
+        return res
 
     def close(self):
         pass
@@ -284,12 +322,17 @@ class CovMatEvaluator(object):
 def main(argv=None):
     """python -m agdiff_amd.evaluation --samples samples_all.npz --refs refs.npz
     samples: `pos_gen_<i>` [G, n, 3] (agdiff_amd.driver output); refs: `pos_ref_<i>` [R, n, 3], `atom_type_<i>` [n],
-    optional `smiles_<i>`, `bond_index_<i>` + `bond_type_<i>` (symmetry-aware RMSD) or `perms_<i>` [P, m].  Prints the COV / MAT table of the reference's eval_covmat.py."""
+    optional `smiles_<i>`, `bond_index_<i>` + `bond_type_<i>` (symmetry-aware RMSD) or `perms_<i>` [P, m].  Prints the COV / MAT table of the reference's eval_covmat.py.
+    --either-hand: then a second table, labelled "either hand", from min(proper, mirror) -- every generated conformer scored as the
+    better of itself and its mirror image -- and the fraction of generated conformers whose nearest reference is reached through
+    the mirror image."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--samples", required=True)
     ap.add_argument("--refs", required=True)
     ap.add_argument("--ratio", type=int, default=2)
+    ap.add_argument("--either-hand", action="store_true",
+                    help="also print the table computed from min(proper, mirror): what the run would score were handedness free")
     args = ap.parse_args(argv)
     zs, zr = np.load(args.samples), np.load(args.refs)
     items = []
@@ -308,8 +351,13 @@ def main(argv=None):
         if "pos_gen_" + i in zs.files:
             d["pos_gen"] = zs["pos_gen_" + i]
         items.append(d)
-    res = CovMatEvaluator(ratio=args.ratio)(items)
+    res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand)(items)
     print_covmat_results(res)
+    if args.either_hand:
+        print("\neither hand (every generated conformer scored as the better of itself and its mirror image):")
+        print_covmat_results(res.either_hand)
+        print("nearest reference reached through the mirror image: %.4f of the generated conformers (mean over %d molecules)"
+              % (float(np.mean(res.mirror_nearest)) if len(res.mirror_nearest) else float("nan"), len(res.mirror_nearest)))
     return res
 
 

@@ -779,6 +779,37 @@ int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* keep, int32_t*
 int agdiff_align_conformers(const float* pos, const int32_t* atom_idx, const float* target, int32_t G, int32_t n, int32_t m,
                             float* out, float* rmsd, void* stream);
 
+/* ---- handedness ------------------------------------------------------------------------------------------------------
+ * The score network sees atom types, bonds and distances only, so the sampler draws a molecule and its mirror image with
+ * equal probability.  Three calls, no atomics, deterministic bit for bit.
+ *
+ * agdiff_rmsd_matrix_hands: agdiff_rmsd_matrix with a second matrix.  out_proper [R][G] is bit for bit what agdiff_rmsd_matrix
+ * writes; out_mirror [R][G] is the same quantity for the generated conformer inverted through its centroid (its mirror
+ * image), minimised over the same mappings: sqrt(max(0, min_p (|X|^2 + |Y|^2 + 2 lambda_min(K_p)) / m)).  K is linear in the
+ * cross-covariance S and the inversion turns S into -S, so both values come from one diagonalisation per (pair, mapping).
+ * Arguments as for agdiff_rmsd_matrix; out_proper and out_mirror must not overlap. */
+int agdiff_rmsd_matrix_hands(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
+                             int32_t R, int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out_proper,
+                             float* out_mirror, void* stream);
+
+/* Parity of tetrahedral stereocentres, per conformer.
+ *   pos [G][n][3]
+ *   quads [C][4] int32     the four bonded neighbours (a, b, c, d) of each centre, in ascending atom index
+ *   target [C] int8        +1 / -1: the parity the centre should have; 0: do not check   (quads / target may be null when C = 0)
+ *   vol [G][C] or null     (p_b - p_a) . ((p_c - p_a) x (p_d - p_a)) in fp64 from the fp32 positions, stored as fp32
+ *   verdict [G] int32      +1: every checked centre has its target parity (also: C = 0, nothing checked)
+ *                          -1: every checked centre is inverted -- the conformer is the mirror image
+ *                           0: the checked centres disagree, or one of them has parity 0: reflection cannot fix it
+ * The parity of a centre is the sign of the fp64 volume, 0 when that is zero or not finite.  A quad naming an atom outside
+ * [0, n) counts as volume 0 and reads nothing. */
+int agdiff_chiral_verdict(const float* pos, const int32_t* quads, const int8_t* target, int32_t G, int32_t n, int32_t C,
+                          float* vol, int32_t* verdict, void* stream);
+
+/* Mirror images in place: for every conformer g with flags[g] != 0 (int32 [G]), p <- (float)(2 c - (double)p) with c the fp64
+ * centroid of ALL n atoms.  Inversion through the centroid keeps every distance and the centroid.  Conformers with
+ * flags[g] == 0 are neither read nor written.  pos [G][n][3]. */
+int agdiff_mirror_conformers(float* pos, const int32_t* flags, int32_t G, int32_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
