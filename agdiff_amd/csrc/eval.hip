@@ -566,6 +566,116 @@ __global__ void __launch_bounds__(64) k_mirror_conformers(float* __restrict__ po
   }
 }
 
+// ---- torsion fingerprint deviation: RMSD grows with the molecule and mixes ring breathing with rotamer changes; the dihedrals of
+// the rotatable bonds are what defines a conformer, so the matrix, the threshold bits and the mirror value exist over them too ----
+
+// one wave per conformer, lanes over the columns (strided past 64), shaped like k_chiral_verdict: the dihedral of every quad
+// (a, u, v, b) in fp64 from the fp32 positions, theta = atan2(|b2| b1 . n2, n1 . n2).  NaN for a degenerate quad (a zero normal),
+// an input that is not finite, or a quad that names an atom outside [0, n), which reads nothing.
+__global__ void __launch_bounds__(64) k_torsion_angles(const float* __restrict__ pos, const int32_t* __restrict__ quads, int n, int Q,
+                                                       float* __restrict__ out) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  for (int c = lane; c < Q; c += 64) {
+    const int a = quads[4 * c], u = quads[4 * c + 1], v = quads[4 * c + 2], b = quads[4 * c + 3];
+    double theta = (double)NAN;
+    if ((unsigned)a < (unsigned)n && (unsigned)u < (unsigned)n && (unsigned)v < (unsigned)n && (unsigned)b < (unsigned)n) {
+      const double ax = p[3 * a], ay = p[3 * a + 1], az = p[3 * a + 2];
+      const double ux = p[3 * u], uy = p[3 * u + 1], uz = p[3 * u + 2];
+      const double vx = p[3 * v], vy = p[3 * v + 1], vz = p[3 * v + 2];
+      const double bx = p[3 * b], by = p[3 * b + 1], bz = p[3 * b + 2];
+      const double b1x = ux - ax, b1y = uy - ay, b1z = uz - az;
+      const double b2x = vx - ux, b2y = vy - uy, b2z = vz - uz;
+      const double b3x = bx - vx, b3y = by - vy, b3z = bz - vz;
+      const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
+      const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
+      const double n1sq = n1x * n1x + n1y * n1y + n1z * n1z, n2sq = n2x * n2x + n2y * n2y + n2z * n2z;
+      // (fp32 inputs: every difference and product above is finite in fp64 iff the twelve coordinates are; an Inf or NaN among
+      // them reaches n1sq or n2sq or both of y and x below)
+      const double y = sqrt(b2x * b2x + b2y * b2y + b2z * b2z) * (b1x * n2x + b1y * n2y + b1z * n2z);
+      const double x = n1x * n2x + n1y * n2y + n1z * n2z;
+      const double lim = 1.79769313486231570e308;
+      const bool finite = fabs(ax) <= lim && fabs(ay) <= lim && fabs(az) <= lim && fabs(ux) <= lim && fabs(uy) <= lim && fabs(uz) <= lim &&
+                          fabs(vx) <= lim && fabs(vy) <= lim && fabs(vz) <= lim && fabs(bx) <= lim && fabs(by) <= lim && fabs(bz) <= lim;
+      if (finite && n1sq > 0.0 && n2sq > 0.0) theta = atan2(y, x);
+    }
+    out[(size_t)g * Q + c] = (float)theta;
+  }
+}
+
+// circular difference of two angles in radians; pi when either is NaN (a broken torsion never makes two conformers look alike)
+__device__ __forceinline__ double ag_circ_diff(double d) {     // d = |alpha - beta| (or |alpha + beta| against the mirror image)
+  const double r = fmin(d, 6.283185307179586476925 - d);
+  return d != d ? 3.141592653589793238462 : r;
+}
+
+// 16 x 16 pairs per workgroup as in k_rmsd_matrix: thread (ty, tx) = (row conformer j0 + ty of ang_x, column conformer i0 + tx of
+// ang_y).  The 16 + 16 angle rows sit in LDS at an odd pitch, so the 16 threads of a tile row, which read one column of 16
+// different y rows, hit 16 different banks (the x row is a broadcast).  One thread walks the P mappings of its pair:
+//   S_p(x -> y) = sum_t w_t delta(x[tmap[0][t]], y[tmap[p][t]]) / (pi sum_t w_t),  value = min_p min(S_p(x -> y), S_p(y -> x)),
+// the mirror value the same with every y angle negated.  Both sums are accumulated in the same order with a delta that is
+// symmetric in its arguments, so thread (x, y) and thread (y, x) of a self matrix compute each other's pair of sums bit for bit.
+// bits: the layout of k_rmsd_self, R rows; the wave's ballot holds four tile rows of 16 flags, the lane with tx == 0 stores its
+// row's piece, and the tiles of the last tile column zero the pad pieces of their rows.
+__global__ void __launch_bounds__(256) k_tfd_matrix(const float* __restrict__ ang_x, const float* __restrict__ ang_y,
+                                                    const int32_t* __restrict__ tmap, const float* __restrict__ w, int R, int G, int Q,
+                                                    int T, int P, float thresh, float* __restrict__ out, float* __restrict__ out_mirror,
+                                                    uint16_t* __restrict__ bits, int pitch) {
+  const int lp = Q | 1;                             // LDS pitch in floats: odd
+  float* sx = ag_eval_smem;
+  float* sy = ag_eval_smem + 16 * lp;
+  const int j0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
+  for (int t = threadIdx.x; t < 16 * Q; t += 256) {
+    const int c = t / Q, o = t % Q;
+    sx[c * lp + o] = (j0 + c < R) ? ang_x[(size_t)(j0 + c) * Q + o] : 0.0f;
+    sy[c * lp + o] = (i0 + c < G) ? ang_y[(size_t)(i0 + c) * Q + o] : 0.0f;
+  }
+  __syncthreads();
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  const bool valid = j0 + ty < R && i0 + tx < G;
+  float v = 0.0f, vm = 0.0f;
+  if (valid && T > 0) {
+    const float* x = sx + ty * lp;
+    const float* y = sy + tx * lp;
+    double wsum = 0.0;
+    for (int t = 0; t < T; ++t) wsum += w ? (double)w[t] : 1.0;
+    double best = 1e300, best_mirror = 1e300;
+    for (int p = 0; p < P; ++p) {
+      const int32_t* mp = tmap + (size_t)p * T;
+      double sxy = 0.0, syx = 0.0, mxy = 0.0, myx = 0.0;
+      for (int t = 0; t < T; ++t) {
+        const int c0 = tmap[t], cp = mp[t];
+        const double wt = w ? (double)w[t] : 1.0;
+        const double x0 = x[c0], yp = y[cp], y0 = y[c0], xp = x[cp];
+        sxy += wt * ag_circ_diff(fabs(x0 - yp));
+        syx += wt * ag_circ_diff(fabs(y0 - xp));
+        mxy += wt * ag_circ_diff(fabs(x0 + yp));
+        myx += wt * ag_circ_diff(fabs(y0 + xp));
+      }
+      best = fmin(best, fmin(sxy, syx));
+      best_mirror = fmin(best_mirror, fmin(mxy, myx));
+    }
+    const double norm = 3.141592653589793238462 * wsum;
+    v = (float)(best / norm);
+    vm = (float)(best_mirror / norm);
+  }
+  if (valid) {
+    const size_t at = (size_t)(j0 + ty) * G + i0 + tx;
+    if (out) out[at] = v;
+    if (out_mirror) out_mirror[at] = vm;
+  }
+  if (bits) {                                       // (every lane of the wave arrives here)
+    // the threshold is taken on the fp32 value as stored, so that bits == (out <= thresh) exactly
+    const unsigned long long flags = __ballot(valid && v <= thresh);
+    const int pieces = pitch >> 1, tiles_g = (G + 15) / 16;
+    if (j0 + ty < R) {
+      uint16_t* row = bits + (size_t)(j0 + ty) * pieces;
+      if (tx == 0) row[blockIdx.x] = (uint16_t)(flags >> (16 * (ty & 3)));
+      if ((int)blockIdx.x == tiles_g - 1 && tx >= 1 && tiles_g - 1 + tx < pieces) row[tiles_g - 1 + tx] = 0;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
@@ -678,6 +788,33 @@ extern "C" int agdiff_mirror_conformers(float* pos, const int32_t* flags, int32_
   if (!pos || !flags || G < 0 || n <= 0) return AGDIFF_ERR_ARG;
   if (G == 0) return AGDIFF_OK;
   k_mirror_conformers<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, flags, n);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_torsion_angles(const float* pos, const int32_t* quads, int32_t G, int32_t n, int32_t Q, float* out, void* stream) {
+  if (!pos || !out || G < 0 || n <= 0 || Q < 0 || (Q > 0 && !quads)) return AGDIFF_ERR_ARG;
+  if (G == 0 || Q == 0) return AGDIFF_OK;
+  k_torsion_angles<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, quads, n, Q, out);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const int32_t* tmap, const float* w, int32_t R, int32_t G,
+                                 int32_t Q, int32_t T, int32_t P, float thresh, float* out, float* out_mirror, uint64_t* bits,
+                                 void* stream) {
+  if (R < 0 || G < 0 || Q < 0 || T < 0 || T > Q || P < 1 || (Q > 0 && (!ang_x || !ang_y)) || (T > 0 && !tmap)) return AGDIFF_ERR_ARG;
+  if ((!out && !out_mirror && !bits) || (out_mirror && out_mirror == out)) return AGDIFF_ERR_ARG;
+  if (bits && (!(thresh >= 0.0f) || ((uintptr_t)bits & 7))) return AGDIFF_ERR_ARG;
+  if (Q > AGDIFF_TFD_MAX_COLUMNS) return AGDIFF_ERR_LIMIT;
+  if (R == 0 || G == 0) return AGDIFF_OK;
+  const auto smem_for = [](int q) { return (size_t)2 * 16 * (q | 1) * sizeof(float); };
+  static std::atomic<uint64_t> attr_done{0};
+  if (smem_for(Q) > 48 * 1024 && !ag_allow_big_lds(attr_done, smem_for(AGDIFF_TFD_MAX_COLUMNS), k_tfd_matrix)) return AGDIFF_ERR_LAUNCH;
+  const int tiles_g = (G + 15) / 16;
+  const int pitch = (tiles_g * 2 + 7) / 8 * 8;
+  k_tfd_matrix<<<dim3((unsigned)tiles_g, (unsigned)((R + 15) / 16)), dim3(256), smem_for(Q), (hipStream_t)stream>>>(
+      ang_x, ang_y, tmap, w, R, G, Q, T, P, thresh, out, out_mirror, (uint16_t*)bits, pitch);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

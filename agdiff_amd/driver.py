@@ -411,7 +411,7 @@ def merge_outputs(out_dir):
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
-            fix_handedness=False):
+            fix_handedness=False, prune_tfd=None):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -421,6 +421,8 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     (agdiff_amd.ensemble.prune_conformers on the GPU, symmetry-aware through the molecule's bonds; at most
     AGDIFF_PRUNE_MAX_CONFS conformers per molecule).  `pos_gen_<i>` holds all conformers either way.  One molecule at a time, after
     the batch's retries have settled, by the rank that writes the batch's file: a few launches next to seconds of sampling.
+    prune_tfd=T (in [0, 1]) instead of prune_rms: the same keys from the same walk over the torsion fingerprint deviation
+    (agdiff_amd.torsions); giving both is a ValueError.
     fix_handedness=True: the sampler cannot tell a molecule from its mirror image, so every conformer's stereocentres are read
     against the molecule's `stereo` tags (load_testset: `stereo_<i>`; a molecule without them is an error) and the mirror images
     are inverted through their centroid (agdiff_amd.stereo.fix_handedness on the GPU) -- before the prune, which then compares
@@ -430,6 +432,10 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
         raise ValueError("noise must be 'default' or 'counter'")
     if prune_rms is not None and not float(prune_rms) >= 0.0:
         raise ValueError("prune_rms must be >= 0 (an RMSD threshold in Angstrom) or None")
+    if prune_tfd is not None and prune_rms is not None:
+        raise ValueError("prune_rms and prune_tfd are two rules for one pair of keys (kept_<i>, cluster_<i>): give one of them")
+    if prune_tfd is not None and not float(prune_tfd) >= 0.0:
+        raise ValueError("prune_tfd must be >= 0 (a torsion fingerprint deviation, in [0, 1]) or None")
     if fix_handedness:
         missing = [m["name"] for m in mols if m.get("stereo") is None]
         if missing:
@@ -492,7 +498,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     fut = submit(mine[0], first=True) if mine else None
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world, counter_seed, prune_rms, fix_handedness)
+                                world, counter_seed, prune_rms, fix_handedness, prune_tfd)
     finally:
         if worker is not None:
             worker.close()
@@ -501,7 +507,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None, prune_rms=None, fix_handedness=False):
+                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None):
     import torch.distributed as dist
     mirrored = undecided = 0
     for pos_in_mine, bidx in enumerate(mine):
@@ -550,10 +556,11 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 out["hand_%d" % m["index"]] = hand
                 mirrored += int((hand < 0).sum())
                 undecided += int((hand == 0).sum())
-            if prune_rms is not None:
+            if prune_rms is not None or prune_tfd is not None:
                 from .ensemble import prune_conformers
                 res = prune_conformers(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
-                                            edge_type=m["edge_type"]), float(prune_rms), align=False, device=device)
+                                            edge_type=m["edge_type"]), float(prune_rms if prune_tfd is None else prune_tfd), align=False,
+                                       device=device, metric="rmsd" if prune_tfd is None else "tfd")
                 out["kept_%d" % m["index"]] = res["kept"].cpu().numpy()
                 out["cluster_%d" % m["index"]] = res["leader"].cpu().numpy()
             if traj is not None:
@@ -602,6 +609,9 @@ def main(argv=None):
     ap.add_argument("--prune-rms", type=float, default=None,
                     help="also save, per molecule, which conformers RDKit's pruneRmsThresh rule keeps at this heavy-atom RMSD "
                          "(Angstrom; symmetry-aware): kept_<i> and cluster_<i> next to pos_gen_<i>, which still holds them all")
+    ap.add_argument("--prune-tfd", type=float, default=None,
+                    help="--prune-rms's keys by the torsion fingerprint deviation (in [0, 1]; agdiff_amd.torsions) instead of the RMSD; "
+                         "not together with --prune-rms")
     ap.add_argument("--fix-handedness", action="store_true",
                     help="invert the conformers that came out as the mirror image (the sampler cannot tell the hands apart): needs "
                          "stereo_<i> in the test set (python -m agdiff_amd.stereo); pos_gen_<i> then holds the mirrored conformers and "
@@ -648,7 +658,7 @@ def main(argv=None):
               clip=args.clip)
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
-            seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness)
+            seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd)
     if own_pg:
         dist.destroy_process_group()
 

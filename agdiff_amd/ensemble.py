@@ -14,6 +14,7 @@ along in the alignment.
 
     python -m agdiff_amd.ensemble --samples out/samples_all.npz --testset test.npz --prune-rms 0.5 [--align] [--fix-handedness]
                                   --out pruned.npz
+    (--prune-tfd 0.2 in --prune-rms's place: the same walk over the torsion fingerprint deviation, agdiff_amd.torsions)
 """
 import numpy as np
 
@@ -125,10 +126,12 @@ def align_conformers(pos, atom_type, target, device="cuda"):
     return _align(p, torch.from_numpy(heavy).to(device), t[0])
 
 
-def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False):
+def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False, metric="rmsd"):
     """RDKit's pruneRmsThresh rule over the item's generated conformers, in their order: a conformer is kept iff its best RMSD
     to every conformer kept before it is above `threshold`; a dropped one belongs to the first kept conformer within the
-    threshold.  Returns a dict of tensors on `device`:
+    threshold.  metric="tfd": the same leader walk with the torsion fingerprint deviation (agdiff_amd.torsions; in [0, 1], the item
+    must carry its bonds) in the RMSD's place; alignment and the handedness fix work as for the RMSD.
+    Returns a dict of tensors on `device`:
         kept   int32 [K]  indices of the kept conformers, ascending
         leader int32 [G]  for every conformer the kept conformer it belongs to (itself when kept)
         count  int32 [K]  size of each kept conformer's cluster (itself included)
@@ -141,6 +144,8 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     and `pos` holds the mirrored coordinates.
     At most AGDIFF_PRUNE_MAX_CONFS conformers."""
     import torch
+    if metric not in ("rmsd", "tfd"):
+        raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
     t = _check_threshold(threshold)
     n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
     gen = _as_conformers(item["pos_gen"], n)
@@ -154,7 +159,12 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
         from .stereo import fix_handedness as fix
         gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
         hand = fix(item, gen)
-    gen, idx, _, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
+    if metric == "tfd":
+        from .torsions import _self_tfd
+        gen, _, bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
+        idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
+    else:
+        gen, idx, _, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
     keep, leader, count, _ = leader_prune(bits, G)
     kept = torch.nonzero(keep, as_tuple=False).reshape(-1)
     pos = gen[kept]
@@ -172,20 +182,24 @@ def main(argv=None):
     """python -m agdiff_amd.ensemble --samples samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
     Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
     symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
-    (+ `name_<i>`).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
+    (+ `name_<i>`).  Exactly one of --prune-rms / --prune-tfd T (the torsion fingerprint deviation, in [0, 1]).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
     python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix."""
     import argparse
     from .driver import load_testset
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", required=True)
     ap.add_argument("--testset", required=True)
-    ap.add_argument("--prune-rms", type=float, required=True, help="RMSD threshold in Angstrom (heavy atoms)")
+    how = ap.add_mutually_exclusive_group(required=True)
+    how.add_argument("--prune-rms", type=float, default=None, help="RMSD threshold in Angstrom (heavy atoms)")
+    how.add_argument("--prune-tfd", type=float, default=None,
+                     help="torsion fingerprint deviation threshold in [0, 1] (agdiff_amd.torsions) instead of an RMSD")
     ap.add_argument("--align", action="store_true", help="superpose the kept conformers on the first of them")
     ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
-    _check_threshold(args.prune_rms)
+    metric, threshold = ("rmsd", args.prune_rms) if args.prune_tfd is None else ("tfd", args.prune_tfd)
+    _check_threshold(threshold)
     zs = np.load(args.samples)
     out, total, left = {}, 0, 0
     for mol in load_testset(args.testset):
@@ -198,7 +212,8 @@ def main(argv=None):
             if mol.get("stereo") is None:
                 raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
             item["stereo"] = mol["stereo"]
-        res = prune_conformers(item, args.prune_rms, align=args.align, device=args.device, fix_handedness=args.fix_handedness)
+        res = prune_conformers(item, threshold, align=args.align, device=args.device, fix_handedness=args.fix_handedness,
+                               metric=metric)
         out["pos_%d" % i] = res["pos"].cpu().numpy()
         out["kept_%d" % i] = res["kept"].cpu().numpy()
         out["cluster_%d" % i] = res["leader"].cpu().numpy()
@@ -209,7 +224,10 @@ def main(argv=None):
         total += int(res["leader"].shape[0])
         left += int(res["kept"].shape[0])
     np.savez_compressed(args.out, **out)
-    print("pruned %d conformers to %d at %.3f A" % (total, left, args.prune_rms))
+    if metric == "tfd":
+        print("pruned %d conformers to %d at TFD %.3f" % (total, left, threshold))
+    else:
+        print("pruned %d conformers to %d at %.3f A" % (total, left, args.prune_rms))
     return out
 
 

@@ -189,6 +189,18 @@ def get_rmsd_confusion_matrix(data, useFF=False, device="cuda", hands=False):
     return out
 
 
+def get_tfd_confusion_matrix(data, hands=False, device="cuda", weights=None):
+    """The confusion matrix of get_rmsd_confusion_matrix with the torsion fingerprint deviation (agdiff_amd.torsions: the mean
+    circular difference of the rotatable bonds' dihedrals, in [0, 1], minimised over the molecule's symmetry) in the RMSD's place:
+    float32 [num_ref, num_gen] on `device`.  The item must carry its bonds.  hands=True: (proper, mirror), mirror being the TFD
+    of every generated conformer's mirror image (a reflection negates every dihedral)."""
+    from .torsions import tfd_matrix
+    return tfd_matrix(data, hands=hands, weights=weights, device=device)
+
+
+TFD_THRESHOLDS = np.arange(1, 61) / 100.0            # 0.01 .. 0.60: the TFD lies in [0, 1], 0.2 being the usual "same conformer"
+
+
 def matrix_minima(confusion):
     """(rmsd_ref_min [R], rmsd_gen_min [G]) of a confusion matrix on the GPU (covmat.py:135-136)."""
     import torch
@@ -242,12 +254,20 @@ class CovMatEvaluator(object):
     either_hand=True: the results also carry `either_hand`, the same five fields computed from min(proper, mirror) -- every
     generated conformer scored as the better of itself and its mirror image (get_rmsd_confusion_matrix(hands=True)) -- and
     `mirror_nearest`, per molecule the fraction of generated conformers whose nearest reference is reached through the mirror
-    image.  No stereo tags are needed: it shows what handedness costs a run.  `confusion_fn` must then return (proper, mirror)."""
+    image.  No stereo tags are needed: it shows what handedness costs a run.  `confusion_fn` must then return (proper, mirror).
+    metric="tfd": the same reductions and table over get_tfd_confusion_matrix; the thresholds then default to 0.01 .. 0.60 in
+    steps of 0.01 (for the RMSD, as in the reference, 0.05 .. 3.00 Angstrom in steps of 0.05)."""
 
-    def __init__(self, num_workers=8, use_force_field=False, thresholds=np.arange(0.05, 3.05, 0.05), ratio=2,
-                 filter_disconnected=True, print_fn=print, confusion_fn=None, either_hand=False):
+    def __init__(self, num_workers=8, use_force_field=False, thresholds=None, ratio=2,
+                 filter_disconnected=True, print_fn=print, confusion_fn=None, either_hand=False, metric="rmsd"):
         if use_force_field:
             raise NotImplementedError("MMFF relaxation needs rdkit; not available here")
+        if metric not in ("rmsd", "tfd"):
+            raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
+        if thresholds is None:
+            thresholds = np.arange(0.05, 3.05, 0.05) if metric == "rmsd" else TFD_THRESHOLDS
+        self.metric = metric
+        self._confusion = get_rmsd_confusion_matrix if metric == "rmsd" else get_tfd_confusion_matrix
         self.num_workers = num_workers
         self.use_force_field = use_force_field
         self.thresholds = np.array(thresholds).flatten()
@@ -285,7 +305,7 @@ class CovMatEvaluator(object):
                     e_ref_min, e_gen_min = both.min(-1), both.min(0)
                 else:
                     import torch
-                    proper, mirror = get_rmsd_confusion_matrix(data, hands=True)
+                    proper, mirror = self._confusion(data, hands=True)
                     rmin, gmin = matrix_minima(proper)
                     _, mmin = matrix_minima(mirror)
                     ermin, egmin = matrix_minima(torch.minimum(proper, mirror))
@@ -298,7 +318,7 @@ class CovMatEvaluator(object):
                 cm = np.asarray(self.confusion_fn(data))
                 ref_min, gen_min = cm.min(-1), cm.min(0)
             else:
-                rmin, gmin = matrix_minima(get_rmsd_confusion_matrix(data))
+                rmin, gmin = matrix_minima(self._confusion(data))
                 ref_min, gen_min = rmin.cpu().numpy(), gmin.cpu().numpy()
             covr, matr, covp, matp = scores_from_minima(ref_min, gen_min, self.thresholds)
             covr_scores.append(covr); matr_scores.append(matr); covp_scores.append(covp); matp_scores.append(matp)
@@ -325,7 +345,9 @@ def main(argv=None):
     optional `smiles_<i>`, `bond_index_<i>` + `bond_type_<i>` (symmetry-aware RMSD) or `perms_<i>` [P, m].  Prints the COV / MAT table of the reference's eval_covmat.py.
     --either-hand: then a second table, labelled "either hand", from min(proper, mirror) -- every generated conformer scored as the
     better of itself and its mirror image -- and the fraction of generated conformers whose nearest reference is reached through
-    the mirror image."""
+    the mirror image.
+    --metric tfd: the tables over the torsion fingerprint deviation (agdiff_amd.torsions; the refs must carry the bonds) at the
+    thresholds 0.01 .. 0.60 instead of the heavy-atom RMSD."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--samples", required=True)
@@ -333,6 +355,8 @@ def main(argv=None):
     ap.add_argument("--ratio", type=int, default=2)
     ap.add_argument("--either-hand", action="store_true",
                     help="also print the table computed from min(proper, mirror): what the run would score were handedness free")
+    ap.add_argument("--metric", default="rmsd", choices=["rmsd", "tfd"],
+                    help="'tfd': COV / MAT over the torsion fingerprint deviation (thresholds 0.01 .. 0.60) instead of the RMSD")
     args = ap.parse_args(argv)
     zs, zr = np.load(args.samples), np.load(args.refs)
     items = []
@@ -351,7 +375,7 @@ def main(argv=None):
         if "pos_gen_" + i in zs.files:
             d["pos_gen"] = zs["pos_gen_" + i]
         items.append(d)
-    res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand)(items)
+    res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand, metric=args.metric)(items)
     print_covmat_results(res)
     if args.either_hand:
         print("\neither hand (every generated conformer scored as the better of itself and its mirror image):")

@@ -41,7 +41,8 @@ extern "C" {
 #define AGDIFF_MAX_CHUNK_TILES 8   /* most tiles one wave walks per chunk in the fused CFConv kernel (128 edges) */
 #define AGDIFF_RMSD_MAX_ATOMS 256  /* most (heavy) atoms per conformer in agdiff_rmsd_matrix / agdiff_rmsd_self */
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
-#define AGDIFF_POLY_MAX_KT 4       /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
+#define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
+#define AGDIFF_POLY_MAX_KT 4      /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
 #define AGDIFF_POLY_MAX_SLOTS 16   /* most local edge types with filter polynomials; the first sets that fit stay in LDS next to the
                                       radius edges' set (5 at poly_kt 1), the others are read from L2 by the tiles that meet them */
@@ -809,6 +810,44 @@ int agdiff_chiral_verdict(const float* pos, const int32_t* quads, const int8_t* 
  * centroid of ALL n atoms.  Inversion through the centroid keeps every distance and the centroid.  Conformers with
  * flags[g] == 0 are neither read nor written.  pos [G][n][3]. */
 int agdiff_mirror_conformers(float* pos, const int32_t* flags, int32_t G, int32_t n, void* stream);
+
+/* ---- torsion fingerprint deviation -----------------------------------------------------------------------------------
+ * The second standard metric between conformers next to the RMSD: the mean circular difference of the rotatable bonds'
+ * dihedrals, in [0, 1] and independent of the molecule's size (rdkit Chem.TorsionFingerprints.GetTFDBetweenConformers /
+ * GetTFDMatrix, which the reference never calls; ring torsions and rdkit's distance-from-centre weights are not built, a caller
+ * passes weights).  The host finds the torsions (agdiff_amd/torsions.py).  Two calls, no atomics, deterministic bit for bit.
+ *
+ * agdiff_torsion_angles: what rdkit's rdMolTransforms.GetDihedralRad gives for every quad of every conformer.
+ *   pos [G][n][3]
+ *   quads [Q][4] int32     atoms (a, u, v, b) of each column: the bond u - v, a neighbour a of u and a neighbour b of v (may be
+ *                          null when Q = 0)
+ *   out [G][Q]             theta = atan2(|b2| (b1 . n2), n1 . n2) in radians in [-pi, pi], with b1 = p_u - p_a, b2 = p_v - p_u,
+ *                          b3 = p_b - p_v, n1 = b1 x b2, n2 = b2 x b3; fp64 from the fp32 positions, stored as fp32.  The
+ *                          mirror image has -theta; theta(a, u, v, b) = theta(b, v, u, a).  NaN when |n1|^2 or |n2|^2 is zero
+ *                          or a coordinate is not finite.  A quad naming an atom outside [0, n) gives NaN and reads nothing.
+ * One wave per conformer, lanes over the columns. */
+int agdiff_torsion_angles(const float* pos, const int32_t* quads, int32_t G, int32_t n, int32_t Q, float* out, void* stream);
+
+/* agdiff_tfd_matrix: what GetTFDMatrix (self) and GetTFDBetweenConformers (cross) give, over angle tables of the call above.
+ *   ang_x [R][Q], ang_y [G][Q]   angle tables of the same molecule (the same table for a self matrix); Q <= AGDIFF_TFD_MAX_COLUMNS
+ *   tmap [P][T] int32            P >= 1 mappings of the T <= Q torsions onto columns, entries in [0, Q) (NOT checked here: the
+ *                                caller does).  Row 0: each torsion's own column; row p: the column that holds the image of
+ *                                torsion t under the molecule's p-th symmetry.
+ *   w [T] or null                weights > 0; null = uniform
+ *   delta(a, b) = min(|a - b|, 2 pi - |a - b|) in fp64 from the stored fp32 angles, pi when either is NaN
+ *   S_p(x -> y) = sum_t w[t] delta(x[tmap[0][t]], y[tmap[p][t]]) / (pi sum_t w[t]),  t ascending, fp64
+ *   out [R][G] or null           min_p min(S_p(x -> y), S_p(y -> x)) as fp32 -- both directions, because row 0's choice of
+ *                                neighbours is not carried along by the symmetries and one direction alone is not symmetric
+ *                                in (x, y).  T = 0 (a rigid molecule): 0.
+ *   out_mirror [R][G] or null    the same with every angle of y negated: the TFD to y's mirror image.  Not overlapping out.
+ *   bits or null                 the adjacency out <= thresh (>= 0) on the fp32 value as stored (computed whether or not out is
+ *                                given), in exactly the layout of agdiff_rmsd_self: R rows of 16-bit pieces, row pitch
+ *                                2 ceil(G / 16) bytes rounded up to 8, bits of columns >= G zero; 8-byte aligned.
+ * With ang_x == ang_y the matrices are exactly symmetric and the diagonal of out is 0 where a conformer's angles are not NaN.
+ * At least one of the three outputs must be given.  One workgroup per 16 x 16 tile of pairs, the 32 angle rows in LDS. */
+int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const int32_t* tmap, const float* w, int32_t R, int32_t G,
+                      int32_t Q, int32_t T, int32_t P, float thresh, float* out, float* out_mirror, uint64_t* bits,
+                      void* stream);
 
 #ifdef __cplusplus
 }
