@@ -676,6 +676,176 @@ __global__ void __launch_bounds__(256) k_tfd_matrix(const float* __restrict__ an
   }
 }
 
+// ---- geometry validity: a sampled conformer can be finite and still broken (a stretched bond, two rings pushed through each
+// other).  Two topology-only checks: bounded pair distances, and an all-pairs clash scan that leaves out the pairs 1 .. 3 bonds apart --
+
+// the fp64 distance of atoms a and b of one conformer from the fp32 positions
+__device__ __forceinline__ double ag_pair_dist(const float* __restrict__ p, int a, int b) {
+  const double dx = (double)p[3 * a] - (double)p[3 * b], dy = (double)p[3 * a + 1] - (double)p[3 * b + 1];
+  const double dz = (double)p[3 * a + 2] - (double)p[3 * b + 2];
+  return sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+// one wave per conformer, lanes over the pairs (strided past 64), shaped like k_torsion_angles: d as fp32, the violation
+// v = max(lo - d, d - hi, 0) on that fp32 d (+inf when d is not finite), then max / lowest index / count across the lanes by
+// shuffles.  A pair that names an atom outside [0, n) has d = NaN, v = +inf and reads nothing.
+__global__ void __launch_bounds__(64) k_pair_bounds(const float* __restrict__ pos, const int32_t* __restrict__ pairs,
+                                                    const float* __restrict__ lo, const float* __restrict__ hi, int n, int K,
+                                                    float* __restrict__ dist, float* __restrict__ worst,
+                                                    int32_t* __restrict__ worst_pair, int32_t* __restrict__ n_bad) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  float best = -1.0f;                               // (below every violation: the lane's first pair is taken)
+  int best_k = -1, bad = 0;
+  for (int k = lane; k < K; k += 64) {
+    const int a = pairs[2 * k], b = pairs[2 * k + 1];
+    float d = NAN;
+    if ((unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n) d = (float)ag_pair_dist(p, a, b);
+    if (dist) dist[(size_t)g * K + k] = d;
+    float v = INFINITY;
+    if (fabsf(d) <= 3.40282347e38f) v = (float)fmax(fmax((double)lo[k] - (double)d, (double)d - (double)hi[k]), 0.0);
+    bad += v > 0.0f ? 1 : 0;
+    if (v > best) { best = v; best_k = k; }         // (k ascends: the lane keeps its lowest k)
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o);
+    const int ok = __shfl_xor(best_k, o);
+    bad += __shfl_xor(bad, o);
+    if (ok >= 0 && (ov > best || (ov == best && ok < best_k))) { best = ov; best_k = ok; }
+  }
+  if (lane == 0) {
+    worst[g] = best_k < 0 ? 0.0f : best;
+    worst_pair[g] = best_k;
+    n_bad[g] = bad;
+  }
+}
+
+// (ratio, i, j) a is the better clash candidate than b: the smaller ratio, then the lowest i (j is already the lowest of its i);
+// "no pair" carries i = INT32_MAX and loses to every pair, one of ratio +inf included
+__device__ __forceinline__ bool ag_clash_better(float ra, int ia, float rb, int ib) { return ra < rb || (ra == rb && ia < ib); }
+
+// Grid (S, G): a workgroup owns the atoms i of one slice of AGDIFF_CLASH_SLICE atoms of one conformer, thread t one i.  The
+// atoms j are walked in tiles of the same size staged in LDS as (x, y, z, radius); every lane reads the same j (a broadcast),
+// and only the tiles from the slice's own on are visited (j > i).  Each lane carries a cursor into its own ascending
+// exclusion row: `nx`, the next excluded j, sits in a register and the row is read again only when j reaches it -- a two-pointer
+// merge, O(n + degree) per atom, no n x n mask.
+//   ratio = (float)(d / (r_i + r_j)) in fp64, 0 when d is not finite.
+// Most pairs are far apart: a pair with d^2 > (c (r_i + r_j))^2 (1 + 1e-6), c = max(thresh, the lane's minimum so far), has a
+// ratio above c after rounding too (fp32 rounding is monotonic and 1e-6 covers the fp64 error many times over), so it neither
+// counts nor lowers the minimum and skips the square root and the division.
+// One partial per (g, slice) goes to scratch: { bits(min ratio), i, j, count }, i = j = -1 when the slice has no pair.
+__global__ void __launch_bounds__(AGDIFF_CLASH_SLICE) k_clash_scan(const float* __restrict__ pos, const float* __restrict__ radius,
+                                                                   const int32_t* __restrict__ ex_ptr,
+                                                                   const int32_t* __restrict__ ex_idx, int n, float thresh,
+                                                                   int32_t* __restrict__ scratch) {
+  __shared__ float4 s_atom[AGDIFF_CLASH_SLICE];
+  __shared__ float s_r[AGDIFF_CLASH_SLICE / 64];
+  __shared__ int32_t s_i[AGDIFF_CLASH_SLICE / 64], s_j[AGDIFF_CLASH_SLICE / 64], s_c[AGDIFF_CLASH_SLICE / 64];
+  const int slice = blockIdx.x, g = blockIdx.y, S = gridDim.x, t = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  const int i = slice * AGDIFF_CLASH_SLICE + t;
+  const bool active = i < n;
+  double xi = 0.0, yi = 0.0, zi = 0.0, ri = 0.0;
+  int cur = 0, end = 0;
+  if (active) {
+    xi = p[3 * i]; yi = p[3 * i + 1]; zi = p[3 * i + 2]; ri = radius[i];
+    int lo_ = ex_ptr[i];
+    end = ex_ptr[i + 1];
+    int hi_ = end;
+    while (lo_ < hi_) {                             // the first entry of the row above i
+      const int mid = (lo_ + hi_) >> 1;
+      if (ex_idx[mid] <= i) lo_ = mid + 1; else hi_ = mid;
+    }
+    cur = lo_;
+  }
+  int nx = cur < end ? ex_idx[cur] : 0x7fffffff;
+  float minr = INFINITY;
+  int minj = -1, count = 0;
+  const double th = (double)thresh;
+  double c2 = (double)INFINITY;                     // (max(thresh, minr))^2 (1 + 1e-6)
+  for (int jt = slice; jt < S; ++jt) {
+    const int j0 = jt * AGDIFF_CLASH_SLICE;
+    __syncthreads();
+    if (j0 + t < n) s_atom[t] = make_float4(p[3 * (j0 + t)], p[3 * (j0 + t) + 1], p[3 * (j0 + t) + 2], radius[j0 + t]);
+    __syncthreads();
+    const int cnt = min(AGDIFF_CLASH_SLICE, n - j0);
+    if (!active) continue;
+    for (int jj = 0; jj < cnt; ++jj) {
+      const int j = j0 + jj;
+      if (j <= i) continue;
+      if (j == nx) {
+        ++cur;
+        nx = cur < end ? ex_idx[cur] : 0x7fffffff;
+        continue;
+      }
+      const float4 q = s_atom[jj];
+      const double dx = xi - (double)q.x, dy = yi - (double)q.y, dz = zi - (double)q.z;
+      const double d2 = dx * dx + dy * dy + dz * dz, rs = ri + (double)q.w;
+      if (d2 > c2 * (rs * rs) && d2 <= 1.79769313486231570e308) continue;
+      const double d = sqrt(d2);
+      const float r = d <= 1.79769313486231570e308 ? (float)(d / rs) : 0.0f;
+      count += r < thresh ? 1 : 0;
+      if (r < minr || minj < 0) {
+        minr = r; minj = j;
+        const double c = fmax(th, (double)r);
+        c2 = c * c * (1.0 + 1e-6);
+      }
+    }
+  }
+  // the workgroup's (min, pair, count): across each wave by shuffles, then the four waves in order
+  int mini = minj >= 0 ? i : 0x7fffffff;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float orr = __shfl_xor(minr, o);
+    const int oi = __shfl_xor(mini, o), oj = __shfl_xor(minj, o);
+    count += __shfl_xor(count, o);
+    if (ag_clash_better(orr, oi, minr, mini)) { minr = orr; mini = oi; minj = oj; }
+  }
+  if ((t & 63) == 0) { s_r[t >> 6] = minr; s_i[t >> 6] = mini; s_j[t >> 6] = minj; s_c[t >> 6] = count; }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int w = 1; w < AGDIFF_CLASH_SLICE / 64; ++w) {
+      count += s_c[w];
+      if (ag_clash_better(s_r[w], s_i[w], minr, mini)) { minr = s_r[w]; mini = s_i[w]; minj = s_j[w]; }
+    }
+    int32_t* o = scratch + ((size_t)g * S + slice) * 4;
+    o[0] = __float_as_int(minr);
+    o[1] = minj >= 0 ? mini : -1;
+    o[2] = minj;
+    o[3] = count;
+  }
+}
+
+// one wave per conformer: the S partials of k_clash_scan, lanes over the slices (strided past 64) in slice order
+__global__ void __launch_bounds__(64) k_clash_finish(const int32_t* __restrict__ scratch, int S, float* __restrict__ min_ratio,
+                                                     int32_t* __restrict__ min_pair, int32_t* __restrict__ n_clash) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  float minr = INFINITY;
+  int mini = 0x7fffffff, minj = -1, count = 0;
+  for (int s = lane; s < S; s += 64) {
+    const int32_t* o = scratch + ((size_t)g * S + s) * 4;
+    const float r = __int_as_float(o[0]);
+    const int oi = o[1] >= 0 ? o[1] : 0x7fffffff;
+    count += o[3];
+    if (ag_clash_better(r, oi, minr, mini)) { minr = r; mini = oi; minj = o[2]; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float orr = __shfl_xor(minr, o);
+    const int oi = __shfl_xor(mini, o), oj = __shfl_xor(minj, o);
+    count += __shfl_xor(count, o);
+    if (ag_clash_better(orr, oi, minr, mini)) { minr = orr; mini = oi; minj = oj; }
+  }
+  if (lane == 0) {
+    min_ratio[g] = minr;
+    min_pair[2 * g] = minj >= 0 ? mini : -1;
+    min_pair[2 * g + 1] = minj;
+    n_clash[g] = count;
+  }
+}
+
 }  // namespace
 
 extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
@@ -815,6 +985,34 @@ extern "C" int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const i
   const int pitch = (tiles_g * 2 + 7) / 8 * 8;
   k_tfd_matrix<<<dim3((unsigned)tiles_g, (unsigned)((R + 15) / 16)), dim3(256), smem_for(Q), (hipStream_t)stream>>>(
       ang_x, ang_y, tmap, w, R, G, Q, T, P, thresh, out, out_mirror, (uint16_t*)bits, pitch);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_pair_bounds(const float* pos, const int32_t* pairs, const float* lo, const float* hi, int32_t G, int32_t n, int32_t K,
+                                  float* dist, float* worst, int32_t* worst_pair, int32_t* n_bad, void* stream) {
+  if (!pos || !worst || !worst_pair || !n_bad || G < 0 || n <= 0 || K < 0 || (K > 0 && (!pairs || !lo || !hi))) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_pair_bounds<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, pairs, lo, hi, n, K, dist, worst, worst_pair, n_bad);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_clash_scan(const float* pos, const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, int32_t G, int32_t n,
+                                 float thresh, int32_t* scratch, float* min_ratio, int32_t* min_pair, int32_t* n_clash, void* stream) {
+  if (!pos || !radius || !ex_ptr || !scratch || !min_ratio || !min_pair || !n_clash || G < 0 || n <= 0) return AGDIFF_ERR_ARG;
+  if (!(thresh >= 0.0f && thresh <= 3.40282347e38f)) return AGDIFF_ERR_ARG;
+  if (n > AGDIFF_MAX_ATOMS_LARGE) return AGDIFF_ERR_LIMIT;
+  if (G == 0) return AGDIFF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int S = (n + AGDIFF_CLASH_SLICE - 1) / AGDIFF_CLASH_SLICE;
+  for (int g0 = 0; g0 < G; g0 += 65535) {           // (a grid's y extent ends at 65535)
+    const int gc = G - g0 < 65535 ? G - g0 : 65535;
+    k_clash_scan<<<dim3((unsigned)S, (unsigned)gc), dim3(AGDIFF_CLASH_SLICE), 0, st>>>(pos + (size_t)g0 * n * 3, radius, ex_ptr, ex_idx, n,
+                                                                                    thresh, scratch + (size_t)g0 * S * 4);
+    AG_CHECK_LAUNCH();
+  }
+  k_clash_finish<<<dim3((unsigned)G), dim3(64), 0, st>>>(scratch, S, min_ratio, min_pair, n_clash);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -12,7 +12,7 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 `num_refs_i` scalar, `name_i` string.  Output: `samples_<first>_<last>.npz` per batch (named by the molecule
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
 --save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T; + `hand_<i>` [num_samples] with --fix-handedness, which needs
-`stereo_<i>` in the test set) and the merged `samples_all.npz`, written by rank 0 after a barrier.
+`stereo_<i>` in the test set; + `valid_<i>`, `bond_dev_<i>` and `clash_<i>` [num_samples] with --check-geometry) and the merged `samples_all.npz`, written by rank 0 after a barrier.
 
 `--noise counter` draws every conformer's pos_init and noise from the counter-based generator under `--seed` and the conformer's
 stream id (`stream_id`): the same numbers whatever --max-atoms, the packing, a --resume or the number of ranks.
@@ -411,7 +411,7 @@ def merge_outputs(out_dir):
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
-            fix_handedness=False, prune_tfd=None):
+            fix_handedness=False, prune_tfd=None, check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -427,7 +427,12 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     against the molecule's `stereo` tags (load_testset: `stereo_<i>`; a molecule without them is an error) and the mirror images
     are inverted through their centroid (agdiff_amd.stereo.fix_handedness on the GPU) -- before the prune, which then compares
     like with like.  `pos_gen_<i>` holds the mirrored conformers, `hand_<i>` int8 [G] the verdict before the fix: -1 was mirrored,
-    0 (a diastereomer or a flat centre) is left as sampled, +1 was right."""
+    0 (a diastereomer or a flat centre) is left as sampled, +1 was right.
+    check_geometry=True: every saved molecule also gets `valid_<i>` int8 [G], `bond_dev_<i>` float32 [G] (the worst violation of a
+    bond-length bound in Angstrom) and `clash_<i>` float32 [G] (the smallest distance between atoms more than three bonds apart as
+    a fraction of their van der Waals sum) -- agdiff_amd.validity.check_geometry with the table bounds, after the handedness fix
+    and before the prune.  `pos_gen_<i>` is left as it is; with a prune switch the invalid conformers take no part in the walk
+    (`cluster_<i>` is -1 for them)."""
     if noise not in ("default", "counter"):
         raise ValueError("noise must be 'default' or 'counter'")
     if prune_rms is not None and not float(prune_rms) >= 0.0:
@@ -498,7 +503,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     fut = submit(mine[0], first=True) if mine else None
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world, counter_seed, prune_rms, fix_handedness, prune_tfd)
+                                world, counter_seed, prune_rms, fix_handedness, prune_tfd, check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -507,9 +512,9 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None):
+                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, check_geometry=False):
     import torch.distributed as dist
-    mirrored = undecided = 0
+    mirrored = undecided = checked = invalid = 0
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
         # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until here,
@@ -556,11 +561,22 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 out["hand_%d" % m["index"]] = hand
                 mirrored += int((hand < 0).sum())
                 undecided += int((hand == 0).sum())
+            valid = None
+            if check_geometry:
+                from .validity import check_geometry as check
+                res = check(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
+                                 edge_type=m["edge_type"]), device=device)
+                valid = res["valid"]
+                out["valid_%d" % m["index"]] = valid.cpu().numpy().astype(np.int8)
+                out["bond_dev_%d" % m["index"]] = res["bond_dev"].cpu().numpy()
+                out["clash_%d" % m["index"]] = res["clash"].cpu().numpy()
+                checked += int(valid.shape[0])
+                invalid += int((~valid).sum())
             if prune_rms is not None or prune_tfd is not None:
                 from .ensemble import prune_conformers
                 res = prune_conformers(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
                                             edge_type=m["edge_type"]), float(prune_rms if prune_tfd is None else prune_tfd), align=False,
-                                       device=device, metric="rmsd" if prune_tfd is None else "tfd")
+                                       device=device, metric="rmsd" if prune_tfd is None else "tfd", valid=valid)
                 out["kept_%d" % m["index"]] = res["kept"].cpu().numpy()
                 out["cluster_%d" % m["index"]] = res["leader"].cpu().numpy()
             if traj is not None:
@@ -571,6 +587,9 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
     if fix_handedness and (rank == 0 or mirrored or undecided):       # (the ranks that wrote files)
         log("rank %d: %d conformers were mirror images and were inverted; %d match neither hand (verdict 0) and stay as sampled"
             % (rank, mirrored, undecided))
+    if check_geometry and (rank == 0 or checked):
+        log("rank %d: %d of %d conformers are invalid (a bond length out of bounds or a steric clash) and are marked in valid_<i>"
+            % (rank, invalid, checked))
     if world > 1:
         dist.barrier()                       # every rank's batch files are on disk
     if SAMPLE_STATS["range_trips"]:
@@ -616,6 +635,10 @@ def main(argv=None):
                     help="invert the conformers that came out as the mirror image (the sampler cannot tell the hands apart): needs "
                          "stereo_<i> in the test set (python -m agdiff_amd.stereo); pos_gen_<i> then holds the mirrored conformers and "
                          "hand_<i> the verdict before the fix (-1 mirrored, 0 neither hand: left as sampled, +1 right)")
+    ap.add_argument("--check-geometry", action="store_true",
+                    help="also save, per molecule, valid_<i>, bond_dev_<i> and clash_<i>: which conformers pass the bond-length bounds "
+                         "and the steric clash scan of agdiff_amd.validity (pos_gen_<i> still holds them all); with --prune-rms / "
+                         "--prune-tfd the invalid ones are left out of the walk (cluster_<i> = -1)")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
     ap.add_argument("--dist-mode", default="shard", choices=["shard", "batches"],
                     help="with several ranks: 'shard' = every packed batch (max-atoms x world atoms) is split into "
@@ -658,7 +681,8 @@ def main(argv=None):
               clip=args.clip)
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
-            seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd)
+            seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
+            check_geometry=args.check_geometry)
     if own_pg:
         dist.destroy_process_group()
 

@@ -13,7 +13,7 @@ heavy-atom self-matches (GetBestRMS), without them the identity mapping only.  H
 along in the alignment.
 
     python -m agdiff_amd.ensemble --samples out/samples_all.npz --testset test.npz --prune-rms 0.5 [--align] [--fix-handedness]
-                                  --out pruned.npz
+                                  [--drop-invalid] --out pruned.npz
     (--prune-tfd 0.2 in --prune-rms's place: the same walk over the torsion fingerprint deviation, agdiff_amd.torsions)
 """
 import numpy as np
@@ -126,7 +126,15 @@ def align_conformers(pos, atom_type, target, device="cuda"):
     return _align(p, torch.from_numpy(heavy).to(device), t[0])
 
 
-def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False, metric="rmsd"):
+def _valid_mask(valid, G):
+    """bool numpy [G] from a bool mask (numpy or tensor); anything else is a ValueError, before any launch"""
+    v = valid.cpu().numpy() if hasattr(valid, "is_cuda") else np.asarray(valid)
+    if v.dtype != np.bool_ or v.shape != (G,):
+        raise ValueError("valid must be a bool mask with one entry per conformer: [%d] (got %s %s)" % (G, v.dtype, tuple(v.shape)))
+    return v
+
+
+def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False, metric="rmsd", valid=None):
     """RDKit's pruneRmsThresh rule over the item's generated conformers, in their order: a conformer is kept iff its best RMSD
     to every conformer kept before it is above `threshold`; a dropped one belongs to the first kept conformer within the
     threshold.  metric="tfd": the same leader walk with the torsion fingerprint deviation (agdiff_amd.torsions; in [0, 1], the item
@@ -142,6 +150,9 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     families that can never superpose; the dict also gets
         hand   int32 [G]  the verdict before the fix: -1 was mirrored, 0 matches neither hand and is left as it is, +1 was right
     and `pos` holds the mirrored coordinates.
+    valid (bool [G], e.g. agdiff_amd.validity.check_geometry(item)["valid"]): the walk runs over the valid conformers only, in their
+    order -- a broken conformer is far from everything, so without the mask the rule keeps every one of them.  `kept` still indexes
+    the item's conformers, `leader` is -1 for an invalid one, and with no valid conformer `kept` is empty and nothing is aligned.
     At most AGDIFF_PRUNE_MAX_CONFS conformers."""
     import torch
     if metric not in ("rmsd", "tfd"):
@@ -154,11 +165,25 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
         raise ValueError("no conformers to prune")
     if G > MAX_CONFS:
         raise _lib.AgdiffLimitError("prune_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
+    mask = None if valid is None else _valid_mask(valid, G)
     hand = None
     if fix_handedness:
         from .stereo import fix_handedness as fix
         gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
         hand = fix(item, gen)
+    sel = None
+    if mask is not None:                                 # compacted on the device; the kernels below see the valid ones only
+        gen = gen.to(device).contiguous()
+        sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
+        G = int(sel.shape[0])
+        if G == 0:
+            res = {"kept": torch.empty(0, dtype=torch.int32, device=gen.device),
+                   "leader": torch.full((mask.shape[0],), -1, dtype=torch.int32, device=gen.device),
+                   "count": torch.empty(0, dtype=torch.int32, device=gen.device), "pos": gen[:0]}
+            if hand is not None:
+                res["hand"] = hand
+            return res
+        gen = gen[sel].contiguous()
     if metric == "tfd":
         from .torsions import _self_tfd
         gen, _, bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
@@ -173,6 +198,10 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
         pos, _ = _align(pos, idx, first)
         pos[0] = first
     res = {"kept": kept.to(torch.int32), "leader": leader, "count": count[kept], "pos": pos}
+    if sel is not None:                                  # back to the item's own conformer indices
+        full = torch.full((mask.shape[0],), -1, dtype=torch.int32, device=leader.device)
+        full[sel] = sel[leader.long()].to(torch.int32)
+        res["kept"], res["leader"] = sel[kept].to(torch.int32), full
     if hand is not None:
         res["hand"] = hand
     return res
@@ -183,7 +212,9 @@ def main(argv=None):
     Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
     symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
     (+ `name_<i>`).  Exactly one of --prune-rms / --prune-tfd T (the torsion fingerprint deviation, in [0, 1]).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
-    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix."""
+    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix.  --drop-invalid: the conformers that fail
+    agdiff_amd.validity.check_geometry (table bounds, default clash ratio) take no part in the walk: `cluster_<i>` is -1 for them;
+    also writes `valid_<i>` int8 [G]."""
     import argparse
     from .driver import load_testset
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -195,6 +226,8 @@ def main(argv=None):
                      help="torsion fingerprint deviation threshold in [0, 1] (agdiff_amd.torsions) instead of an RMSD")
     ap.add_argument("--align", action="store_true", help="superpose the kept conformers on the first of them")
     ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
+    ap.add_argument("--drop-invalid", action="store_true",
+                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the walk")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -212,8 +245,13 @@ def main(argv=None):
             if mol.get("stereo") is None:
                 raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
             item["stereo"] = mol["stereo"]
+        valid = None
+        if args.drop_invalid:
+            from .validity import check_geometry
+            valid = check_geometry(item, device=args.device)["valid"]       # (mirroring keeps every distance: before or after the fix)
+            out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
         res = prune_conformers(item, threshold, align=args.align, device=args.device, fix_handedness=args.fix_handedness,
-                               metric=metric)
+                               metric=metric, valid=valid)
         out["pos_%d" % i] = res["pos"].cpu().numpy()
         out["kept_%d" % i] = res["kept"].cpu().numpy()
         out["cluster_%d" % i] = res["leader"].cpu().numpy()

@@ -1,0 +1,300 @@
+"""Geometry validity of sampled conformers.
+
+Every later stage asks of a conformer's geometry only that it is finite.  A diffusion sampler also produces conformers that are
+finite and wrong -- a bond stretched to 2.5 A after a clip_local retry, two ring systems pushed through each other, a hydrogen on top
+of a carbon five bonds away -- and the leader prune keeps exactly those, because a broken conformer is far from everything kept before
+it.  The reference pipeline catches them with rdkit's sanitisation and its optional MMFF step; this project has neither, but it holds
+what a topology-only check needs.  Two checks on the GPU (csrc/eval.hip; there is no CPU fallback):
+    agdiff_pair_bounds   the distances of named atom pairs against [lo, hi]: bond lengths, and through the 1-3 distances bond angles
+    agdiff_clash_scan    every pair i < j that is NOT 1, 2 or 3 bonds apart against a fraction of the sum of two radii
+
+  d           |p_i - p_j|, every coordinate converted to float64 before the first subtraction
+  violation   v = max(lo - d, d - hi, 0) in Angstrom on d rounded to float32; +inf when d is not finite or the pair names an atom
+              outside the molecule.  Per conformer: worst = max v, the lowest pair attaining it, n_bad = #{v > 0}
+  exclusions  every entry of type > 0 of the item's extended edge list (types 1 .. 21 bonds, 23 two-hop, 24 three-hop), as a
+              symmetric CSR with ascending rows
+  ratio       (float32)(d / (r_i + r_j)) over the pairs not excluded, 0 when d is not finite.  Per conformer: the smallest ratio
+              (+inf when there is no pair), the lowest (i, j) attaining it, n_clash = #{ratio < clash}
+  valid       n_bad == 0 and n_clash == 0
+
+The defaults are this project's choices, not rdkit's: covalent radii of Cordero et al. 2008 for the table bounds (a bond is within
+[0.72, 1.20] x (rc_i + rc_j): 0.72 admits C#N at 0.79 of the sum and C=O at 0.85, 1.20 every common single bond, all <= 1.02),
+Bondi's van der Waals radii for the clash scan at clash = 0.60 of their sum (O...H 1.63 A, C...C 2.04 A, H...H 1.44 A -- below an
+intramolecular hydrogen bond, so hydrogen bonds are not flagged).  Nobody has run them over GEOM's reference conformers: no
+false-positive rate is claimed.
+
+    python -m agdiff_amd.validity --samples out/samples_all.npz --testset test.npz [--refs refs.npz] [--clash 0.6] --out validity.npz
+"""
+import numpy as np
+
+from . import _lib
+from .evaluation import _as_conformers
+from .stereo import _bonds_of
+
+CLASH_SLICE = _lib.DEFINES["AGDIFF_CLASH_SLICE"]
+
+COVALENT_RADII = {1: 0.31, 5: 0.84, 6: 0.76, 7: 0.71, 8: 0.66, 9: 0.57, 14: 1.11, 15: 1.07, 16: 1.05, 17: 1.02, 35: 1.20, 53: 1.39}
+COVALENT_DEFAULT = 1.50
+VDW_RADII = {1: 1.20, 5: 1.92, 6: 1.70, 7: 1.55, 8: 1.52, 9: 1.47, 14: 2.10, 15: 1.80, 16: 1.80, 17: 1.75, 35: 1.85, 53: 1.98}
+VDW_DEFAULT = 2.00
+
+
+def covalent_radii(atom_type):
+    """float64 [n]: Cordero 2008 by atomic number, COVALENT_DEFAULT for an element not in the table."""
+    return np.array([COVALENT_RADII.get(int(a), COVALENT_DEFAULT) for a in np.asarray(atom_type).reshape(-1)], dtype=np.float64)
+
+
+def vdw_radii(atom_type):
+    """float32 [n]: Bondi by atomic number, VDW_DEFAULT for an element not in the table."""
+    return np.array([VDW_RADII.get(int(a), VDW_DEFAULT) for a in np.asarray(atom_type).reshape(-1)], dtype=np.float32)
+
+
+def _edges(n, edge_index, edge_type):
+    """(i, j, type) int64 of the entries of type > 0, i != j, range-checked"""
+    ei = np.asarray(edge_index).reshape(2, -1).astype(np.int64)
+    et = np.asarray(edge_type).reshape(-1).astype(np.int64)
+    if ei.shape[1] != et.shape[0]:
+        raise ValueError("%d edges but %d edge types" % (ei.shape[1], et.shape[0]))
+    sel = (et > 0) & (ei[0] != ei[1])
+    i, j, t = ei[0][sel], ei[1][sel], et[sel]
+    if i.size and (min(i.min(), j.min()) < 0 or max(i.max(), j.max()) >= n):
+        raise ValueError("the edge list names atoms outside the molecule's %d atoms" % n)
+    return i, j, t
+
+
+def exclusions(n, edge_index, edge_type):
+    """(ex_ptr int32 [n + 1], ex_idx int32): the pairs a clash scan leaves out, from EVERY entry of type > 0 of an extended edge list
+    (1, 2 or 3 bonds apart when the list is extended to order 3, as the driver's test sets are) -- symmetrised, each row ascending,
+    without duplicates or self entries."""
+    n = int(n)
+    i, j, _ = _edges(n, edge_index, edge_type)
+    key = np.unique(np.concatenate([i * n + j, j * n + i]))
+    rows, cols = key // max(n, 1), key % max(n, 1)
+    ex_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(ex_ptr, rows + 1, 1)
+    return np.cumsum(ex_ptr).astype(np.int32), cols.astype(np.int32)
+
+
+def _check_exclusions(n, ex_ptr, ex_idx):
+    ptr = np.asarray(ex_ptr)
+    idx = np.asarray(ex_idx)
+    if ptr.dtype != np.int32 or idx.dtype != np.int32 or ptr.ndim != 1 or idx.ndim != 1:
+        raise ValueError("ex_ptr and ex_idx must be one-dimensional int32 arrays")
+    if ptr.shape[0] != n + 1 or ptr[0] != 0 or (np.diff(ptr) < 0).any() or ptr[-1] != idx.shape[0]:
+        raise ValueError("ex_ptr must be [n + 1] = [%d], start at 0, not decrease and end at len(ex_idx)" % (n + 1))
+    if idx.size == 0:
+        return
+    if idx.min() < 0 or idx.max() >= n:
+        raise ValueError("ex_idx names atoms outside [0, %d)" % n)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+    same_row = rows[1:] == rows[:-1]
+    if (np.diff(idx.astype(np.int64))[same_row] <= 0).any():
+        raise ValueError("every row of ex_idx must be strictly ascending (unsorted or repeated entry)")
+    if (rows == idx).any():
+        raise ValueError("ex_idx holds a self entry")
+    if not np.array_equal(rows * n + idx, np.sort(idx.astype(np.int64) * n + rows)):
+        raise ValueError("the exclusions are not symmetric")
+
+
+def _bond_pairs(item, types):
+    """sorted unique (i, j), i < j, of the item's edge entries whose type passes `types`; the item must carry bonds"""
+    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    i, j, t = _edges(n, *_bonds_of(item))
+    sel = types(t)
+    a, b = np.minimum(i[sel], j[sel]), np.maximum(i[sel], j[sel])
+    key = np.unique(a * n + b)
+    return np.stack([key // max(n, 1), key % max(n, 1)], axis=1).astype(np.int32).reshape(-1, 2)
+
+
+def bounds_from_table(item, bond_lo=0.72, bond_hi=1.20):
+    """(pairs int32 [K, 2], lo float32 [K], hi float32 [K]): one pair per bond of type 1 .. 21, i < j, in (i, j) order, bounded by
+    bond_lo and bond_hi x the sum of the two covalent radii."""
+    if not 0.0 <= float(bond_lo) <= float(bond_hi):
+        raise ValueError("need 0 <= bond_lo <= bond_hi (got %r, %r)" % (bond_lo, bond_hi))
+    pairs = _bond_pairs(item, lambda t: (t >= 1) & (t <= 21))
+    rc = covalent_radii(item["atom_type"])
+    s = rc[pairs[:, 0]] + rc[pairs[:, 1]]
+    return pairs, (float(bond_lo) * s).astype(np.float32), (float(bond_hi) * s).astype(np.float32)
+
+
+def bounds_from_references(item, slack=0.05):
+    """(pairs, lo, hi) from the item's reference conformers `pos_ref` [R, n, 3]: the bonds and the two-hop entries (types 1 .. 21 and
+    23; the 1-3 distances bound the bond angles), lo = (1 - slack) x the smallest and hi = (1 + slack) x the largest distance over
+    the references.  Host work in float64."""
+    if not 0.0 <= float(slack) < 1.0:
+        raise ValueError("slack must be in [0, 1) (got %r)" % (slack,))
+    get = (lambda k: item.get(k)) if isinstance(item, dict) else (lambda k: getattr(item, k, None))
+    if get("pos_ref") is None:
+        raise ValueError("the item carries no reference conformers (pos_ref)")
+    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    ref = get("pos_ref")
+    ref = (ref.detach().cpu().numpy() if hasattr(ref, "detach") else np.asarray(ref)).astype(np.float64).reshape(-1, n, 3)
+    if ref.shape[0] == 0 or not np.isfinite(ref).all():
+        raise ValueError("pos_ref must hold at least one conformer and be finite")
+    pairs = _bond_pairs(item, lambda t: ((t >= 1) & (t <= 21)) | (t == 23))
+    d = np.sqrt(((ref[:, pairs[:, 0]] - ref[:, pairs[:, 1]]) ** 2).sum(-1))
+    return pairs, ((1.0 - float(slack)) * d.min(0)).astype(np.float32), ((1.0 + float(slack)) * d.max(0)).astype(np.float32)
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
+
+
+def pair_bounds(pos, pairs, lo, hi, want_dist=False):
+    """agdiff_pair_bounds on pos [G, n, 3] (float32, contiguous, on the GPU): (worst float32 [G], worst_pair int32 [G], n_bad int32
+    [G], dist float32 [G, K] or None).  pairs int32 [K, 2], lo / hi [K] (numpy or tensors; no NaN, lo <= hi).  A pair naming an atom
+    outside [0, n) is allowed: its violation is +inf and nothing is read."""
+    import torch
+    from .stereo import _device_conformers
+    _device_conformers(pos)
+    G, n = int(pos.shape[0]), int(pos.shape[1])
+    if n == 0:
+        raise ValueError("conformers without atoms")
+    pr = np.array(_host(pairs).reshape(-1, 2), dtype=np.int32)          # (copies: the caller's arrays may be read-only)
+    K = pr.shape[0]
+    lo_, hi_ = (np.array(_host(x).reshape(-1), dtype=np.float32) for x in (lo, hi))
+    if lo_.shape[0] != K or hi_.shape[0] != K:
+        raise ValueError("%d pairs but %d lower and %d upper bounds" % (K, lo_.shape[0], hi_.shape[0]))
+    if K and not (lo_ <= hi_).all():
+        raise ValueError("every pair needs lo <= hi (and neither may be NaN)")
+    lib = _lib.load()
+    dev = pos.device
+    worst = torch.empty(G, dtype=torch.float32, device=dev)
+    worst_pair, n_bad = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
+    dist = torch.empty((G, K), dtype=torch.float32, device=dev) if want_dist else None
+    if G:
+        pt, lt, ht = ((torch.from_numpy(x).to(dev) if K else None) for x in (pr, lo_, hi_))
+        with torch.cuda.device(dev):
+            _lib.check(lib.agdiff_pair_bounds(_lib.ptr(pos), _lib.ptr(pt), _lib.ptr(lt), _lib.ptr(ht), G, n, K,
+                                              _lib.ptr(dist if (dist is not None and dist.numel()) else None), _lib.ptr(worst),
+                                              _lib.ptr(worst_pair), _lib.ptr(n_bad), _lib.stream_ptr()), "agdiff_pair_bounds")
+    return worst, worst_pair, n_bad, dist
+
+
+def clash_scan(pos, radius, ex_ptr, ex_idx, thresh, want_scratch=False):
+    """agdiff_clash_scan on pos [G, n, 3] (float32, contiguous, on the GPU): (min_ratio float32 [G], min_pair int32 [G, 2], n_clash
+    int32 [G]) (+ the call's scratch, int32 [G, S, 4], with want_scratch).  radius [n] finite and > 0; ex_ptr int32 [n + 1] / ex_idx
+    int32 (numpy: `exclusions`) are checked here, on the host, for range, ascending rows and symmetry -- the kernel does not.  More than
+    AGDIFF_MAX_ATOMS_LARGE atoms: AgdiffLimitError."""
+    import torch
+    from .stereo import _device_conformers
+    _device_conformers(pos)
+    G, n = int(pos.shape[0]), int(pos.shape[1])
+    if n == 0:
+        raise ValueError("conformers without atoms")
+    th = float(thresh)
+    if not (th >= 0.0 and np.isfinite(th)):
+        raise ValueError("the clash threshold must be finite and >= 0 (got %r)" % (thresh,))
+    rad = np.array(_host(radius).reshape(-1), dtype=np.float32)
+    if rad.shape[0] != n or not (np.isfinite(rad).all() and (rad > 0).all()):
+        raise ValueError("radius must hold %d finite numbers > 0" % n)
+    ptr, idx = _host(ex_ptr), _host(ex_idx)
+    _check_exclusions(n, ptr, idx)
+    lib = _lib.load()
+    dev = pos.device
+    S = (n + CLASH_SLICE - 1) // CLASH_SLICE
+    scratch = torch.empty((G, S, 4), dtype=torch.int32, device=dev)
+    min_ratio = torch.empty(G, dtype=torch.float32, device=dev)
+    min_pair = torch.empty((G, 2), dtype=torch.int32, device=dev)
+    n_clash = torch.empty(G, dtype=torch.int32, device=dev)
+    rt, pt = torch.from_numpy(rad).to(dev), torch.from_numpy(np.array(ptr)).to(dev)
+    it = torch.from_numpy(np.array(idx)).to(dev) if idx.size else None
+    if G:
+        with torch.cuda.device(dev):
+            _lib.check(lib.agdiff_clash_scan(_lib.ptr(pos), _lib.ptr(rt), _lib.ptr(pt), _lib.ptr(it), G, n, th, _lib.ptr(scratch),
+                                             _lib.ptr(min_ratio), _lib.ptr(min_pair), _lib.ptr(n_clash), _lib.stream_ptr()),
+                       "agdiff_clash_scan")
+    return (min_ratio, min_pair, n_clash, scratch) if want_scratch else (min_ratio, min_pair, n_clash)
+
+
+def _tables(item, bounds, table_kw):
+    """(pairs, lo, hi, radius, ex_ptr, ex_idx) of an item: host work, and every ValueError an item can cause, before any launch"""
+    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    b_idx, b_typ = _bonds_of(item)                    # (an item without bonds: ValueError)
+    if isinstance(bounds, str):
+        if bounds == "table":
+            pairs, lo, hi = bounds_from_table(item, **table_kw)
+        elif bounds == "references":
+            pairs, lo, hi = bounds_from_references(item, **table_kw)
+        else:
+            raise ValueError("bounds must be 'table', 'references' or (pairs, lo, hi) (got %r)" % (bounds,))
+    else:
+        if table_kw:
+            raise ValueError("keyword arguments %s go with bounds='table' or 'references'" % sorted(table_kw))
+        pairs, lo, hi = bounds
+    return (pairs, lo, hi, vdw_radii(item["atom_type"])) + exclusions(n, b_idx, b_typ)
+
+
+def check_geometry(item, bounds="table", clash=0.60, device="cuda", **table_kw):
+    """Both checks over the item's generated conformers (atom_type [n], pos_gen, and its bonds: edge_index + edge_type extended to
+    order 3, or bond_index + bond_type).  bounds: "table" (bounds_from_table; bond_lo / bond_hi as keywords), "references"
+    (bounds_from_references, the item carries pos_ref; slack as a keyword) or (pairs, lo, hi).  clash: the fraction of the van der
+    Waals sum below which a pair not excluded clashes.  Returns a dict of tensors on `device`:
+        valid      bool [G]       n_bad == 0 and n_clash == 0
+        bond_dev   float32 [G]    the worst violation of a bound in Angstrom (+inf: a distance that is not finite)
+        bond_pair  int32 [G, 2]   the atoms of the pair with that violation, -1 when there are no bounded pairs
+        n_bad      int32 [G]      violated pairs
+        clash      float32 [G]    the smallest d / (rvdw_i + rvdw_j) over the pairs more than three bonds apart (+inf: none)
+        clash_pair int32 [G, 2]   the atoms of that pair, -1 when there is none
+        n_clash    int32 [G]      pairs below `clash`"""
+    import torch
+    pairs, lo, hi, radius, ex_ptr, ex_idx = _tables(item, bounds, table_kw)
+    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    pos = _as_conformers(item["pos_gen"], n).to(device).contiguous()
+    worst, worst_pair, n_bad, _ = pair_bounds(pos, pairs, lo, hi)
+    min_ratio, min_pair, n_clash = clash_scan(pos, radius, ex_ptr, ex_idx, clash)
+    pt = torch.from_numpy(np.array(_host(pairs).reshape(-1, 2), dtype=np.int32)).to(pos.device)
+    pt = torch.cat([pt, torch.full((1, 2), -1, dtype=torch.int32, device=pos.device)])      # (row -1 = K: no pair)
+    return {"valid": (n_bad == 0) & (n_clash == 0), "bond_dev": worst, "bond_pair": pt[worst_pair.long()], "n_bad": n_bad,
+            "clash": min_ratio, "clash_pair": min_pair, "n_clash": n_clash}
+
+
+def main(argv=None):
+    """python -m agdiff_amd.validity --samples samples_all.npz --testset test.npz [--refs refs.npz] [--clash 0.6] --out validity.npz
+    Checks every molecule of a finished job (agdiff_amd.driver: `pos_gen_<i>`; the bonds come from the test set, extended to order 3).
+    Writes per molecule `valid_<i>` int8 [G], `bond_dev_<i>` float32 [G], `bond_pair_<i>` int32 [G, 2], `n_bad_<i>` int32 [G],
+    `clash_<i>` float32 [G], `clash_pair_<i>` int32 [G, 2], `n_clash_<i>` int32 [G] (+ `name_<i>`).  --refs (`pos_ref_<i>` [R, n, 3]):
+    the bounds come from the molecule's reference conformers (bounds_from_references) instead of the covalent-radius table."""
+    import argparse
+    from .driver import load_testset
+    ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--samples", required=True)
+    ap.add_argument("--testset", required=True)
+    ap.add_argument("--refs", default=None, help="bounds from these reference conformers instead of the covalent-radius table")
+    ap.add_argument("--clash", type=float, default=0.60, help="fraction of the van der Waals sum below which a pair clashes")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    if not (args.clash >= 0.0 and np.isfinite(args.clash)):
+        ap.error("--clash must be finite and >= 0")
+    zs = np.load(args.samples)
+    zr = np.load(args.refs, allow_pickle=False) if args.refs else None
+    out, mols, confs, invalid, by_bond, by_clash = {}, 0, 0, 0, 0, 0
+    for mol in load_testset(args.testset):
+        i = mol["index"]
+        if "pos_gen_%d" % i not in zs.files:
+            continue
+        item = {"atom_type": mol["atom_type"], "pos_gen": zs["pos_gen_%d" % i], "edge_index": mol["edge_index"],
+                "edge_type": mol["edge_type"]}
+        if zr is not None:
+            if "pos_ref_%d" % i not in zr.files:
+                raise ValueError("--refs: %s has no pos_ref_%d" % (args.refs, i))
+            item["pos_ref"] = zr["pos_ref_%d" % i]
+        res = check_geometry(item, bounds="references" if zr is not None else "table", clash=args.clash, device=args.device)
+        for k, v in res.items():
+            out["%s_%d" % (k, i)] = v.cpu().numpy().astype(np.int8) if k == "valid" else v.cpu().numpy()
+        out["name_%d" % i] = np.str_(mol["name"])
+        bad, hit = res["n_bad"].cpu().numpy() > 0, res["n_clash"].cpu().numpy() > 0
+        mols += 1
+        confs += bad.shape[0]
+        invalid += int((bad | hit).sum())
+        by_bond += int(bad.sum())
+        by_clash += int(hit.sum())
+    np.savez_compressed(args.out, **out)
+    print("%d molecules, %d conformers, %d invalid (%d with a distance out of bounds, %d with a clash)"
+          % (mols, confs, invalid, by_bond, by_clash))
+    return out
+
+
+if __name__ == "__main__":
+    main()

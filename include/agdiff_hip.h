@@ -42,6 +42,7 @@ extern "C" {
 #define AGDIFF_RMSD_MAX_ATOMS 256  /* most (heavy) atoms per conformer in agdiff_rmsd_matrix / agdiff_rmsd_self */
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
 #define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
+#define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
 #define AGDIFF_POLY_MAX_KT 4      /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
 #define AGDIFF_POLY_MAX_SLOTS 16   /* most local edge types with filter polynomials; the first sets that fit stay in LDS next to the
@@ -848,6 +849,45 @@ int agdiff_torsion_angles(const float* pos, const int32_t* quads, int32_t G, int
 int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const int32_t* tmap, const float* w, int32_t R, int32_t G,
                       int32_t Q, int32_t T, int32_t P, float thresh, float* out, float* out_mirror, uint64_t* bits,
                       void* stream);
+
+/* ---- geometry validity -----------------------------------------------------------------------------------------------
+ * A sampled conformer can be finite and still broken: a bond stretched to 2.5 A, two ring systems pushed through each other, a
+ * hydrogen on top of a carbon five bonds away.  Two checks that need the topology only (no force field, no rdkit; the reference
+ * has no counterpart).  The host builds their tables (agdiff_amd/validity.py).  No atomics, deterministic bit for bit.
+ * Both take d = |p_i - p_j| with every coordinate converted to fp64 before the first subtraction.
+ *
+ * agdiff_pair_bounds: distances of K named pairs against [lo, hi].
+ *   pos [G][n][3]
+ *   pairs [K][2] int32, lo [K], hi [K]   atoms of each pair and its bounds in Angstrom (all three may be null when K = 0)
+ *   dist [G][K] or null    d as fp32; NaN for a pair that names an atom outside [0, n), which reads nothing
+ *   worst [G]              max_k v,  v = (float)max(lo - d, d - hi, 0) on the fp32 d as stored, +inf when that d is not finite;
+ *                          0 when K = 0
+ *   worst_pair [G] int32   the lowest k attaining worst; -1 when K = 0
+ *   n_bad [G] int32        the number of pairs with v > 0
+ * One wave per conformer, lanes over the pairs. */
+int agdiff_pair_bounds(const float* pos, const int32_t* pairs, const float* lo, const float* hi, int32_t G, int32_t n, int32_t K,
+                       float* dist /* [G][K] or null */, float* worst /* [G] */, int32_t* worst_pair /* [G] */,
+                       int32_t* n_bad /* [G] */, void* stream);
+
+/* agdiff_clash_scan: every pair i < j of a conformer that is not excluded, against the sum of two radii.
+ *   pos [G][n][3], n <= AGDIFF_MAX_ATOMS_LARGE (else AGDIFF_ERR_LIMIT)
+ *   radius [n]             > 0 and finite (NOT checked here: the caller does)
+ *   ex_ptr [n + 1], ex_idx [ex_ptr[n]] int32   the excluded partners of every atom as a CSR: symmetric, every row strictly
+ *                          ascending, entries in [0, n) (NOT checked here: the caller does).  ex_idx may be null when
+ *                          ex_ptr[n] = 0.
+ *   thresh                 finite and >= 0, else AGDIFF_ERR_ARG
+ *   ratio(i, j) = (float)(d / ((double)radius[i] + (double)radius[j])), 0 when d is not finite in fp64
+ *   scratch [4 G S] int32  S = ceil(n / AGDIFF_CLASH_SLICE); one partial { bits(min ratio), i, j, count } per (g, slice), written
+ *                          by the call
+ *   min_ratio [G]          the smallest ratio; +inf when every pair is excluded or n < 2
+ *   min_pair [G][2] int32  the lowest (i, j) attaining it, i < j, lowest i first then lowest j; (-1, -1) when there is no pair
+ *   n_clash [G] int32      the number of pairs with ratio < thresh, taken on the fp32 ratio
+ * Grid (S, G): a workgroup of AGDIFF_CLASH_SLICE threads owns one slice of atoms i of one conformer and walks the atoms j > i in
+ * LDS tiles, every lane merging its own ascending exclusion row as j ascends (no n x n mask); a second launch of one wave per
+ * conformer reduces the S partials in slice order. */
+int agdiff_clash_scan(const float* pos, const float* radius /* [n], > 0 */, const int32_t* ex_ptr, const int32_t* ex_idx,
+                      int32_t G, int32_t n, float thresh, int32_t* scratch, float* min_ratio /* [G] */,
+                      int32_t* min_pair /* [G][2] */, int32_t* n_clash /* [G] */, void* stream);
 
 #ifdef __cplusplus
 }
