@@ -8,9 +8,36 @@
 // proper rotation as a unit quaternion; reflections are excluded by construction).  lambda_max comes from cyclic
 // Jacobi sweeps in fp64: a few hundred flops per pair, robust for planar / collinear / identical conformers.
 // Latency-bound, tiny next to the sampler: one thread per (reference, generated) pair, conformer tiles staged in LDS.
+//
+// There is ONE copy of each step of that formula: ag_cov_add (S), ag_horn_key (K), ag_jacobi4 (the sweeps, with or without
+// eigenvectors) and ag_pair_msd (the minimum over the mappings, with or without the mirror image).  k_rmsd_matrix<false>,
+// k_rmsd_matrix<true> and k_rmsd_self agree bit for bit because they call that one routine; k_align_conformers runs the same sweeps.
 #include "common.hpp"
 
 namespace {
+
+// each argument summed over the 64 lanes of the wave, in place, in every lane: xor butterfly, offsets 32, 16, ... 1
+template <typename... T>
+__device__ __forceinline__ void ag_wave_sum(T&... x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ((x += __shfl_xor(x, o)), ...);
+}
+template <int N>
+__device__ __forceinline__ void ag_wave_sum(double (&x)[N]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int e = 0; e < N; ++e) x[e] += __shfl_xor(x[e], o);
+}
+
+// every listed atom index lies in [0, n)
+template <typename... I>
+__device__ __forceinline__ bool ag_atoms_in_range(int n, I... a) {
+  return (((unsigned)a < (unsigned)n) && ...);
+}
+
+// neither Inf nor NaN
+__device__ __forceinline__ bool ag_finite(double x) { return fabs(x) <= 1.79769313486231570e308; }
 
 // centred coordinates of the selected atoms, one wave per conformer (centroid in fp64, rounded once):
 // out[c] = { x_0 y_0 z_0 ... x_{m-1} y_{m-1} z_{m-1} | unused }
@@ -23,8 +50,7 @@ __global__ void __launch_bounds__(64) k_center_selected(const float* __restrict_
     const int a = idx[k];
     sx += p[3 * a]; sy += p[3 * a + 1]; sz += p[3 * a + 2];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+  ag_wave_sum(sx, sy, sz);
   const double cx = sx / m, cy = sy / m, cz = sz / m;
   float* o = out + (size_t)c * (3 * m + 1);
   for (int k = lane; k < m; k += 64) {
@@ -34,9 +60,30 @@ __global__ void __launch_bounds__(64) k_center_selected(const float* __restrict_
   if (lane == 0) o[3 * m] = 0.0f;
 }
 
-// largest eigenvalue of the symmetric 4x4 matrix with upper triangle k[0..9] = (00 01 02 03 11 12 13 22 23 33)
-__device__ double ag_lambda_max4(const double (&k)[10]) {
+// cross-covariance of one atom pair: S += x y^T, row-major
+__device__ __forceinline__ void ag_cov_add(double (&S)[9], double x0, double x1, double x2, double y0, double y1, double y2) {
+  S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
+  S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
+  S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
+}
+
+// Horn's key matrix of the cross-covariance S: the upper triangle K[0..9] = (00 01 02 03 11 12 13 22 23 33) of a symmetric 4x4
+__device__ __forceinline__ void ag_horn_key(const double (&S)[9], double (&K)[10]) {
+  const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+  K[0] = Sxx + Syy + Szz; K[1] = Syz - Szy; K[2] = Szx - Sxz; K[3] = Sxy - Syx;
+  K[4] = Sxx - Syy - Szz; K[5] = Sxy + Syx; K[6] = Szx + Sxz;
+  K[7] = -Sxx + Syy - Szz; K[8] = Syz + Szy;
+  K[9] = -Sxx - Syy + Szz;
+}
+
+// cyclic Jacobi sweeps over the symmetric 4x4 matrix with upper triangle k (12 at most, until the off-diagonal mass is gone):
+// d = the diagonal that is left, the eigenvalues in no particular order; kVectors: vectors = the accumulated rotations, column j
+// the eigenvector of d[j] (not touched otherwise).  A and V are locals and the results are copied out at the end: a matrix
+// handed in by reference stays in memory until this is inlined, and the unrolled sweeps then compile to other code.
+template <bool kVectors>
+__device__ void ag_jacobi4(const double (&k)[10], double (&d)[4], double (*vectors)[4] = nullptr) {
   double A[4][4] = {{k[0], k[1], k[2], k[3]}, {k[1], k[4], k[5], k[6]}, {k[2], k[5], k[7], k[8]}, {k[3], k[6], k[8], k[9]}};
+  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
   for (int sweep = 0; sweep < 12; ++sweep) {
     double off = 0.0;
 #pragma unroll
@@ -58,6 +105,11 @@ __device__ double ag_lambda_max4(const double (&k)[10]) {
           const double arp = A[r][p], arq = A[r][q];
           A[r][p] = c * arp - s * arq;
           A[r][q] = s * arp + c * arq;
+          if constexpr (kVectors) {
+            const double vrp = V[r][p], vrq = V[r][q];
+            V[r][p] = c * vrp - s * vrq;
+            V[r][q] = s * vrp + c * vrq;
+          }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {           // rows p, q
@@ -68,29 +120,23 @@ __device__ double ag_lambda_max4(const double (&k)[10]) {
       }
     }
   }
-  return fmax(fmax(A[0][0], A[1][1]), fmax(A[2][2], A[3][3]));
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    d[r] = A[r][r];
+    if constexpr (kVectors) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) vectors[r][c] = V[r][c];
+    }
+  }
 }
 
-extern __shared__ float ag_eval_smem[];
-
-// 16 x 16 pairs per workgroup: thread (ty, tx) = (reference ty, generated tx) of the tile
-__global__ void __launch_bounds__(256) k_rmsd_matrix(const float* __restrict__ cref, const float* __restrict__ cgen,
-                                                     const int32_t* __restrict__ perms, int R, int G, int m, int P,
-                                                     float* __restrict__ out) {
-  const int stride = 3 * m + 1;
-  float* sref = ag_eval_smem;
-  float* sgen = ag_eval_smem + 16 * stride;
-  const int j0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
-  for (int t = threadIdx.x; t < 16 * stride; t += 256) {
-    const int c = t / stride, o = t % stride;
-    sref[t] = (j0 + c < R) ? cref[(size_t)(j0 + c) * stride + o] : 0.0f;
-    sgen[t] = (i0 + c < G) ? cgen[(size_t)(i0 + c) * stride + o] : 0.0f;
-  }
-  __syncthreads();
-  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-  if (j0 + ty >= R || i0 + tx >= G) return;
-  const float* y = sref + ty * stride;      // reference
-  const float* x = sgen + tx * stride;      // generated (probe)
+// Mean-square deviation of the conformers x and y (centred, m atoms, 3 m floats each) after the best proper rotation, minimised
+// over the P atom mappings of y (perms == nullptr: the identity alone).  kMirror: best_mirror = the same for x inverted through
+// its centroid.  K is linear in S and the inversion turns S into -S, so lambda_max(K(-S)) = -lambda_min(K(S)): the best fit of
+// the mirror image comes out of the diagonalisation the proper fit already pays for.
+template <bool kMirror>
+__device__ __forceinline__ void ag_pair_msd(const float* x, const float* y, const int32_t* perms, int m, int P, double& best,
+                                            double& best_mirror) {
   // squared norms from the SAME rounded coordinates the cross-covariance uses, in fp64: near RMSD = 0 the difference
   // |X|^2 + |Y|^2 - 2 lambda cancels to ~1e-16 relative only if both sides see identical inputs
   double gsum = 0.0;
@@ -99,7 +145,8 @@ __global__ void __launch_bounds__(256) k_rmsd_matrix(const float* __restrict__ c
     const double y0 = y[3 * k], y1 = y[3 * k + 1], y2 = y[3 * k + 2];
     gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (y0 * y0 + y1 * y1 + y2 * y2);
   }
-  double best = 1e300;
+  best = 1e300;
+  if constexpr (kMirror) best_mirror = 1e300;
   for (int p = 0; p < (perms ? P : 1); ++p) {
     const int32_t* pm = perms ? perms + (size_t)p * m : nullptr;
     double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -107,19 +154,50 @@ __global__ void __launch_bounds__(256) k_rmsd_matrix(const float* __restrict__ c
       const int kr = pm ? pm[k] : k;
       const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
       const double y0 = y[3 * kr], y1 = y[3 * kr + 1], y2 = y[3 * kr + 2];
-      S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
-      S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
-      S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
+      ag_cov_add(S, x0, x1, x2, y0, y1, y2);
     }
-    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-    const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
-                          Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
-                          -Sxx + Syy - Szz, Syz + Szy,
-                          -Sxx - Syy + Szz};
-    const double msd = (gsum - 2.0 * ag_lambda_max4(K)) / m;
-    best = fmin(best, msd);
+    double K[10], d[4];
+    ag_horn_key(S, K);
+    ag_jacobi4<false>(K, d);
+    best = fmin(best, (gsum - 2.0 * fmax(fmax(d[0], d[1]), fmax(d[2], d[3]))) / m);
+    if constexpr (kMirror) best_mirror = fmin(best_mirror, (gsum + 2.0 * fmin(fmin(d[0], d[1]), fmin(d[2], d[3]))) / m);
   }
-  out[(size_t)(j0 + ty) * G + i0 + tx] = (float)sqrt(fmax(best, 0.0));
+}
+
+extern __shared__ float ag_eval_smem[];
+
+// two LDS tiles of 16 centred conformers each (`stride` floats per conformer): a0 .. a0 + 15 of the na conformers of a, the
+// same for b; zeros past the end.  The caller synchronises.
+__device__ __forceinline__ void ag_stage_tiles(float* sa, const float* a, int a0, int na, float* sb, const float* b, int b0, int nb,
+                                               int stride) {
+  for (int t = threadIdx.x; t < 16 * stride; t += 256) {
+    const int c = t / stride, o = t % stride;
+    sa[t] = (a0 + c < na) ? a[(size_t)(a0 + c) * stride + o] : 0.0f;
+    sb[t] = (b0 + c < nb) ? b[(size_t)(b0 + c) * stride + o] : 0.0f;
+  }
+}
+
+// 16 x 16 pairs per workgroup: thread (ty, tx) = (reference ty, generated tx) of the tile.  kMirror: out_mirror = the same quantity
+// for the generated conformer inverted through its centroid, minimised over the same mappings (out_mirror is not read otherwise)
+template <bool kMirror>
+__global__ void __launch_bounds__(256) k_rmsd_matrix(const float* __restrict__ cref, const float* __restrict__ cgen,
+                                                     const int32_t* __restrict__ perms, int R, int G, int m, int P,
+                                                     float* __restrict__ out, float* __restrict__ out_mirror) {
+  const int stride = 3 * m + 1;
+  float* sref = ag_eval_smem;
+  float* sgen = ag_eval_smem + 16 * stride;
+  const int j0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
+  ag_stage_tiles(sref, cref, j0, R, sgen, cgen, i0, G, stride);
+  __syncthreads();
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  if (j0 + ty >= R || i0 + tx >= G) return;
+  double best, best_mirror;
+  const float* y = sref + ty * stride;      // reference
+  const float* x = sgen + tx * stride;      // generated (probe)
+  ag_pair_msd<kMirror>(x, y, perms, m, P, best, best_mirror);
+  const size_t at = (size_t)(j0 + ty) * G + i0 + tx;
+  out[at] = (float)sqrt(fmax(best, 0.0));
+  if constexpr (kMirror) out_mirror[at] = (float)sqrt(fmax(best_mirror, 0.0));
 }
 
 // one wave per row (blockIdx.y == 0) or per column (== 1)
@@ -154,8 +232,8 @@ __device__ __forceinline__ void ag_triangle_tile(long long b, int T, int& ti, in
   tj = r + (int)(b - ((long long)r * T - (long long)r * (r - 1) / 2));
 }
 
-// 16 x 16 pairs per workgroup, upper-triangular tiles only: thread (ty, tx) = (conformer i0 + ty, conformer j0 + tx), the pair
-// arithmetic of k_rmsd_matrix with x = conformer i, y = conformer j, computed once for i < j and mirrored through LDS.
+// 16 x 16 pairs per workgroup, upper-triangular tiles only: thread (ty, tx) = (conformer i0 + ty, conformer j0 + tx),
+// ag_pair_msd with x = conformer i, y = conformer j, computed once for i < j and mirrored through LDS.
 // bits: rows of 16-bit pieces (piece w of row i = columns 16 w .. 16 w + 15), row pitch `pitch` bytes; every piece has ONE
 // writer, the tile that owns it -- (ti, tj) writes piece tj of its rows i0.. and piece ti of the rows j0.., a diagonal tile
 // its own pieces once and the zero pieces that pad its rows up to the pitch.
@@ -171,43 +249,14 @@ __global__ void __launch_bounds__(256) k_rmsd_self(const float* __restrict__ cen
   ag_triangle_tile((long long)blockIdx.x, T, ti, tj);
   const int i0 = ti * 16, j0 = tj * 16;
   const bool diag = ti == tj;
-  for (int t = threadIdx.x; t < 16 * stride; t += 256) {
-    const int c = t / stride, o = t % stride;
-    srow[t] = (i0 + c < G) ? cen[(size_t)(i0 + c) * stride + o] : 0.0f;
-    scol[t] = (j0 + c < G) ? cen[(size_t)(j0 + c) * stride + o] : 0.0f;
-  }
+  ag_stage_tiles(srow, cen, i0, G, scol, cen, j0, G, stride);
   __syncthreads();
   const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
   const bool valid = i0 + ty < G && j0 + tx < G;
   float v = 0.0f;
   if (valid && (!diag || ty < tx)) {
-    const float* x = srow + ty * stride;
-    const float* y = scol + tx * stride;
-    double gsum = 0.0;
-    for (int k = 0; k < m; ++k) {
-      const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
-      const double y0 = y[3 * k], y1 = y[3 * k + 1], y2 = y[3 * k + 2];
-      gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (y0 * y0 + y1 * y1 + y2 * y2);
-    }
-    double best = 1e300;
-    for (int p = 0; p < (perms ? P : 1); ++p) {
-      const int32_t* pm = perms ? perms + (size_t)p * m : nullptr;
-      double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      for (int k = 0; k < m; ++k) {
-        const int kr = pm ? pm[k] : k;
-        const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
-        const double y0 = y[3 * kr], y1 = y[3 * kr + 1], y2 = y[3 * kr + 2];
-        S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
-        S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
-        S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
-      }
-      const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-      const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
-                            Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
-                            -Sxx + Syy - Szz, Syz + Szy,
-                            -Sxx - Syy + Szz};
-      best = fmin(best, (gsum - 2.0 * ag_lambda_max4(K)) / m);
-    }
+    double best, unused;
+    ag_pair_msd<false>(srow + ty * stride, scol + tx * stride, perms, m, P, best, unused);
     v = (float)sqrt(fmax(best, 0.0));
   }
   // the threshold is taken on the fp32 value as stored, so that bits == (out <= thresh) exactly
@@ -294,57 +343,22 @@ __global__ void __launch_bounds__(64) k_leader_prune(const uint64_t* __restrict_
     count[i] = s_count[i];
   }
   int k = __popcll(kept);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o);
+  ag_wave_sum(k);
   if (lane == 0) n_kept[0] = k;
 }
 
-// eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_lambda_max4) by the same cyclic Jacobi sweeps, with
-// the rotations accumulated: returns the largest eigenvalue and its unit eigenvector q
+// eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
+// accumulated: returns the largest eigenvalue and its unit eigenvector q
 __device__ double ag_eigvec_max4(const double (&k)[10], double (&q)[4]) {
-  double A[4][4] = {{k[0], k[1], k[2], k[3]}, {k[1], k[4], k[5], k[6]}, {k[2], k[5], k[7], k[8]}, {k[3], k[6], k[8], k[9]}};
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    double off = 0.0;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int q_ = p + 1; q_ < 4; ++q_) off += A[p][q_] * A[p][q_];
-    if (off < 1e-30) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q_ = p + 1; q_ < 4; ++q_) {
-        const double apq = A[p][q_];
-        if (apq == 0.0) continue;
-        const double theta = (A[q_][q_] - A[p][p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const double arp = A[r][p], arq = A[r][q_];
-          A[r][p] = c * arp - s * arq;
-          A[r][q_] = s * arp + c * arq;
-          const double vrp = V[r][p], vrq = V[r][q_];
-          V[r][p] = c * vrp - s * vrq;
-          V[r][q_] = s * vrp + c * vrq;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const double apr = A[p][r], aqr = A[q_][r];
-          A[p][r] = c * apr - s * aqr;
-          A[q_][r] = s * apr + c * aqr;
-        }
-      }
-    }
-  }
-  double lam = A[0][0];
+  double d[4], V[4][4];
+  ag_jacobi4<true>(k, d, V);
+  double lam = d[0];
 #pragma unroll
   for (int r = 0; r < 4; ++r) q[r] = V[r][0];
 #pragma unroll
   for (int j = 1; j < 4; ++j) {
-    const bool up = A[j][j] > lam;
-    lam = up ? A[j][j] : lam;
+    const bool up = d[j] > lam;
+    lam = up ? d[j] : lam;
 #pragma unroll
     for (int r = 0; r < 4; ++r) q[r] = up ? V[r][j] : q[r];
   }
@@ -368,10 +382,7 @@ __global__ void __launch_bounds__(64) k_align_conformers(const float* __restrict
     c[0] += p[3 * a]; c[1] += p[3 * a + 1]; c[2] += p[3 * a + 2];
     c[3] += target[3 * a]; c[4] += target[3 * a + 1]; c[5] += target[3 * a + 2];
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int e = 0; e < 6; ++e) c[e] += __shfl_xor(c[e], o);
+  ag_wave_sum(c);
 #pragma unroll
   for (int e = 0; e < 6; ++e) c[e] /= m;
   double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -379,20 +390,11 @@ __global__ void __launch_bounds__(64) k_align_conformers(const float* __restrict
     const int a = idx[k];
     const double x0 = p[3 * a] - c[0], x1 = p[3 * a + 1] - c[1], x2 = p[3 * a + 2] - c[2];
     const double y0 = target[3 * a] - c[3], y1 = target[3 * a + 1] - c[4], y2 = target[3 * a + 2] - c[5];
-    S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
-    S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
-    S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
+    ag_cov_add(S, x0, x1, x2, y0, y1, y2);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int e = 0; e < 9; ++e) S[e] += __shfl_xor(S[e], o);
-  const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-  const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
-                        Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
-                        -Sxx + Syy - Szz, Syz + Szy,
-                        -Sxx - Syy + Szz};
-  double q[4];
+  ag_wave_sum(S);
+  double K[10], q[4];
+  ag_horn_key(S, K);
   ag_eigvec_max4(K, q);
   const double q0 = q[0], qx = q[1], qy = q[2], qz = q[3];
   const double R[9] = {q0 * q0 + qx * qx - qy * qy - qz * qz, 2.0 * (qx * qy - q0 * qz), 2.0 * (qx * qz + q0 * qy),
@@ -415,106 +417,12 @@ __global__ void __launch_bounds__(64) k_align_conformers(const float* __restrict
     const double e2 = (double)(float)(R[6] * x0 + R[7] * x1 + R[8] * x2 + c[5]) - target[3 * a + 2];
     d2 += e0 * e0 + e1 * e1 + e2 * e2;
   }
-#pragma unroll
-  for (int o_ = 32; o_ > 0; o_ >>= 1) d2 += __shfl_xor(d2, o_);
+  ag_wave_sum(d2);
   if (lane == 0) rmsd[g] = (float)sqrt(d2 / m);
 }
 
 // ---- handedness: the sampler cannot tell a molecule from its mirror image (the score network sees distances only), so the RMSD
 // to the mirror image, the parity of the stereocentres and the inversion of a wrong-handed conformer live here ----------------
-
-// ag_lambda_max4's sweeps, statement for statement, returning BOTH extreme diagonal entries.  K is linear in the cross-covariance
-// S and inverting one conformer through its centroid turns S into -S, so lambda_max(K(-S)) = -lambda_min(K(S)): the best fit of
-// the mirror image comes out of the diagonalisation the proper fit already pays for.
-__device__ void ag_lambda_ext4(const double (&k)[10], double& lmax, double& lmin) {
-  double A[4][4] = {{k[0], k[1], k[2], k[3]}, {k[1], k[4], k[5], k[6]}, {k[2], k[5], k[7], k[8]}, {k[3], k[6], k[8], k[9]}};
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    double off = 0.0;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
-    if (off < 1e-30) break;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        const double apq = A[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {           // columns p, q
-          const double arp = A[r][p], arq = A[r][q];
-          A[r][p] = c * arp - s * arq;
-          A[r][q] = s * arp + c * arq;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {           // rows p, q
-          const double apr = A[p][r], aqr = A[q][r];
-          A[p][r] = c * apr - s * aqr;
-          A[q][r] = s * apr + c * aqr;
-        }
-      }
-    }
-  }
-  lmax = fmax(fmax(A[0][0], A[1][1]), fmax(A[2][2], A[3][3]));
-  lmin = fmin(fmin(A[0][0], A[1][1]), fmin(A[2][2], A[3][3]));
-}
-
-// k_rmsd_matrix with a second result: out_proper is that kernel's value, out_mirror the same quantity for the generated
-// conformer inverted through its centroid, minimised over the same mappings
-__global__ void __launch_bounds__(256) k_rmsd_matrix_hands(const float* __restrict__ cref, const float* __restrict__ cgen,
-                                                           const int32_t* __restrict__ perms, int R, int G, int m, int P,
-                                                           float* __restrict__ out_proper, float* __restrict__ out_mirror) {
-  const int stride = 3 * m + 1;
-  float* sref = ag_eval_smem;
-  float* sgen = ag_eval_smem + 16 * stride;
-  const int j0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
-  for (int t = threadIdx.x; t < 16 * stride; t += 256) {
-    const int c = t / stride, o = t % stride;
-    sref[t] = (j0 + c < R) ? cref[(size_t)(j0 + c) * stride + o] : 0.0f;
-    sgen[t] = (i0 + c < G) ? cgen[(size_t)(i0 + c) * stride + o] : 0.0f;
-  }
-  __syncthreads();
-  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-  if (j0 + ty >= R || i0 + tx >= G) return;
-  const float* y = sref + ty * stride;      // reference
-  const float* x = sgen + tx * stride;      // generated (probe)
-  double gsum = 0.0;
-  for (int k = 0; k < m; ++k) {
-    const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
-    const double y0 = y[3 * k], y1 = y[3 * k + 1], y2 = y[3 * k + 2];
-    gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (y0 * y0 + y1 * y1 + y2 * y2);
-  }
-  double best = 1e300, best_mirror = 1e300;
-  for (int p = 0; p < (perms ? P : 1); ++p) {
-    const int32_t* pm = perms ? perms + (size_t)p * m : nullptr;
-    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < m; ++k) {
-      const int kr = pm ? pm[k] : k;
-      const double x0 = x[3 * k], x1 = x[3 * k + 1], x2 = x[3 * k + 2];
-      const double y0 = y[3 * kr], y1 = y[3 * kr + 1], y2 = y[3 * kr + 2];
-      S[0] += x0 * y0; S[1] += x0 * y1; S[2] += x0 * y2;
-      S[3] += x1 * y0; S[4] += x1 * y1; S[5] += x1 * y2;
-      S[6] += x2 * y0; S[7] += x2 * y1; S[8] += x2 * y2;
-    }
-    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-    const double K[10] = {Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx,
-                          Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz,
-                          -Sxx + Syy - Szz, Syz + Szy,
-                          -Sxx - Syy + Szz};
-    double lmax, lmin;
-    ag_lambda_ext4(K, lmax, lmin);
-    const double msd = (gsum - 2.0 * lmax) / m;
-    best = fmin(best, msd);
-    best_mirror = fmin(best_mirror, (gsum + 2.0 * lmin) / m);
-  }
-  const size_t at = (size_t)(j0 + ty) * G + i0 + tx;
-  out_proper[at] = (float)sqrt(fmax(best, 0.0));
-  out_mirror[at] = (float)sqrt(fmax(best_mirror, 0.0));
-}
 
 // one wave per conformer, lanes over the stereocentres (strided past 64): the signed volume of each centre's four neighbours in
 // fp64, its sign against the target, and the three "some checked centre ..." facts combined across the wave by ballot.
@@ -528,7 +436,7 @@ __global__ void __launch_bounds__(64) k_chiral_verdict(const float* __restrict__
   for (int c = lane; c < C; c += 64) {
     const int a = quads[4 * c], b = quads[4 * c + 1], d = quads[4 * c + 2], e = quads[4 * c + 3];
     double v = 0.0;
-    if ((unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n && (unsigned)d < (unsigned)n && (unsigned)e < (unsigned)n) {
+    if (ag_atoms_in_range(n, a, b, d, e)) {
       const double ax = p[3 * a], ay = p[3 * a + 1], az = p[3 * a + 2];
       const double ux = p[3 * b] - ax, uy = p[3 * b + 1] - ay, uz = p[3 * b + 2] - az;
       const double vx = p[3 * d] - ax, vy = p[3 * d + 1] - ay, vz = p[3 * d + 2] - az;
@@ -556,8 +464,7 @@ __global__ void __launch_bounds__(64) k_mirror_conformers(float* __restrict__ po
   float* p = pos + (size_t)g * n * 3;
   double sx = 0.0, sy = 0.0, sz = 0.0;
   for (int a = lane; a < n; a += 64) { sx += p[3 * a]; sy += p[3 * a + 1]; sz += p[3 * a + 2]; }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); sz += __shfl_xor(sz, o); }
+  ag_wave_sum(sx, sy, sz);
   const double cx2 = 2.0 * (sx / n), cy2 = 2.0 * (sy / n), cz2 = 2.0 * (sz / n);
   for (int a = lane; a < n; a += 64) {
     p[3 * a] = (float)(cx2 - (double)p[3 * a]);
@@ -579,7 +486,7 @@ __global__ void __launch_bounds__(64) k_torsion_angles(const float* __restrict__
   for (int c = lane; c < Q; c += 64) {
     const int a = quads[4 * c], u = quads[4 * c + 1], v = quads[4 * c + 2], b = quads[4 * c + 3];
     double theta = (double)NAN;
-    if ((unsigned)a < (unsigned)n && (unsigned)u < (unsigned)n && (unsigned)v < (unsigned)n && (unsigned)b < (unsigned)n) {
+    if (ag_atoms_in_range(n, a, u, v, b)) {
       const double ax = p[3 * a], ay = p[3 * a + 1], az = p[3 * a + 2];
       const double ux = p[3 * u], uy = p[3 * u + 1], uz = p[3 * u + 2];
       const double vx = p[3 * v], vy = p[3 * v + 1], vz = p[3 * v + 2];
@@ -594,9 +501,8 @@ __global__ void __launch_bounds__(64) k_torsion_angles(const float* __restrict__
       // them reaches n1sq or n2sq or both of y and x below)
       const double y = sqrt(b2x * b2x + b2y * b2y + b2z * b2z) * (b1x * n2x + b1y * n2y + b1z * n2z);
       const double x = n1x * n2x + n1y * n2y + n1z * n2z;
-      const double lim = 1.79769313486231570e308;
-      const bool finite = fabs(ax) <= lim && fabs(ay) <= lim && fabs(az) <= lim && fabs(ux) <= lim && fabs(uy) <= lim && fabs(uz) <= lim &&
-                          fabs(vx) <= lim && fabs(vy) <= lim && fabs(vz) <= lim && fabs(bx) <= lim && fabs(by) <= lim && fabs(bz) <= lim;
+      const bool finite = ag_finite(ax) && ag_finite(ay) && ag_finite(az) && ag_finite(ux) && ag_finite(uy) && ag_finite(uz) &&
+                          ag_finite(vx) && ag_finite(vy) && ag_finite(vz) && ag_finite(bx) && ag_finite(by) && ag_finite(bz);
       if (finite && n1sq > 0.0 && n2sq > 0.0) theta = atan2(y, x);
     }
     out[(size_t)g * Q + c] = (float)theta;
@@ -700,7 +606,7 @@ __global__ void __launch_bounds__(64) k_pair_bounds(const float* __restrict__ po
   for (int k = lane; k < K; k += 64) {
     const int a = pairs[2 * k], b = pairs[2 * k + 1];
     float d = NAN;
-    if ((unsigned)a < (unsigned)n && (unsigned)b < (unsigned)n) d = (float)ag_pair_dist(p, a, b);
+    if (ag_atoms_in_range(n, a, b)) d = (float)ag_pair_dist(p, a, b);
     if (dist) dist[(size_t)g * K + k] = d;
     float v = INFINITY;
     if (fabsf(d) <= 3.40282347e38f) v = (float)fmax(fmax((double)lo[k] - (double)d, (double)d - (double)hi[k]), 0.0);
@@ -848,9 +754,14 @@ __global__ void __launch_bounds__(64) k_clash_finish(const int32_t* __restrict__
 
 }  // namespace
 
-extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
-                                  int32_t R, int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out,
-                                  void* stream) {
+// bytes per row of a threshold bit-matrix of `columns` columns: 16-bit pieces, rounded up to 8 bytes
+static int ag_bits_pitch(int columns) { return ((columns + 15) / 16 * 2 + 7) / 8 * 8; }
+
+// agdiff_rmsd_matrix (out_mirror unused) and agdiff_rmsd_matrix_hands: the shared argument checks, both centring launches and
+// the matrix kernel
+template <bool kMirror>
+static int ag_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms, int32_t R,
+                          int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out, float* out_mirror, void* stream) {
   if (!pos_ref || !pos_gen || !atom_idx || !scratch || !out || R < 0 || G < 0 || n <= 0 || m <= 0 || m > n || (perms && P <= 0))
     return AGDIFF_ERR_ARG;
   if (m > AGDIFF_RMSD_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
@@ -863,12 +774,20 @@ extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, co
   k_center_selected<<<dim3((unsigned)G), dim3(64), 0, st>>>(pos_gen, atom_idx, n, m, cgen);
   AG_CHECK_LAUNCH();
   const size_t smem = (size_t)2 * 16 * (3 * m + 1) * sizeof(float);
-  static std::atomic<uint64_t> attr_done{0};
-  if (smem > 48 * 1024 && !ag_allow_big_lds(attr_done, (size_t)2 * 16 * (3 * AGDIFF_RMSD_MAX_ATOMS + 1) * sizeof(float), k_rmsd_matrix))
+  static std::atomic<uint64_t> attr_done{0};        // (one per instantiation: ag_allow_big_lds records it per kernel function)
+  if (smem > 48 * 1024 &&
+      !ag_allow_big_lds(attr_done, (size_t)2 * 16 * (3 * AGDIFF_RMSD_MAX_ATOMS + 1) * sizeof(float), k_rmsd_matrix<kMirror>))
     return AGDIFF_ERR_LAUNCH;
-  k_rmsd_matrix<<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem, st>>>(cref, cgen, perms, R, G, m, P, out);
+  k_rmsd_matrix<kMirror><<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem, st>>>(cref, cgen, perms, R, G, m, P,
+                                                                                                            out, out_mirror);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
+}
+
+extern "C" int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
+                                  int32_t R, int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out,
+                                  void* stream) {
+  return ag_rmsd_matrix<false>(pos_ref, pos_gen, atom_idx, perms, R, G, n, m, P, scratch, out, nullptr, stream);
 }
 
 extern "C" int agdiff_matrix_minima(const float* mat, int32_t R, int32_t G, float* row_min, float* col_min, void* stream) {
@@ -894,8 +813,8 @@ extern "C" int agdiff_rmsd_self(const float* pos, const int32_t* atom_idx, const
   const auto smem_for = [](int mm) { return ((size_t)2 * 16 * (3 * mm + 1) + 2 * 16 * 17) * sizeof(float); };
   static std::atomic<uint64_t> attr_done{0};
   if (smem_for(m) > 48 * 1024 && !ag_allow_big_lds(attr_done, smem_for(AGDIFF_RMSD_MAX_ATOMS), k_rmsd_self)) return AGDIFF_ERR_LAUNCH;
-  const int pitch = (int)((T * 2 + 7) / 8 * 8);
-  k_rmsd_self<<<dim3((unsigned)tiles), dim3(256), smem_for(m), st>>>(scratch, perms, G, m, P, (int)T, thresh, out, (uint16_t*)bits, pitch);
+  k_rmsd_self<<<dim3((unsigned)tiles), dim3(256), smem_for(m), st>>>(scratch, perms, G, m, P, (int)T, thresh, out, (uint16_t*)bits,
+                                                                           ag_bits_pitch(G));
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
@@ -904,7 +823,7 @@ extern "C" int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* kee
                                    void* stream) {
   if (!bits || !keep || !leader || !count || !n_kept || G < 0 || ((uintptr_t)bits & 7)) return AGDIFF_ERR_ARG;
   if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
-  const int words = (((G + 15) / 16) * 2 + 7) / 8;        // 64-bit words per row = the row pitch of agdiff_rmsd_self / 8
+  const int words = ag_bits_pitch(G) / 8;                 // 64-bit words per row
   k_leader_prune<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(bits, G, words, keep, leader, count, n_kept);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
@@ -922,27 +841,8 @@ extern "C" int agdiff_align_conformers(const float* pos, const int32_t* atom_idx
 extern "C" int agdiff_rmsd_matrix_hands(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
                                         int32_t R, int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out_proper,
                                         float* out_mirror, void* stream) {
-  if (!pos_ref || !pos_gen || !atom_idx || !scratch || !out_proper || !out_mirror || out_proper == out_mirror || R < 0 || G < 0 ||
-      n <= 0 || m <= 0 || m > n || (perms && P <= 0))
-    return AGDIFF_ERR_ARG;
-  if (m > AGDIFF_RMSD_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
-  if (R == 0 || G == 0) return AGDIFF_OK;
-  hipStream_t st = (hipStream_t)stream;
-  float* cref = scratch;
-  float* cgen = scratch + (size_t)R * (3 * m + 1);
-  k_center_selected<<<dim3((unsigned)R), dim3(64), 0, st>>>(pos_ref, atom_idx, n, m, cref);
-  AG_CHECK_LAUNCH();
-  k_center_selected<<<dim3((unsigned)G), dim3(64), 0, st>>>(pos_gen, atom_idx, n, m, cgen);
-  AG_CHECK_LAUNCH();
-  const size_t smem = (size_t)2 * 16 * (3 * m + 1) * sizeof(float);
-  static std::atomic<uint64_t> attr_done{0};
-  if (smem > 48 * 1024 &&
-      !ag_allow_big_lds(attr_done, (size_t)2 * 16 * (3 * AGDIFF_RMSD_MAX_ATOMS + 1) * sizeof(float), k_rmsd_matrix_hands))
-    return AGDIFF_ERR_LAUNCH;
-  k_rmsd_matrix_hands<<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem, st>>>(cref, cgen, perms, R, G, m, P,
-                                                                                                          out_proper, out_mirror);
-  AG_CHECK_LAUNCH();
-  return AGDIFF_OK;
+  if (!out_mirror || out_proper == out_mirror) return AGDIFF_ERR_ARG;
+  return ag_rmsd_matrix<true>(pos_ref, pos_gen, atom_idx, perms, R, G, n, m, P, scratch, out_proper, out_mirror, stream);
 }
 
 extern "C" int agdiff_chiral_verdict(const float* pos, const int32_t* quads, const int8_t* target, int32_t G, int32_t n, int32_t C,
@@ -981,10 +881,8 @@ extern "C" int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const i
   const auto smem_for = [](int q) { return (size_t)2 * 16 * (q | 1) * sizeof(float); };
   static std::atomic<uint64_t> attr_done{0};
   if (smem_for(Q) > 48 * 1024 && !ag_allow_big_lds(attr_done, smem_for(AGDIFF_TFD_MAX_COLUMNS), k_tfd_matrix)) return AGDIFF_ERR_LAUNCH;
-  const int tiles_g = (G + 15) / 16;
-  const int pitch = (tiles_g * 2 + 7) / 8 * 8;
-  k_tfd_matrix<<<dim3((unsigned)tiles_g, (unsigned)((R + 15) / 16)), dim3(256), smem_for(Q), (hipStream_t)stream>>>(
-      ang_x, ang_y, tmap, w, R, G, Q, T, P, thresh, out, out_mirror, (uint16_t*)bits, pitch);
+  k_tfd_matrix<<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem_for(Q), (hipStream_t)stream>>>(
+      ang_x, ang_y, tmap, w, R, G, Q, T, P, thresh, out, out_mirror, (uint16_t*)bits, ag_bits_pitch(G));
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -19,7 +19,7 @@ along in the alignment.
 import numpy as np
 
 from . import _lib
-from .evaluation import _as_conformers, selection_of
+from .evaluation import _as_conformers, selection_of, selection_on_device
 
 MAX_CONFS = _lib.DEFINES["AGDIFF_PRUNE_MAX_CONFS"]
 
@@ -40,14 +40,10 @@ def _self_rmsd(item, device, threshold=None, want_out=True):
     """(gen [G, n, 3] on the device, heavy index tensor, out [G, G] or None, bits int64 [G, pitch / 8] or None)"""
     import torch
     lib = _lib.load()
-    at, heavy, pa = selection_of(item)
-    n, m = at.shape[0], int(heavy.size)
+    at, idx, P, pt = selection_on_device(item, device)
+    n, m = at.shape[0], idx.shape[0]
     gen = _as_conformers(item["pos_gen"], n).to(device).contiguous()
     G = gen.shape[0]
-    idx = torch.from_numpy(heavy).to(device)
-    P, pt = 0, None
-    if pa is not None:
-        P, pt = pa.shape[0], torch.from_numpy(pa).to(device)
     out = torch.empty((G, G), dtype=torch.float32, device=device) if want_out else None
     bits = None
     if threshold is not None:

@@ -155,6 +155,17 @@ def selection_of(data):
     return at, heavy, pa
 
 
+def selection_on_device(data, device):
+    """selection_of(data) as the RMSD entry points take it: (atom_type [n], heavy-atom index tensor int32 [m], P, mappings tensor
+    int32 [P, m]) on `device`; (..., 0, None) = the identity only."""
+    import torch
+    at, heavy, pa = selection_of(data)
+    idx = torch.from_numpy(heavy).to(device)
+    if pa is None:
+        return at, idx, 0, None
+    return at, idx, pa.shape[0], torch.from_numpy(pa).to(device)
+
+
 def get_rmsd_confusion_matrix(data, useFF=False, device="cuda", hands=False):
     """covmat.py:16-35.  Returns a float32 torch tensor [num_ref, num_gen] on `device`.
     hands=True: (proper, mirror) -- `proper` is that matrix bit for bit, `mirror` the same quantity for every generated conformer's
@@ -167,26 +178,18 @@ def get_rmsd_confusion_matrix(data, useFF=False, device="cuda", hands=False):
     n = np.asarray(data["atom_type"]).reshape(-1).shape[0]
     ref = _as_conformers(data["pos_ref"], n).to(device).contiguous()
     gen = _as_conformers(data["pos_gen"], n).to(device).contiguous()
-    _, heavy, pa = selection_of(data)
-    m = int(heavy.size)
-    idx = torch.from_numpy(heavy).to(device)
-    P, pt = 0, None
-    if pa is not None:
-        P, pt = pa.shape[0], torch.from_numpy(pa).to(device)
+    _, idx, P, pt = selection_on_device(data, device)
+    m = idx.shape[0]
     R, G = ref.shape[0], gen.shape[0]
     out = torch.empty((R, G), dtype=torch.float32, device=device)
+    mirror = torch.empty((R, G), dtype=torch.float32, device=device) if hands else None
     scratch = torch.empty((R + G) * (3 * m + 1), dtype=torch.float32, device=device)
-    if hands:
-        mirror = torch.empty((R, G), dtype=torch.float32, device=device)
-        with torch.cuda.device(out.device):
-            _lib.check(lib.agdiff_rmsd_matrix_hands(_lib.ptr(ref), _lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), R, G, n, m, P,
-                                                    _lib.ptr(scratch), _lib.ptr(out), _lib.ptr(mirror), _lib.stream_ptr()),
-                       "agdiff_rmsd_matrix_hands")
-        return out, mirror
+    name = "agdiff_rmsd_matrix_hands" if hands else "agdiff_rmsd_matrix"
+    outs = (_lib.ptr(out), _lib.ptr(mirror)) if hands else (_lib.ptr(out),)
     with torch.cuda.device(out.device):
-        _lib.check(lib.agdiff_rmsd_matrix(_lib.ptr(ref), _lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), R, G, n, m, P,
-                                          _lib.ptr(scratch), _lib.ptr(out), _lib.stream_ptr()), "agdiff_rmsd_matrix")
-    return out
+        _lib.check(getattr(lib, name)(_lib.ptr(ref), _lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), R, G, n, m, P, _lib.ptr(scratch),
+                                      *outs, _lib.stream_ptr()), name)
+    return (out, mirror) if hands else out
 
 
 def get_tfd_confusion_matrix(data, hands=False, device="cuda", weights=None):
