@@ -200,6 +200,63 @@ __global__ void __launch_bounds__(256) k_rmsd_matrix(const float* __restrict__ c
   if constexpr (kMirror) out_mirror[at] = (float)sqrt(fmax(best_mirror, 0.0));
 }
 
+// Trajectory tracking: the RMSD of graph g in frame s to that graph's atoms of `target`, after the best proper rotation, over the
+// atoms with select[a] != 0 -- identity mapping, one wave per (g, s), lanes striding over the graph's atoms whatever their number.
+// The recipe of the header above with the centring of k_center_selected folded in: centroids in fp64, centred coordinates rounded
+// to fp32 once, S and the squared norms from those rounded values in fp64.  kMirror: out_mirror = the same for the frame inverted
+// through its centroid, from the same diagonalisation (ag_pair_msd).  NaN when a selected coordinate of either side is not finite
+// (or the centred coordinates leave fp32's range), and for a graph with no selected atom.
+template <bool kMirror>
+__global__ void __launch_bounds__(64) k_traj_rmsd(const float* __restrict__ frames, long long frame_stride, const float* __restrict__ target,
+                                                  const uint8_t* __restrict__ select, const int32_t* __restrict__ graph_ptr, int G, int N,
+                                                  float* __restrict__ out, float* __restrict__ out_mirror) {
+  const int g = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
+  const float* p = frames + (size_t)s * frame_stride;
+  const int a0 = max(graph_ptr[g], 0), a1 = min(graph_ptr[g + 1], N);       // (a graph_ptr that is not one reads nothing outside)
+  double c[7] = {0, 0, 0, 0, 0, 0, 0};          // sums of the frame's and the target's selected atoms, and their number
+  for (int a = a0 + lane; a < a1; a += 64) {
+    if (!select[a]) continue;
+    const size_t o = (size_t)3 * a;
+    c[0] += p[o]; c[1] += p[o + 1]; c[2] += p[o + 2];
+    c[3] += target[o]; c[4] += target[o + 1]; c[5] += target[o + 2];
+    c[6] += 1.0;
+  }
+  ag_wave_sum(c);
+  const double m = c[6];
+  bool ok = m > 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) ok = ok && ag_finite(c[e]);
+  double best = 0.0, best_mirror = 0.0;
+  if (ok) {                                      // (wave-uniform: every lane holds the same sums)
+    const double cx = c[0] / m, cy = c[1] / m, cz = c[2] / m, tx = c[3] / m, ty = c[4] / m, tz = c[5] / m;
+    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gsum = 0.0;
+    for (int a = a0 + lane; a < a1; a += 64) {
+      if (!select[a]) continue;
+      const size_t o = (size_t)3 * a;
+      const double x0 = (float)(p[o] - cx), x1 = (float)(p[o + 1] - cy), x2 = (float)(p[o + 2] - cz);
+      const double y0 = (float)(target[o] - tx), y1 = (float)(target[o + 1] - ty), y2 = (float)(target[o + 2] - tz);
+      ag_cov_add(S, x0, x1, x2, y0, y1, y2);
+      gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (y0 * y0 + y1 * y1 + y2 * y2);
+    }
+    ag_wave_sum(S);
+    ag_wave_sum(gsum);
+    ok = ag_finite(gsum);
+    if (ok) {
+      double K[10], d[4];
+      ag_horn_key(S, K);
+      ag_jacobi4<false>(K, d);
+      best = (gsum - 2.0 * fmax(fmax(d[0], d[1]), fmax(d[2], d[3]))) / m;
+      if constexpr (kMirror) best_mirror = (gsum + 2.0 * fmin(fmin(d[0], d[1]), fmin(d[2], d[3]))) / m;
+    }
+  }
+  if (lane == 0) {
+    const float nan = __int_as_float(0x7fc00000);
+    const size_t at = (size_t)s * G + g;
+    out[at] = ok ? (float)sqrt(fmax(best, 0.0)) : nan;
+    if constexpr (kMirror) out_mirror[at] = ok ? (float)sqrt(fmax(best_mirror, 0.0)) : nan;
+  }
+}
+
 // one wave per row (blockIdx.y == 0) or per column (== 1)
 __global__ void __launch_bounds__(64) k_matrix_minima(const float* __restrict__ mat, int R, int G, float* __restrict__ row_min,
                                                       float* __restrict__ col_min) {
@@ -912,5 +969,25 @@ extern "C" int agdiff_clash_scan(const float* pos, const float* radius, const in
   }
   k_clash_finish<<<dim3((unsigned)G), dim3(64), 0, st>>>(scratch, S, min_ratio, min_pair, n_clash);
   AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_traj_rmsd(const float* frames, int64_t frame_stride, const float* target, const uint8_t* select,
+                                const int32_t* graph_ptr, int32_t S, int32_t G, int32_t N, float* out, float* out_mirror, void* stream) {
+  if (!frames || !target || !select || !graph_ptr || !out || out_mirror == out || S < 0 || G < 0 || N <= 0 || frame_stride < (int64_t)3 * N)
+    return AGDIFF_ERR_ARG;
+  if (S == 0 || G == 0) return AGDIFF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  for (int s0 = 0; s0 < S; s0 += 65535) {           // (a grid's y extent ends at 65535)
+    const int sc = S - s0 < 65535 ? S - s0 : 65535;
+    const float* f = frames + (size_t)s0 * frame_stride;
+    float* o = out + (size_t)s0 * G;
+    if (out_mirror)
+      k_traj_rmsd<true><<<dim3((unsigned)G, (unsigned)sc), dim3(64), 0, st>>>(f, frame_stride, target, select, graph_ptr, G, N, o,
+                                                                             out_mirror + (size_t)s0 * G);
+    else
+      k_traj_rmsd<false><<<dim3((unsigned)G, (unsigned)sc), dim3(64), 0, st>>>(f, frame_stride, target, select, graph_ptr, G, N, o, nullptr);
+    AG_CHECK_LAUNCH();
+  }
   return AGDIFF_OK;
 }

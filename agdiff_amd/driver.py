@@ -12,7 +12,9 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 `num_refs_i` scalar, `name_i` string.  Output: `samples_<first>_<last>.npz` per batch (named by the molecule
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
 --save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T; + `hand_<i>` [num_samples] with --fix-handedness, which needs
-`stereo_<i>` in the test set; + `valid_<i>`, `bond_dev_<i>` and `clash_<i>` [num_samples] with --check-geometry) and the merged `samples_all.npz`, written by rank 0 after a barrier.
+`stereo_<i>` in the test set; + `valid_<i>`, `bond_dev_<i>` and `clash_<i>` [num_samples] with --check-geometry; + `rmsd_traj_<i>` [steps, num_samples] with --track-rmsd, which needs `pos_target_<i>` in the test set: every
+conformer's heavy-atom RMSD to that target after every step, + `rmsd_mirror_traj_<i>` with --track-rmsd-mirror) and the merged
+`samples_all.npz`, written by rank 0 after a barrier.
 
 `--noise counter` draws every conformer's pos_init and noise from the counter-based generator under `--seed` and the conformer's
 stream id (`stream_id`): the same numbers whatever --max-atoms, the packing, a --resume or the number of ranks.
@@ -39,7 +41,8 @@ def num_confs(spec):
 
 def save_testset(path, molecules):
     """molecules: list of dicts with atom_type, edge_index, edge_type, num_refs, name; optionally stereo (int8 [n]: the target
-    parity at the stereocentres, 0 elsewhere -- agdiff_amd.stereo), saved as `stereo_<i>` when present."""
+    parity at the stereocentres, 0 elsewhere -- agdiff_amd.stereo), saved as `stereo_<i>` when present, and pos_target (float32
+    [n, 3]: the structure --track-rmsd follows every conformer's RMSD to -- agdiff_amd.trajectory), saved as `pos_target_<i>`."""
     out = {"count": np.int64(len(molecules))}
     for i, m in enumerate(molecules):
         out["atom_type_%d" % i] = np.asarray(m["atom_type"], dtype=np.int64)
@@ -49,6 +52,12 @@ def save_testset(path, molecules):
         out["name_%d" % i] = np.str_(m.get("name", "mol%d" % i))
         if m.get("stereo") is not None:
             out["stereo_%d" % i] = np.asarray(m["stereo"], dtype=np.int8)
+        if m.get("pos_target") is not None:
+            n = np.asarray(m["atom_type"]).reshape(-1).shape[0]
+            target = np.asarray(m["pos_target"], dtype=np.float32)
+            if target.shape != (n, 3):
+                raise ValueError("pos_target of molecule %d has shape %s, expected (%d, 3)" % (i, target.shape, n))
+            out["pos_target_%d" % i] = target
     np.savez_compressed(path, **out)
 
 
@@ -61,6 +70,8 @@ def load_testset(path):
                          name=str(z["name_%d" % i]), index=i))
         if "stereo_%d" % i in z.files:
             mols[-1]["stereo"] = z["stereo_%d" % i]
+        if "pos_target_%d" % i in z.files:
+            mols[-1]["pos_target"] = z["pos_target_%d" % i]
     return mols
 
 
@@ -132,9 +143,10 @@ def plan_batches(mols, confs_of, max_atoms):
 def pack_batch(mols, confs_of):
     """repeat_data (utils/misc.py:88-90) for every molecule of the batch, concatenated.  When every molecule carries its `index`
     (load_testset), `stream_ids` [num_graphs] names each graph's random stream (stream_id, attempt 0): the ids travel with the
-    graphs through subset_batch and dist.shard_of."""
+    graphs through subset_batch and dist.shard_of.  When every molecule carries a `pos_target` [n, 3], `pos_target` [N, 3] holds it
+    once per conformer (float32): what the sampler tracks every graph's RMSD to (--track-rmsd)."""
     from .synth import repeat_molecule
-    ats, rs, cs, ts, bs, spans, ids = [], [], [], [], [], [], []
+    ats, rs, cs, ts, bs, spans, ids, targets = [], [], [], [], [], [], [], []
     node_off, g_off = 0, 0
     for m in mols:
         g = confs_of(m["num_refs"])
@@ -145,12 +157,16 @@ def pack_batch(mols, confs_of):
         spans.append((node_off, n, g))
         if isinstance(m, dict) and m.get("index") is not None:
             ids.append(stream_id(int(m["index"]), np.arange(g, dtype=np.int64)))
+        if isinstance(m, dict) and m.get("pos_target") is not None:
+            targets.append(np.tile(np.asarray(m["pos_target"], dtype=np.float32).reshape(n, 3), (g, 1)))
         node_off += n * g
         g_off += g
     out = dict(atom_type=np.concatenate(ats), bond_index=np.stack([np.concatenate(rs), np.concatenate(cs)]),
                bond_type=np.concatenate(ts), batch=np.concatenate(bs), num_graphs=g_off, spans=spans)
     if len(ids) == len(mols):
         out["stream_ids"] = np.concatenate(ids) if ids else np.zeros(0, dtype=np.int64)
+    if mols and len(targets) == len(mols):
+        out["pos_target"] = np.concatenate(targets)
     return out
 
 
@@ -204,7 +220,7 @@ def _prepare_in_worker(bmols, confs, rank, world, topo_opts):
 
 
 def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_retry=2, log=print, pos_init=None,
-                 noise=None, topology=None, counter_seed=None):
+                 noise=None, topology=None, counter_seed=None, *, curves=None):
     """test.py:143-181 for every molecule of a packed batch: a molecule in which a NaN appeared is sampled again
     (fresh pos_init) with clip_local=20, at most `max_retry` attempts in all, and dropped after that; the molecules
     packed with it keep their first result -- graphs are independent on the whole path, and the update kernel flags
@@ -215,12 +231,20 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
     `counter_seed` (--noise counter): pos_init and the steps' noise come from the counter-based generator with this key and
     the batch's `stream_ids` instead of torch's generator -- a conformer's draws then depend on (seed, molecule index,
     conformer, attempt) alone.  A NaN retry draws with attempt + 1; a split-bf16 re-run of a range-only fault keeps its attempt
-    (the same draws in wider arithmetic)."""
+    (the same draws in wider arithmetic).
+    `curves`: a dict to fill with the tracked RMSD curves (epsnet.LangevinRun: rmsd_target = the batch's `pos_target`, heavy atoms):
+    curves["rmsd"] float32 [steps, num_graphs] and, when it came in with curves["mirror"] true, curves["rmsd_mirror"].  A molecule's
+    columns come from the pass that succeeded; columns of dropped molecules are NaN."""
     import torch
     T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
     spans = packed["spans"]
     n_mol = len(spans)
     _check_counter(model, packed, counter_seed)
+    if curves is not None:
+        if packed.get("pos_target") is None:
+            raise ValueError("tracking the RMSD needs `pos_target` in the packed batch (every molecule with its pos_target)")
+        if not hasattr(model, "begin_sampling"):
+            raise ValueError("tracking the RMSD needs a model with begin_sampling")
     if not hasattr(model, "begin_sampling"):
         at, bi, bt, ba = T(packed["atom_type"]), T(packed["bond_index"]), T(packed["bond_type"]), T(packed["batch"])
         clip_local = None
@@ -261,6 +285,8 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
             p0 = torch.randn(at.shape[0], 3).to(device)
         with _arithmetic(model, wide):
             extra = {"topology": topology} if (topology is not None and sub is packed) else {}
+            if curves is not None:
+                extra.update(rmsd_target=sub["pos_target"], rmsd_mirror=bool(curves.get("mirror")))
             run = model.begin_sampling(at, p0, bi, bt, ba, sub["num_graphs"], False, clip_local=clip_local,
                                        save_traj=save_traj, raise_on_nan=False,
                                        noise=(noise if first else None), **extra, **counter, **sampler_kwargs)
@@ -277,6 +303,8 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
                 traj_out = torch.full((traj.shape[0], N, 3), float("nan"))
         nan_failed, range_failed = _sort_results(todo, sub["spans"], spans, bad_graph, out_of_range, wide, ok, pos_out, pos,
                                                  traj_out if save_traj else None, traj if save_traj else None)
+        if curves is not None:
+            _sort_curves(curves, run, todo, sub["spans"], spans, set(nan_failed) | set(range_failed))
         if out_of_range:
             SAMPLE_STATS["range_trips"] += len(out_of_range)
         if range_failed:
@@ -315,6 +343,23 @@ def _sort_results(todo, sub_spans, spans, bad_graph, out_of_range, wide, ok, pos
                 traj_out[:, off:off + n * g] = traj[:, off_s:off_s + n * g]
         g_off += g
     return nan_failed, range_failed
+
+
+def _sort_curves(curves, run, todo, sub_spans, spans, failed):
+    """One pass's tracked curves (run.rmsd_curve [steps, graphs of the pass]): the columns of the molecules that succeeded go into
+    curves["rmsd"] / curves["rmsd_mirror"] [steps, graphs of `packed`], which start out as NaN."""
+    import torch
+    gfirst = np.concatenate([[0], np.cumsum([g for (_, _, g) in spans])])
+    for key, got in (("rmsd", run.rmsd_curve), ("rmsd_mirror", run.rmsd_curve_mirror)):
+        if got is None:
+            continue
+        if curves.get(key) is None:
+            curves[key] = torch.full((got.shape[0], int(gfirst[-1])), float("nan"))
+        g_off = 0
+        for slot, (_, _, g) in zip(todo, sub_spans):
+            if slot not in failed:
+                curves[key][:, gfirst[slot]:gfirst[slot] + g] = got[:, g_off:g_off + g]
+            g_off += g
 
 
 def _check_counter(model, packed, counter_seed):
@@ -369,6 +414,8 @@ def subset_batch(packed, slots):
                bond_type=packed["bond_type"][esel], batch=np.concatenate(batch), num_graphs=g_off, spans=spans)
     if packed.get("stream_ids") is not None:
         sub["stream_ids"] = np.asarray(packed["stream_ids"])[np.concatenate(keep_graphs).astype(np.int64)]
+    if packed.get("pos_target") is not None:
+        sub["pos_target"] = np.asarray(packed["pos_target"])[keep]
     return sub
 
 
@@ -411,7 +458,7 @@ def merge_outputs(out_dir):
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
-            fix_handedness=False, prune_tfd=None, check_geometry=False):
+            fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -432,7 +479,21 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     bond-length bound in Angstrom) and `clash_<i>` float32 [G] (the smallest distance between atoms more than three bonds apart as
     a fraction of their van der Waals sum) -- agdiff_amd.validity.check_geometry with the table bounds, after the handedness fix
     and before the prune.  `pos_gen_<i>` is left as it is; with a prune switch the invalid conformers take no part in the walk
-    (`cluster_<i>` is -1 for them)."""
+    (`cluster_<i>` is -1 for them).
+    track_rmsd=True: every saved molecule also gets `rmsd_traj_<i>` float32 [steps, G]: each conformer's heavy-atom RMSD to the
+    molecule's `pos_target` (load_testset: `pos_target_<i>`; a molecule without one is an error) after every denoising step,
+    computed while the run samples (agdiff_amd.trajectory), with or without save_traj; track_rmsd_mirror=True adds
+    `rmsd_mirror_traj_<i>`, the RMSD of the mirror image.  Not with graph-sharded sampling (shard=True, what --dist-mode shard is over
+    several ranks: each rank updates only its own graphs); whole batches per rank (shard=False) work."""
+    track_rmsd = bool(track_rmsd or track_rmsd_mirror)
+    if track_rmsd:
+        missing = [m["name"] for m in mols if m.get("pos_target") is None]
+        if missing:
+            raise ValueError("track_rmsd needs `pos_target_<i>` in the test set; missing for %d molecules: %s"
+                             % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
+        if shard:
+            raise ValueError("track_rmsd does not work with graph-sharded sampling (shard=True, %d ranks: each rank updates only its "
+                             "own graphs); use --dist-mode batches" % world)
     if noise not in ("default", "counter"):
         raise ValueError("noise must be 'default' or 'counter'")
     if prune_rms is not None and not float(prune_rms) >= 0.0:
@@ -503,7 +564,8 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     fut = submit(mine[0], first=True) if mine else None
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world, counter_seed, prune_rms, fix_handedness, prune_tfd, check_geometry)
+                                world, counter_seed, prune_rms, fix_handedness, prune_tfd,
+                                ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -512,7 +574,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, check_geometry=False):
+                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, check_geometry=False):
     import torch.distributed as dist
     mirrored = undecided = checked = invalid = 0
     for pos_in_mine, bidx in enumerate(mine):
@@ -539,16 +601,23 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
             if rank != 0:
                 continue
         else:
+            curves = dict(track) if track is not None else None
             pos, traj, ok = sample_batch(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log, topology=topology,
-                                         counter_seed=counter_seed)
+                                         counter_seed=counter_seed, **({"curves": curves} if curves is not None else {}))
         if not ok.any():
             log("batch %d: every molecule failed twice (NaN); skipped: %s" % (bidx, [m["name"] for m in bmols]))
             continue
         out = {}
+        g_first = 0
         for m, (off, n, g), good in zip(bmols, packed["spans"], ok):
+            g_first += g
             if not good:
                 log("molecule %s failed twice (NaN); skipped" % m["name"])
                 continue
+            if track is not None:
+                for key, name in (("rmsd", "rmsd_traj_%d"), ("rmsd_mirror", "rmsd_mirror_traj_%d")):
+                    if curves.get(key) is not None:
+                        out[name % m["index"]] = curves[key][:, g_first - g:g_first].numpy().copy()
             out["pos_gen_%d" % m["index"]] = pos[off:off + n * g].numpy().reshape(g, n, 3)
             out["name_%d" % m["index"]] = np.str_(m["name"])
             if fix_handedness:
@@ -639,6 +708,13 @@ def main(argv=None):
                     help="also save, per molecule, valid_<i>, bond_dev_<i> and clash_<i>: which conformers pass the bond-length bounds "
                          "and the steric clash scan of agdiff_amd.validity (pos_gen_<i> still holds them all); with --prune-rms / "
                          "--prune-tfd the invalid ones are left out of the walk (cluster_<i> = -1)")
+    ap.add_argument("--track-rmsd", action="store_true",
+                    help="also save, per molecule, rmsd_traj_<i> [steps, num_samples]: every conformer's heavy-atom RMSD to the "
+                         "molecule's pos_target_<i> of the test set after every denoising step, computed while the run samples "
+                         "(agdiff_amd.trajectory) -- the convergence curve without --save-traj's steps x atoms x 12 bytes; not with "
+                         "--dist-mode shard over several ranks")
+    ap.add_argument("--track-rmsd-mirror", action="store_true",
+                    help="--track-rmsd plus rmsd_mirror_traj_<i>: the RMSD of each conformer's mirror image to the target")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
     ap.add_argument("--dist-mode", default="shard", choices=["shard", "batches"],
                     help="with several ranks: 'shard' = every packed batch (max-atoms x world atoms) is split into "
@@ -682,7 +758,7 @@ def main(argv=None):
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
             seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
-            check_geometry=args.check_geometry)
+            check_geometry=args.check_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror)
     if own_pg:
         dist.destroy_process_group()
 

@@ -640,6 +640,12 @@ class DualEncoderEpsNetwork(nn.Module):
                            atom index inside the graph, i), filled 128 steps per launch: the same numbers for a conformer
                            wherever it is packed, whatever ran before it and however the batch is sharded
                            (model.counter_normals gives the matching pos_init; no step graphs in this mode)
+          rmsd_target      [N, 3]: track every graph's RMSD to it (after the optimal proper rotation; identity atom mapping) after
+                           every step while the run samples -- agdiff_amd/trajectory.py.  The run (begin_sampling) then has
+                           `rmsd_curve`, after finish() a float32 host tensor [steps, G] (columns of nan_graphs() all NaN), and
+                           with rmsd_mirror=True `rmsd_curve_mirror`, the RMSD to the mirror image.  rmsd_select [N]: the atoms
+                           that enter (default: the heavy atoms, atom_type != 1).  Works without save_traj (a ring of
+                           2 x nan_check_every frames); no step graphs in such a run.  What the call returns does not change.
           traj_overlap_min_bytes  the trajectory goes to the host while the run samples when a poll interval's chunk
                            (nan_check_every x N x 12 B) is at least this large (default 16 MiB); else one copy at the end
         """
@@ -692,7 +698,7 @@ class LangevinRun:
                  n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global, noise=None,
                  save_traj=True, skip_discarded_global=True, nan_check_every=64, step_indices=None, on_step=None,
                  extend_radius=True, raise_on_nan=True, noise_mode="chunked", traj_overlap_min_bytes=16 << 20, topology=None,
-                 noise_seed=None, stream_ids=None, **_ignored):
+                 noise_seed=None, stream_ids=None, *, rmsd_target=None, rmsd_select=None, rmsd_mirror=False, **_ignored):
         if noise_mode not in ("chunked", "per_step", "counter"):
             raise ValueError("noise_mode must be 'chunked', 'per_step' or 'counter'")
         if noise_mode == "counter" and (noise_seed is None or stream_ids is None):
@@ -722,6 +728,20 @@ class LangevinRun:
         self._traj_host, self._traj_sent, self._traj_pending, self._traj_stage, self._traj_stream = None, 0, None, None, None
         self._traj_ready = 0                   # trajectory rows whose writing launch has been enqueued
         self._traj_overlap = bool(save_traj) and max(int(nan_check_every), 1) * N * 12 >= int(traj_overlap_min_bytes)
+        # rmsd_target [N, 3]: every graph's RMSD to it after every step (agdiff_amd/trajectory.py), one
+        # agdiff_traj_rmsd launch per poll over the frames the update kernels have written since the last one: rows of self.traj, or
+        # -- without save_traj -- of a ring of 2 x nan_check_every frames (doubled: with the fused front the last step's update is
+        # still pending at a poll, so up to nan_check_every + 1 frames wait for the next one; see _traj_ready).  Stream order alone
+        # keeps a ring row from being overwritten before it is read.
+        self._rmsd, self._rmsd_ring, self._rmsd_done = None, None, 0
+        self.rmsd_curve, self.rmsd_curve_mirror = None, None
+        if rmsd_target is not None:
+            from .trajectory import RmsdTracker
+            self._rmsd = RmsdTracker(rmsd_target, rmsd_select, self.topo.graph_ptr, len(self.steps), dev, mirror=bool(rmsd_mirror),
+                                     atom_type=atom_type)
+            if self.traj is None:
+                rows = max(1, min(2 * max(int(nan_check_every), 1), len(self.steps)))
+                self._rmsd_ring = torch.empty((rows, N, 3), dtype=torch.float32, device=dev)
         self.noise, self.on_step = noise, on_step
         self.step_lr, self.global_start_sigma = step_lr, global_start_sigma
         self.skip_discarded, self.nan_every = bool(skip_discarded_global), int(nan_check_every)
@@ -759,7 +779,7 @@ class LangevinRun:
         sg = getattr(model, "step_graphs", "auto")
         self._use_graphs = bool((sg is True or (sg == "auto" and N <= model.STEP_GRAPH_MAX_NODES)) and on_step is None and
                                 noise_mode == "chunked" and self.pk.poly_kt > 0 and getattr(model, "fused_front", True) and
-                                not getattr(model, "front_split_graph", False) and not self.topo.large)
+                                not getattr(model, "front_split_graph", False) and not self.topo.large and self._rmsd is None)
         self._graphs, self._step_table, self._step_index, self._dev_index = {}, None, None, None
         # (a capture needs a stream of its own: the legacy default stream, which torch hands out as the current one, cannot be captured)
         self._gstream = torch.cuda.Stream(device=dev) if self._use_graphs else None
@@ -832,12 +852,20 @@ class LangevinRun:
         sig, step_size, noise_scale, use_global = self._sched[k]
         cur = self._noise_for(k, dev, N)
         a.noise = _lib.ptr(cur)
-        a.traj_out = ctypes.c_void_p(self.traj[k].data_ptr()) if self.traj is not None else ctypes.c_void_p(0)
+        a.traj_out = self._traj_row(k)
         a.sigma = sig
         a.step_size = step_size
         a.noise_scale = noise_scale
         a.use_global = 1 if use_global else 0
         return cur, bool(use_global or not self.skip_discarded)
+
+    def _traj_row(self, k):
+        """Where the update of step k writes its frame: row k of the trajectory, else row k of the tracker's ring, else nowhere."""
+        if self.traj is not None:
+            return ctypes.c_void_p(self.traj[k].data_ptr())
+        if self._rmsd_ring is not None:
+            return ctypes.c_void_p(self._rmsd_ring[k % self._rmsd_ring.shape[0]].data_ptr())
+        return ctypes.c_void_p(0)
 
     def _build_step_table(self, first):
         """The update's arguments of EVERY step of the run as a device array of agdiff_step_args_t (what _fill_args would put into
@@ -977,7 +1005,7 @@ class LangevinRun:
                 cur = self._noise_for(k, dev, N)
                 sig, step_size, noise_scale, use_global = self._sched[k]
                 a.noise = _lib.ptr(cur)
-                a.traj_out = ctypes.c_void_p(self.traj[k].data_ptr()) if self.traj is not None else ctypes.c_void_p(0)
+                a.traj_out = self._traj_row(k)
                 a.sigma = sig
                 a.step_size = step_size
                 a.noise_scale = noise_scale
@@ -1011,6 +1039,7 @@ class LangevinRun:
         split-bf16 (fp32's range) while the others run on."""
         self._traj_land()                    # (before the first synchronisation: the device still has the interval's steps queued)
         self._traj_send(self._traj_ready)    # (rows whose update is enqueued: with the fused front the last step's is still pending)
+        self._rmsd_flush(self._traj_ready)   # (the same rows -> the tracked RMSD curve, one launch, before the host blocks)
         if self.raise_on_nan and int(self.ws.nan_flag[0].item()) != 0:
             print("NaN detected. Please restart.")
             raise FloatingPointError()
@@ -1058,6 +1087,19 @@ class LangevinRun:
             self._traj_pending = (ev, lo, hi, buf)
             self._traj_sent = hi
 
+    def _rmsd_flush(self, upto):
+        """Steps [_rmsd_done, upto) -> rows of the tracked curve: one agdiff_traj_rmsd launch on the current stream over the frames
+        of the trajectory, or over their rows of the ring (two launches when the span wraps)."""
+        if self._rmsd is None or upto <= self._rmsd_done:
+            return
+        from .trajectory import ring_spans
+        frames = self.traj if self.traj is not None else self._rmsd_ring
+        step = self._rmsd_done
+        for lo, hi in ring_spans(step, upto, frames.shape[0] if self.traj is None else len(self.steps)):
+            self._rmsd.evaluate(frames[lo:hi], 3 * self.topo.N, hi - lo, step)
+            step += hi - lo
+        self._rmsd_done = upto
+
     def nan_graphs(self):
         """Bool tensor [G] (host): graphs in which a position became NaN so far (ws.nan_flag[1 + g]) or that left the
         split-fp16 range (range_graphs: also when that showed at the very last poll, after the last update)."""
@@ -1069,6 +1111,17 @@ class LangevinRun:
     def finish(self):
         """(pos on device, pos_traj list of CPU tensors) as dualenc.py:547 returns them."""
         self.check_nan()
+        if self._rmsd is not None:
+            # (a quarantined graph carries placeholder geometry, not a conformer: its whole column is NaN)
+            self._rmsd_flush(self.k)
+            bad = self.nan_graphs()
+            curves = []
+            for rows in (self._rmsd.rows, self._rmsd.rows_mirror):
+                if rows is not None:
+                    rows = rows[:self.k].cpu()
+                    rows[:, bad] = float("nan")
+                curves.append(rows)
+            self.rmsd_curve, self.rmsd_curve_mirror = curves
         if self.traj is not None and self._traj_overlap:
             self._traj_send(self.k)
             self._traj_land()

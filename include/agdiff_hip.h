@@ -889,6 +889,31 @@ int agdiff_clash_scan(const float* pos, const float* radius /* [n], > 0 */, cons
                       int32_t G, int32_t n, float thresh, int32_t* scratch, float* min_ratio /* [G] */,
                       int32_t* min_pair /* [G][2] */, int32_t* n_clash /* [G] */, void* stream);
 
+/* ---- trajectory tracking ---------------------------------------------------------------------------------------------
+ * The convergence curve of examples/test_alanine_dipeptide.py:106-164 (every frame of the denoising run superposed on a target
+ * structure, heavy-atom RMSD) for a PACKED batch, without keeping the trajectory: epsnet.LangevinRun calls this once per NaN
+ * poll over the frames written since the last one (agdiff_amd/trajectory.py).
+ *
+ * agdiff_traj_rmsd: out[s][g] = RMSD of graph g in frame s to the same atoms of `target` after the optimal proper rotation +
+ * translation, over the graph's atoms with select != 0, identity atom mapping (no symmetry: what mdtraj's rmsd does).
+ *   frames                 S frames of a packed batch, [N][3] each, frame s at frames + s * frame_stride (in floats,
+ *                          >= 3 N, else AGDIFF_ERR_ARG): a trajectory, a ring of frames or a strided view of either
+ *   target [N][3]          packed like a frame; need not be centred
+ *   select [N] uint8       1 = the atom enters
+ *   graph_ptr [G + 1]      first atom of every graph (agdiff_topo_t.graph_ptr); entries are clamped to [0, N]
+ *   out [S][G]             sqrt(max((|X|^2 + |Y|^2 - 2 lambda_max(K)) / m, 0)), m = the graph's selected atoms: centroids in
+ *                          fp64, centred coordinates rounded to fp32 once, cross-covariance and norms in fp64 from those
+ *                          (the arithmetic of agdiff_rmsd_matrix with another summation order: equal to ~1e-7, not bit for bit)
+ *   out_mirror [S][G] or null   sqrt(max((|X|^2 + |Y|^2 + 2 lambda_min(K)) / m, 0)): the RMSD of the frame's mirror image, from the
+ *                          same diagonalisation.  Not overlapping out.
+ * Both are NaN for an (s, g) in which a selected coordinate of the frame or of the target is not finite (no other entry
+ * changes), and for a graph without a selected atom.  One 64-lane wave per (g, s), lanes striding over the graph's atoms: any
+ * number of atoms per graph.  No atomics, deterministic bit for bit, independent of S and of frame_stride. */
+int agdiff_traj_rmsd(const float* frames, int64_t frame_stride /* floats between frames, >= 3 N */,
+                     const float* target /* [N][3] */, const uint8_t* select /* [N] */, const int32_t* graph_ptr /* [G + 1] */,
+                     int32_t S, int32_t G, int32_t N, float* out /* [S][G] */, float* out_mirror /* [S][G] or null */,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
