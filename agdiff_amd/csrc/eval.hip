@@ -809,6 +809,208 @@ __global__ void __launch_bounds__(64) k_clash_finish(const int32_t* __restrict__
   }
 }
 
+// ---- distance-distribution MMD (ConfGF / CGCF / GraphDG; include/agdiff_hip.h has the definition): Z = [X; Y], M = R + G rows of
+// K interatomic distances.  "all" is one problem over the rows, "single" one problem per column.  Everything is fp64 from the
+// stored fp32 values; every sum has a fixed order (thread-strided terms, the xor butterfly, then waves or tiles in index order).
+
+// row a of Z = [X; Y]
+__device__ __forceinline__ const float* ag_mmd_row(const float* __restrict__ x, const float* __restrict__ y, int R, int K, int a) {
+  return a < R ? x + (size_t)a * K : y + (size_t)(a - R) * K;
+}
+
+// k = sum_{i = 0 .. 4} exp(-D2 / (b 2^(i - 2))) from ninv = -1 / (4 b): ONE exponential, of the widest bandwidth, and four
+// squarings (e^2, e^4, e^8, e^16 are the bandwidths 2 b, b, b / 2, b / 4).  D2 = 0 gives exactly 5.
+__device__ __forceinline__ double ag_mmd_kernel(double d2, double ninv) {
+  const double e1 = exp(d2 * ninv), e2 = e1 * e1, e4 = e2 * e2, e8 = e4 * e4, e16 = e8 * e8;
+  return (((e16 + e8) + e4) + e2) + e1;
+}
+
+// pair a <= b of the upper triangle into the three ordered-pair sums: XX and YY count (a, b) and (b, a), the diagonal once; XY counts
+// each reference-generated pair once
+__device__ __forceinline__ void ag_mmd_add(int a, int b, int R, double v, double& xx, double& yy, double& xy) {
+  const double w = a == b ? v : 2.0 * v;            // (selects, not branches: the lanes of a wave differ in their class)
+  xx += b < R ? w : 0.0;
+  yy += a >= R ? w : 0.0;
+  xy += (a < R && b >= R) ? v : 0.0;
+}
+
+// mmd2 from the three sums; b == 0 (every row equal) is 0, a bandwidth that is not finite (a non-finite entry) NaN
+__device__ __forceinline__ float ag_mmd_value(double xx, double yy, double xy, int R, int G, double b) {
+  if (b == 0.0) return 0.0f;
+  if (!ag_finite(b)) return __builtin_nanf("");
+  return (float)((xx / ((double)R * R) + yy / ((double)G * G)) - 2.0 * (xy / ((double)R * G)));
+}
+
+// Statistics pass: per column c the scatter q[c] = sum_a (Z[a][c] - mu_c)^2 around the column mean (NaN when the column holds an
+// entry that is not finite), from which b = 2 M q / (M^2 - M) is the mean of D2 over the ordered pairs a != b without a pass over
+// pairs and without cancellation.  Workgroup = 16 columns; thread (ty, tx) walks the rows ty, ty + 16, ... of column c0 + tx (64-byte
+// segments of a table row), the 16 stripes are summed through LDS in stripe order.  With zt it also writes the table transposed,
+// zt [K][M], through a 16 x 17 LDS tile (64-byte segments again), so that k_mmd_single reads a column contiguously; with bw / bw32
+// the per-column bandwidths.
+__global__ void __launch_bounds__(256) k_mmd_stats(const float* __restrict__ x, const float* __restrict__ y, int R, int G, int K,
+                                                   float* __restrict__ zt, double* __restrict__ scatter, double* __restrict__ bw,
+                                                   float* __restrict__ bw32) {
+  __shared__ float tile[16][17];
+  __shared__ double red[16][16];
+  __shared__ int redbad[16][16];
+  const int M = R + G, c0 = blockIdx.x * 16;
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  const int c = c0 + tx;
+  double s = 0.0;
+  int bad = 0;
+  for (int a0 = 0; a0 < M; a0 += 16) {
+    const int a = a0 + ty;
+    float z = 0.0f;
+    if (a < M && c < K) {
+      z = ag_mmd_row(x, y, R, K, a)[c];
+      s += (double)z;
+      bad |= !ag_finite((double)z);
+    }
+    if (zt) {                                       // (uniform: the barriers are reached by every thread)
+      tile[ty][tx] = z;
+      __syncthreads();
+      if (c0 + ty < K && a0 + tx < M) zt[(size_t)(c0 + ty) * M + a0 + tx] = tile[tx][ty];
+      __syncthreads();
+    }
+  }
+  red[ty][tx] = s;
+  redbad[ty][tx] = bad;
+  __syncthreads();
+  double sum = 0.0;
+  bad = 0;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { sum += red[r][tx]; bad |= redbad[r][tx]; }
+  const double mu = sum / (double)M;
+  __syncthreads();
+  double q = 0.0;
+  if (c < K)
+    for (int a = ty; a < M; a += 16) {
+      const double d = (double)ag_mmd_row(x, y, R, K, a)[c] - mu;
+      q += d * d;
+    }
+  red[ty][tx] = q;
+  __syncthreads();
+  if (ty == 0 && c < K) {
+    double qs = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) qs += red[r][tx];
+    if (bad) qs = __builtin_nan("");
+    scatter[c] = qs;
+    if (bw) {
+      const double b = (2.0 * (double)M * qs) / ((double)M * (double)M - (double)M);
+      bw[c] = b;
+      bw32[c] = (float)b;
+    }
+  }
+}
+
+// one wave: the "all" bandwidth from the K column scatters, lanes striding over the columns
+__global__ void __launch_bounds__(64) k_mmd_bandwidth(const double* __restrict__ scatter, int K, int M, double* __restrict__ bw,
+                                                      float* __restrict__ bw32) {
+  double q = 0.0;
+  for (int c = threadIdx.x; c < K; c += 64) q += scatter[c];
+  ag_wave_sum(q);
+  if (threadIdx.x == 0) {
+    const double b = (2.0 * (double)M * q) / ((double)M * (double)M - (double)M);
+    *bw = b;
+    *bw32 = (float)b;
+  }
+}
+
+// "all": one workgroup per 16 x 16 tile of the upper triangle of the M x M row pairs, thread (ty, tx) = rows (i0 + ty, j0 + tx).  The
+// 16 + 16 table rows are staged in LDS AG_MMD_CHUNK columns at a time at an odd pitch (the 16 tx of a tile row read 16 different
+// banks, the ty row is a broadcast).  A diagonal tile counts ty <= tx only.  One partial { XX, YY, XY } per tile.
+#define AG_MMD_CHUNK 64
+__global__ void __launch_bounds__(256) k_mmd_all(const float* __restrict__ x, const float* __restrict__ y, int R, int G, int K, int T,
+                                                 const double* __restrict__ bw, double* __restrict__ partial) {
+  __shared__ float srow[16][AG_MMD_CHUNK + 1];
+  __shared__ float scol[16][AG_MMD_CHUNK + 1];
+  __shared__ double sred[4][3];
+  const double b = *bw;
+  if (!(b > 0.0)) return;                           // (uniform; k_mmd_all_finish does not read the partials then)
+  const double ninv = -0.25 / b;
+  const int M = R + G;
+  int ti, tj;
+  ag_triangle_tile((long long)blockIdx.x, T, ti, tj);
+  const int i0 = ti * 16, j0 = tj * 16;
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  const int ai = i0 + ty, aj = j0 + tx;
+  const bool valid = ai < M && aj < M && ai <= aj;
+  double d2 = 0.0;
+  for (int k0 = 0; k0 < K; k0 += AG_MMD_CHUNK) {
+    const int kc = K - k0 < AG_MMD_CHUNK ? K - k0 : AG_MMD_CHUNK;
+    for (int t = threadIdx.x; t < 16 * AG_MMD_CHUNK; t += 256) {
+      const int r = t / AG_MMD_CHUNK, o = t % AG_MMD_CHUNK;
+      srow[r][o] = (i0 + r < M && o < kc) ? ag_mmd_row(x, y, R, K, i0 + r)[k0 + o] : 0.0f;
+      scol[r][o] = (j0 + r < M && o < kc) ? ag_mmd_row(x, y, R, K, j0 + r)[k0 + o] : 0.0f;
+    }
+    __syncthreads();
+    if (valid)
+      for (int o = 0; o < kc; ++o) {
+        const double d = (double)srow[ty][o] - (double)scol[tx][o];
+        d2 += d * d;
+      }
+    __syncthreads();
+  }
+  double xx = 0.0, yy = 0.0, xy = 0.0;
+  if (valid) ag_mmd_add(ai, aj, R, ag_mmd_kernel(d2, ninv), xx, yy, xy);
+  ag_wave_sum(xx, yy, xy);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sred[wave][0] = xx; sred[wave][1] = yy; sred[wave][2] = xy; }
+  __syncthreads();
+  const int e = threadIdx.x;
+  if (e < 3) partial[(size_t)blockIdx.x * 3 + e] = ((sred[0][e] + sred[1][e]) + sred[2][e]) + sred[3][e];
+}
+
+// one wave: the tile partials, lanes striding over the tiles in tile order
+__global__ void __launch_bounds__(64) k_mmd_all_finish(const double* __restrict__ partial, long long tiles, const double* __restrict__ bw,
+                                                       int R, int G, float* __restrict__ mmd2) {
+  const double b = *bw;
+  double xx = 0.0, yy = 0.0, xy = 0.0;
+  if (b > 0.0)
+    for (long long t = threadIdx.x; t < tiles; t += 64) { xx += partial[3 * t]; yy += partial[3 * t + 1]; xy += partial[3 * t + 2]; }
+  ag_wave_sum(xx, yy, xy);
+  if (threadIdx.x == 0) *mmd2 = ag_mmd_value(xx, yy, xy, R, G, b);
+}
+
+// "single": one workgroup per column, its M values in LDS (read contiguously from the transposed table of k_mmd_stats).  The pairs
+// a <= b are numbered row by row, p = 0 .. M (M + 1) / 2 - 1, and thread t takes p = t, t + 1024, ...: every thread the same number
+// of pairs to within one, whatever M is; the lanes of a wave read consecutive b and (mostly) one a.  Thread sums, butterfly, then
+// the 16 waves in wave order.
+#define AG_MMD_SINGLE_THREADS 1024
+__global__ void __launch_bounds__(AG_MMD_SINGLE_THREADS) k_mmd_single(const float* __restrict__ zt, const double* __restrict__ bw, int R,
+                                                                      int G, float* __restrict__ mmd2) {
+  __shared__ double sred[AG_MMD_SINGLE_THREADS / 64][3];
+  float* z = ag_eval_smem;                          // [M]
+  const int M = R + G, c = blockIdx.x;
+  const double b = bw[c];
+  if (!(b > 0.0)) {                                 // (uniform)
+    if (threadIdx.x == 0) mmd2[c] = ag_mmd_value(0.0, 0.0, 0.0, R, G, b);
+    return;
+  }
+  const double ninv = -0.25 / b;
+  for (int a = threadIdx.x; a < M; a += AG_MMD_SINGLE_THREADS) z[a] = zt[(size_t)c * M + a];
+  __syncthreads();
+  double xx = 0.0, yy = 0.0, xy = 0.0;
+  int a = 0, off = threadIdx.x;                     // pair (a, a + off); row a holds M - a pairs
+  while (a < M && off >= M - a) { off -= M - a; ++a; }
+  while (a < M) {
+    const double d = (double)z[a] - (double)z[a + off];
+    ag_mmd_add(a, a + off, R, ag_mmd_kernel(d * d, ninv), xx, yy, xy);
+    off += AG_MMD_SINGLE_THREADS;
+    while (a < M && off >= M - a) { off -= M - a; ++a; }
+  }
+  ag_wave_sum(xx, yy, xy);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sred[wave][0] = xx; sred[wave][1] = yy; sred[wave][2] = xy; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    xx = yy = xy = 0.0;
+    for (int w = 0; w < AG_MMD_SINGLE_THREADS / 64; ++w) { xx += sred[w][0]; yy += sred[w][1]; xy += sred[w][2]; }
+    mmd2[c] = ag_mmd_value(xx, yy, xy, R, G, b);
+  }
+}
+
 }  // namespace
 
 // bytes per row of a threshold bit-matrix of `columns` columns: 16-bit pieces, rounded up to 8 bytes
@@ -989,5 +1191,52 @@ extern "C" int agdiff_traj_rmsd(const float* frames, int64_t frame_stride, const
       k_traj_rmsd<false><<<dim3((unsigned)G, (unsigned)sc), dim3(64), 0, st>>>(f, frame_stride, target, select, graph_ptr, G, N, o, nullptr);
     AG_CHECK_LAUNCH();
   }
+  return AGDIFF_OK;
+}
+
+// the checks the two MMD calls share; M = R + G <= 2^31 - 2 either way
+static int ag_mmd_check(const float* tab_x, const float* tab_y, int32_t R, int32_t G, int32_t K, const void* scratch, const float* mmd2,
+                        const float* bandwidth) {
+  if (!tab_x || !tab_y || !scratch || !mmd2 || !bandwidth || R < 1 || G < 1 || K < 1 || ((uintptr_t)scratch & 7)) return AGDIFF_ERR_ARG;
+  if ((int64_t)R + (int64_t)G > 0x7ffffffell) return AGDIFF_ERR_LIMIT;
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_mmd_all(const float* tab_x, const float* tab_y, int32_t R, int32_t G, int32_t K, void* scratch, float* mmd2,
+                              float* bandwidth, void* stream) {
+  const int rc = ag_mmd_check(tab_x, tab_y, R, G, K, scratch, mmd2, bandwidth);
+  if (rc != AGDIFF_OK) return rc;
+  const int64_t T = ((int64_t)R + G + 15) / 16;
+  const int64_t tiles = T * (T + 1) / 2;
+  if (tiles >= (1ll << 24)) return AGDIFF_ERR_LIMIT;      // (256 threads per tile: the grid stays below 2^32 threads)
+  hipStream_t st = (hipStream_t)stream;
+  double* scatter = (double*)scratch;               // [K]
+  double* bw = scatter + K;                         // [1]
+  double* partial = bw + 1;                         // [tiles][3]
+  k_mmd_stats<<<dim3((unsigned)(((int64_t)K + 15) / 16)), dim3(256), 0, st>>>(tab_x, tab_y, R, G, K, nullptr, scatter, nullptr, nullptr);
+  AG_CHECK_LAUNCH();
+  k_mmd_bandwidth<<<dim3(1), dim3(64), 0, st>>>(scatter, K, R + G, bw, bandwidth);
+  AG_CHECK_LAUNCH();
+  k_mmd_all<<<dim3((unsigned)tiles), dim3(256), 0, st>>>(tab_x, tab_y, R, G, K, (int)T, bw, partial);
+  AG_CHECK_LAUNCH();
+  k_mmd_all_finish<<<dim3(1), dim3(64), 0, st>>>(partial, (long long)tiles, bw, R, G, mmd2);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_mmd_single(const float* tab_x, const float* tab_y, int32_t R, int32_t G, int32_t K, void* scratch, float* mmd2,
+                                 float* bandwidth, void* stream) {
+  const int rc = ag_mmd_check(tab_x, tab_y, R, G, K, scratch, mmd2, bandwidth);
+  if (rc != AGDIFF_OK) return rc;
+  if ((int64_t)R + G > AGDIFF_MMD_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  hipStream_t st = (hipStream_t)stream;
+  const int M = R + G;
+  double* scatter = (double*)scratch;               // [K]
+  double* bw = scatter + K;                         // [K]
+  float* zt = (float*)(bw + K);                     // [K][M]
+  k_mmd_stats<<<dim3((unsigned)(((int64_t)K + 15) / 16)), dim3(256), 0, st>>>(tab_x, tab_y, R, G, K, zt, scatter, bw, bandwidth);
+  AG_CHECK_LAUNCH();
+  k_mmd_single<<<dim3((unsigned)K), dim3(AG_MMD_SINGLE_THREADS), (size_t)M * sizeof(float), st>>>(zt, bw, R, G, mmd2);
+  AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -43,6 +43,7 @@ extern "C" {
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
 #define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
+#define AGDIFF_MMD_MAX_CONFS 8192 /* most reference + generated conformers of agdiff_mmd_single: one column of them is 32 KB of LDS */
 #define AGDIFF_POLY_MAX_KT 4      /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
 #define AGDIFF_POLY_MAX_SLOTS 16   /* most local edge types with filter polynomials; the first sets that fit stay in LDS next to the
@@ -913,6 +914,41 @@ int agdiff_traj_rmsd(const float* frames, int64_t frame_stride /* floats between
                      const float* target /* [N][3] */, const uint8_t* select /* [N] */, const int32_t* graph_ptr /* [G + 1] */,
                      int32_t S, int32_t G, int32_t N, float* out /* [S][G] */, float* out_mirror /* [S][G] or null */,
                      void* stream);
+
+/* ---- distance-distribution MMD -----------------------------------------------------------------------------------------
+ * The maximum mean discrepancy between the interatomic-distance distributions of the generated and the reference conformers of
+ * one molecule, as the ConfGF / CGCF / GraphDG line reports it ("all", and "single" per atom pair; their "pair" mode, over all
+ * pairs of columns, is not built).  The tables are what agdiff_pair_bounds writes as `dist`.
+ *   tab_x [R][K], tab_y [G][K]   fp32 distances of K atom pairs in the R reference and the G generated conformers
+ *   Z = [X; Y], M = R + G, R >= 1, G >= 1, K >= 1; all arithmetic in fp64 from the stored fp32 values
+ *   D2(a, b)  = sum_k (Z[a][k] - Z[b][k])^2
+ *   b         = sum_{a, b} D2(a, b) / (M^2 - M), computed as the equal 2 M sum_a |Z[a] - mu|^2 / (M^2 - M), mu the column mean
+ *   k(a, b)   = sum_{i = 0 .. 4} exp(-D2(a, b) / (b 2^(i - 2)));  k(a, a) = 5, and the diagonal is included (biased V-statistic)
+ *   mmd2      = mean_{a, b in X} k + mean_{a, b in Y} k - 2 mean_{a in X, b in Y} k, stored as fp32
+ *   b == 0 (all rows equal): mmd2 = 0.  An entry that is not finite in the rows / columns involved: mmd2 = bandwidth = NaN.
+ *
+ * agdiff_mmd_all: ONE problem over the K-dimensional rows.
+ *   scratch   8-byte aligned, 8 (K + 1 + 3 T (T + 1) / 2) bytes, T = ceil(M / 16); written by the call
+ *   mmd2 [1], bandwidth [1]   (bandwidth = b as fp32)
+ *   T (T + 1) / 2 >= 2^24 tiles (M > 92,672): AGDIFF_ERR_LIMIT -- the grid of 256-thread workgroups stays below 2^32 threads
+ * A statistics pass (column means and scatters, 16 columns per workgroup), one wave that sums the scatters into b, one workgroup
+ * per 16 x 16 tile of the upper triangle of the M x M pairs (off-diagonal pairs weighted twice, table rows staged in LDS 64
+ * columns at a time, one exponential and four squarings per pair, one partial { XX, YY, XY } per tile) and one wave that sums the
+ * partials in tile order.
+ *
+ * agdiff_mmd_single: K independent one-dimensional problems, column k of both tables each.
+ *   scratch   8-byte aligned, 16 K + 4 K M bytes; written by the call (the column scatters, the fp64 bandwidths and the table
+ *             transposed to [K][M]: the statistics pass transposes, the callers pass [R][K] / [G][K] as to agdiff_mmd_all)
+ *   mmd2 [K], bandwidth [K]   a column with an entry that is not finite is NaN in both; no other column changes
+ *   M > AGDIFF_MMD_MAX_CONFS: AGDIFF_ERR_LIMIT
+ * The statistics pass, then one workgroup of 1024 threads per column: its M values in LDS, the pairs a <= b numbered row by row
+ * and dealt to the threads round robin.
+ * Both: AGDIFF_ERR_ARG for R < 1, G < 1, K < 1 or a null pointer.  No atomics, deterministic bit for bit; multiplying both tables
+ * by a power of two changes no bit of mmd2. */
+int agdiff_mmd_all(const float* tab_x /* [R][K] */, const float* tab_y /* [G][K] */, int32_t R, int32_t G, int32_t K, void* scratch,
+                   float* mmd2 /* [1] */, float* bandwidth /* [1] */, void* stream);
+int agdiff_mmd_single(const float* tab_x /* [R][K] */, const float* tab_y /* [G][K] */, int32_t R, int32_t G, int32_t K, void* scratch,
+                      float* mmd2 /* [K] */, float* bandwidth /* [K] */, void* stream);
 
 #ifdef __cplusplus
 }
