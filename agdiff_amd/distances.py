@@ -21,7 +21,8 @@ ConfGF's "pair" mode (all pairs of columns) is not built.
 import numpy as np
 
 from . import _lib
-from .evaluation import _as_conformers
+from .molecule import num_atoms, reference_items
+from .validity import pair_bounds
 
 MAX_CONFS = _lib.DEFINES["AGDIFF_MMD_MAX_CONFS"]
 
@@ -37,16 +38,13 @@ def pair_list(atom_type, ignore_h=True):
 def distance_table(pos, pairs):
     """float32 [C, K] on pos's device: the distances of `pairs` (int32 [K, 2]) in the conformers pos [C, n, 3] (float32, contiguous,
     on the GPU), as agdiff_pair_bounds computes them: in fp64 from the fp32 coordinates, rounded once."""
-    from .validity import pair_bounds
     K = np.asarray(pairs).reshape(-1, 2).shape[0]
     return pair_bounds(pos, pairs, np.zeros(K, dtype=np.float32), np.full(K, np.inf, dtype=np.float32), want_dist=True)[3]
 
 
 def _tables(tab_ref, tab_gen):
-    import torch
     for t in (tab_ref, tab_gen):
-        if not (hasattr(t, "is_cuda") and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
-            raise ValueError("the distance tables must be contiguous float32 [conformers, pairs] tensors on the GPU")
+        _lib.require_device_table(t, "the distance tables must be contiguous float32 [conformers, pairs] tensors on the GPU")
     R, G, K = int(tab_ref.shape[0]), int(tab_gen.shape[0]), int(tab_ref.shape[1])
     if int(tab_gen.shape[1]) != K or tab_gen.device != tab_ref.device:
         raise ValueError("both tables must hold the same pairs on the same device (got %d and %d columns)" % (K, tab_gen.shape[1]))
@@ -64,9 +62,7 @@ def mmd_all(tab_ref, tab_gen):
     dev = tab_ref.device
     scratch = torch.empty(K + 1 + 3 * (T * (T + 1) // 2), dtype=torch.float64, device=dev)
     mmd2, bw = (torch.empty(1, dtype=torch.float32, device=dev) for _ in range(2))
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().agdiff_mmd_all(_lib.ptr(tab_ref), _lib.ptr(tab_gen), R, G, K, _lib.ptr(scratch), _lib.ptr(mmd2),
-                                              _lib.ptr(bw), _lib.stream_ptr()), "agdiff_mmd_all")
+    _lib.call("agdiff_mmd_all", tab_ref, tab_gen, R, G, K, scratch, mmd2, bw)
     return mmd2, bw
 
 
@@ -78,9 +74,7 @@ def mmd_single(tab_ref, tab_gen):
     dev = tab_ref.device
     scratch = torch.empty(2 * K + (K * (R + G) + 1) // 2, dtype=torch.float64, device=dev)
     mmd2, bw = (torch.empty(K, dtype=torch.float32, device=dev) for _ in range(2))
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().agdiff_mmd_single(_lib.ptr(tab_ref), _lib.ptr(tab_gen), R, G, K, _lib.ptr(scratch), _lib.ptr(mmd2),
-                                                 _lib.ptr(bw), _lib.stream_ptr()), "agdiff_mmd_single")
+    _lib.call("agdiff_mmd_single", tab_ref, tab_gen, R, G, K, scratch, mmd2, bw)
     return mmd2, bw
 
 
@@ -105,10 +99,10 @@ def distance_mmd(item, ignore_h=True, device="cuda", want_tables=False):
     and, with want_tables only (two more copies to the host),
         table_ref, table_gen            the float32 distance tables [R, K], [G, K] the numbers were computed from (numpy)
     A molecule with fewer than two such atoms has no pair: all NaN, `single` empty."""
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    n = num_atoms(item)
     pairs = pair_list(item["atom_type"], ignore_h)
-    ref = _as_conformers(item["pos_ref"], n).to(device).contiguous()
-    gen = _as_conformers(item["pos_gen"], n).to(device).contiguous()
+    ref = _lib.conformers(item["pos_ref"], n, device)
+    gen = _lib.conformers(item["pos_gen"], n, device)
     if ref.shape[0] < 1 or gen.shape[0] < 1:
         raise ValueError("need at least one reference and one generated conformer")
     nan = float("nan")
@@ -142,16 +136,11 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
-    zs, zr = np.load(args.samples), np.load(args.refs)
     out, rows = {}, []
-    for key in zr.files:
-        if not key.startswith("pos_ref_"):
+    for i, item in reference_items(args.refs, args.samples):
+        if "pos_gen" not in item:
             continue
-        i = key[len("pos_ref_"):]
-        if "pos_gen_" + i not in zs.files:
-            continue
-        res = distance_mmd({"pos_ref": zr[key], "pos_gen": zs["pos_gen_" + i], "atom_type": zr["atom_type_" + i]},
-                           ignore_h=not args.with_h, device=args.device)
+        res = distance_mmd(item, ignore_h=not args.with_h, device=args.device)
         rows.append([res["single_mean"], res["single_median"], res["all"]])
         out["all_" + i] = np.float32(res["all"])
         out["single_" + i] = res["single"]

@@ -19,7 +19,10 @@ along in the alignment.
 import numpy as np
 
 from . import _lib
-from .evaluation import _as_conformers, selection_of, selection_on_device
+from .evaluation import selection_of, selection_on_device
+from .molecule import as_host, check_threshold, heavy_atoms, num_atoms, sampled_items
+from .stereo import fix_handedness as _fix_handedness
+from .validity import check_geometry
 
 MAX_CONFS = _lib.DEFINES["AGDIFF_PRUNE_MAX_CONFS"]
 
@@ -29,30 +32,19 @@ def bits_pitch(G):
     return ((((G + 15) // 16) * 2 + 7) // 8) * 8
 
 
-def _check_threshold(threshold):
-    t = float(threshold)
-    if not t >= 0.0:
-        raise ValueError("the RMSD threshold must be >= 0 (got %r)" % (threshold,))
-    return t
-
-
 def _self_rmsd(item, device, threshold=None, want_out=True):
     """(gen [G, n, 3] on the device, heavy index tensor, out [G, G] or None, bits int64 [G, pitch / 8] or None)"""
     import torch
-    lib = _lib.load()
     at, idx, P, pt = selection_on_device(item, device)
     n, m = at.shape[0], idx.shape[0]
-    gen = _as_conformers(item["pos_gen"], n).to(device).contiguous()
+    gen = _lib.conformers(item["pos_gen"], n, device)
     G = gen.shape[0]
     out = torch.empty((G, G), dtype=torch.float32, device=device) if want_out else None
     bits = None
     if threshold is not None:
         bits = torch.empty((G, bits_pitch(G) // 8), dtype=torch.int64, device=device)
     scratch = torch.empty(max(G, 1) * (3 * m + 1), dtype=torch.float32, device=device)
-    with torch.cuda.device(gen.device):
-        _lib.check(lib.agdiff_rmsd_self(_lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), G, n, m, P,
-                                        0.0 if threshold is None else threshold, _lib.ptr(scratch), _lib.ptr(out),
-                                        _lib.ptr(bits), _lib.stream_ptr()), "agdiff_rmsd_self")
+    _lib.call("agdiff_rmsd_self", gen, idx, pt, G, n, m, P, 0.0 if threshold is None else threshold, scratch, out, bits)
     return gen, idx, out, bits
 
 
@@ -66,7 +58,7 @@ def self_rmsd_matrix(item, device="cuda"):
 def threshold_bits(item, threshold, device="cuda"):
     """(out [G, G], adjacency bool [G, 8 * pitch]): the matrix and the kernel's packed `out <= threshold`, unpacked (columns
     from G on are padding)."""
-    t = _check_threshold(threshold)
+    t = check_threshold(threshold, "RMSD")
     gen, _, out, bits = _self_rmsd(item, device, threshold=t)
     return out, unpack_bits(bits, gen.shape[0])
 
@@ -83,25 +75,19 @@ def leader_prune(bits, G):
     """agdiff_leader_prune on a packed bit-matrix (int64 [G, pitch / 8] on the GPU): (keep, leader, count, n_kept) int32.
     More than AGDIFF_PRUNE_MAX_CONFS conformers: AgdiffLimitError."""
     import torch
-    lib = _lib.load()
     dev = bits.device
     keep, leader, count = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(3))
     n_kept = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.agdiff_leader_prune(_lib.ptr(bits), G, _lib.ptr(keep), _lib.ptr(leader), _lib.ptr(count),
-                                           _lib.ptr(n_kept), _lib.stream_ptr()), "agdiff_leader_prune")
+    _lib.call("agdiff_leader_prune", bits, G, keep, leader, count, n_kept)
     return keep, leader, count, n_kept
 
 
 def _align(pos, idx, target):
     import torch
-    lib = _lib.load()
     G, n = pos.shape[0], pos.shape[1]
     out = torch.empty_like(pos)
     rmsd = torch.empty(G, dtype=torch.float32, device=pos.device)
-    with torch.cuda.device(pos.device):
-        _lib.check(lib.agdiff_align_conformers(_lib.ptr(pos), _lib.ptr(idx), _lib.ptr(target), G, n, int(idx.shape[0]),
-                                               _lib.ptr(out), _lib.ptr(rmsd), _lib.stream_ptr()), "agdiff_align_conformers")
+    _lib.call("agdiff_align_conformers", pos, idx, target, G, n, int(idx.shape[0]), out, rmsd)
     return out, rmsd
 
 
@@ -110,13 +96,10 @@ def align_conformers(pos, atom_type, target, device="cuda"):
     labels (rdkit AlignMolConformers): proper rotation + translation, applied to all atoms.  Returns (aligned [G, n, 3],
     rmsd [G]: the heavy-atom RMSD to the target after alignment) as float32 tensors on `device`."""
     import torch
-    at = np.asarray(atom_type).reshape(-1)
-    n = at.shape[0]
-    heavy = np.nonzero(at != 1)[0].astype(np.int32)
-    if heavy.size == 0:
-        raise ValueError("molecule without heavy atoms")
-    p = _as_conformers(pos, n).to(device).contiguous()
-    t = _as_conformers(target, n).to(device).contiguous()
+    n = np.asarray(atom_type).reshape(-1).shape[0]
+    heavy = heavy_atoms(atom_type)
+    p = _lib.conformers(pos, n, device)
+    t = _lib.conformers(target, n, device)
     if t.shape[0] != 1:
         raise ValueError("target must be one conformer [n, 3]")
     return _align(p, torch.from_numpy(heavy).to(device), t[0])
@@ -124,7 +107,7 @@ def align_conformers(pos, atom_type, target, device="cuda"):
 
 def _valid_mask(valid, G):
     """bool numpy [G] from a bool mask (numpy or tensor); anything else is a ValueError, before any launch"""
-    v = valid.cpu().numpy() if hasattr(valid, "is_cuda") else np.asarray(valid)
+    v = as_host(valid)
     if v.dtype != np.bool_ or v.shape != (G,):
         raise ValueError("valid must be a bool mask with one entry per conformer: [%d] (got %s %s)" % (G, v.dtype, tuple(v.shape)))
     return v
@@ -153,9 +136,8 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     import torch
     if metric not in ("rmsd", "tfd"):
         raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
-    t = _check_threshold(threshold)
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
-    gen = _as_conformers(item["pos_gen"], n)
+    t = check_threshold(threshold, "RMSD")
+    gen = _lib.conformers(item["pos_gen"], num_atoms(item))
     G = gen.shape[0]
     if G == 0:
         raise ValueError("no conformers to prune")
@@ -164,9 +146,8 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     mask = None if valid is None else _valid_mask(valid, G)
     hand = None
     if fix_handedness:
-        from .stereo import fix_handedness as fix
         gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
-        hand = fix(item, gen)
+        hand = _fix_handedness(item, gen)
     sel = None
     if mask is not None:                                 # compacted on the device; the kernels below see the valid ones only
         gen = gen.to(device).contiguous()
@@ -212,7 +193,6 @@ def main(argv=None):
     agdiff_amd.validity.check_geometry (table bounds, default clash ratio) take no part in the walk: `cluster_<i>` is -1 for them;
     also writes `valid_<i>` int8 [G]."""
     import argparse
-    from .driver import load_testset
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", required=True)
     ap.add_argument("--testset", required=True)
@@ -228,22 +208,16 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     metric, threshold = ("rmsd", args.prune_rms) if args.prune_tfd is None else ("tfd", args.prune_tfd)
-    _check_threshold(threshold)
-    zs = np.load(args.samples)
+    check_threshold(threshold, "RMSD")
     out, total, left = {}, 0, 0
-    for mol in load_testset(args.testset):
+    for mol, item in sampled_items(args.testset, args.samples):
         i = mol["index"]
-        if "pos_gen_%d" % i not in zs.files:
-            continue
-        item = {"atom_type": mol["atom_type"], "pos_gen": zs["pos_gen_%d" % i], "edge_index": mol["edge_index"],
-                "edge_type": mol["edge_type"]}
         if args.fix_handedness:
             if mol.get("stereo") is None:
                 raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
             item["stereo"] = mol["stereo"]
         valid = None
         if args.drop_invalid:
-            from .validity import check_geometry
             valid = check_geometry(item, device=args.device)["valid"]       # (mirroring keeps every distance: before or after the fix)
             out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
         res = prune_conformers(item, threshold, align=args.align, device=args.device, fix_handedness=args.fix_handedness,

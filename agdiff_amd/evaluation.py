@@ -15,18 +15,11 @@ Data items are plain dicts (the reference uses PyG Data objects with an rdkit mo
     get an UPPER BOUND of GetBestRMS (COV a lower bound, MAT an upper bound).
 Force-field relaxation (use_force_field=True -> rdkit MMFF) is not available.
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
 from .config import Config
-
-
-def _as_conformers(pos, n):
-    import torch
-    t = pos if hasattr(pos, "is_cuda") else torch.as_tensor(np.asarray(pos))
-    return t.reshape(-1, n, 3).to(torch.float32)
+from .molecule import bonded_neighbours, bonds_of, field, heavy_atoms, num_atoms, reference_items, refine_colours
 
 
 def heavy_atom_automorphisms(atom_type, bond_index, bond_type, max_perms=65536):
@@ -42,32 +35,12 @@ def heavy_atom_automorphisms(atom_type, bond_index, bond_type, max_perms=65536):
     maps atoms class by class, checking every bond to the atoms already placed.  Raises if the group has more than
     `max_perms` elements (rdkit's own cap, maxMatches, is 1e6)."""
     at = np.asarray(atom_type).reshape(-1).astype(np.int64)
-    heavy = np.nonzero(at != 1)[0]
+    heavy = heavy_atoms(at)
     m = int(heavy.size)
-    if m == 0:
-        raise ValueError("molecule without heavy atoms")
-    new_id = np.full(at.shape[0], -1, dtype=np.int64)
-    new_id[heavy] = np.arange(m)
-    bi = np.asarray(bond_index).reshape(2, -1).astype(np.int64)
-    bt = np.asarray(bond_type).reshape(-1).astype(np.int64)
-    adj = [dict() for _ in range(m)]                 # neighbour -> bond type
-    for (u, v), ty in zip(bi.T, bt):
-        if ty <= 0 or ty >= 22 or u == v:
-            continue
-        a, b = new_id[u], new_id[v]
-        if a < 0 or b < 0:
-            continue
-        adj[a][int(b)] = int(ty)
-        adj[b][int(a)] = int(ty)
-    colour = [int(at[h]) for h in heavy]
-    for _ in range(m):                               # 1-WL refinement to a fixed point
-        sig = [(colour[i], tuple(sorted((colour[j], ty) for j, ty in adj[i].items()))) for i in range(m)]
-        ids = {s_: k for k, s_ in enumerate(sorted(set(sig)))}
-        new = [ids[s_] for s_ in sig]
-        if len(set(new)) == len(set(colour)):
-            colour = new
-            break
-        colour = new
+    new_id = {int(h): k for k, h in enumerate(heavy)}
+    full = bonded_neighbours(at.shape[0], bond_index, bond_type)
+    adj = [{new_id[j]: ty for j, ty in full[h].items() if j in new_id} for h in heavy]     # the heavy-atom graph
+    colour = refine_colours(at[heavy], adj)
     # visiting order: breadth first from the rarest colour class, so that every atom after the first of its component has
     # a placed neighbour to be checked against
     count = {c: colour.count(c) for c in set(colour)}
@@ -136,16 +109,12 @@ def selection_of(data):
     bond_type, or edge_index + edge_type) -- the molecule's own symmetry as GetBestRMS finds it (heavy_atom_automorphisms);
     None = the identity only."""
     at = np.asarray(data["atom_type"]).reshape(-1)
-    heavy = np.nonzero(at != 1)[0].astype(np.int32)
-    if heavy.size == 0:
-        raise ValueError("molecule without heavy atoms")
+    heavy = heavy_atoms(at)
     m = int(heavy.size)
-    get = (lambda k: data.get(k)) if isinstance(data, dict) else (lambda k: getattr(data, k, None))
-    perms = get("perms")
+    perms = field(data, "perms")
     if perms is None:       # the molecule's own symmetry, as GetBestRMS finds it, when the item carries its bonds
-        b_idx = get("bond_index") if get("bond_index") is not None else get("edge_index")
-        b_typ = get("bond_type") if get("bond_type") is not None else get("edge_type")
-        if b_idx is not None and b_typ is not None:
+        b_idx, b_typ = bonds_of(data, required=False)
+        if b_idx is not None:
             perms = heavy_atom_automorphisms(at, b_idx, b_typ)
     if perms is None:
         return at, heavy, None
@@ -174,21 +143,17 @@ def get_rmsd_confusion_matrix(data, useFF=False, device="cuda", hands=False):
     import torch
     if useFF:
         raise NotImplementedError("MMFF relaxation needs rdkit (covmat.py:27-29); not available here")
-    lib = _lib.load()
-    n = np.asarray(data["atom_type"]).reshape(-1).shape[0]
-    ref = _as_conformers(data["pos_ref"], n).to(device).contiguous()
-    gen = _as_conformers(data["pos_gen"], n).to(device).contiguous()
+    n = num_atoms(data)
+    ref = _lib.conformers(data["pos_ref"], n, device)
+    gen = _lib.conformers(data["pos_gen"], n, device)
     _, idx, P, pt = selection_on_device(data, device)
     m = idx.shape[0]
     R, G = ref.shape[0], gen.shape[0]
     out = torch.empty((R, G), dtype=torch.float32, device=device)
     mirror = torch.empty((R, G), dtype=torch.float32, device=device) if hands else None
     scratch = torch.empty((R + G) * (3 * m + 1), dtype=torch.float32, device=device)
-    name = "agdiff_rmsd_matrix_hands" if hands else "agdiff_rmsd_matrix"
-    outs = (_lib.ptr(out), _lib.ptr(mirror)) if hands else (_lib.ptr(out),)
-    with torch.cuda.device(out.device):
-        _lib.check(getattr(lib, name)(_lib.ptr(ref), _lib.ptr(gen), _lib.ptr(idx), _lib.ptr(pt), R, G, n, m, P, _lib.ptr(scratch),
-                                      *outs, _lib.stream_ptr()), name)
+    _lib.call("agdiff_rmsd_matrix_hands" if hands else "agdiff_rmsd_matrix", ref, gen, idx, pt, R, G, n, m, P, scratch,
+              *((out, mirror) if hands else (out,)))
     return (out, mirror) if hands else out
 
 
@@ -207,14 +172,11 @@ TFD_THRESHOLDS = np.arange(1, 61) / 100.0            # 0.01 .. 0.60: the TFD lie
 def matrix_minima(confusion):
     """(rmsd_ref_min [R], rmsd_gen_min [G]) of a confusion matrix on the GPU (covmat.py:135-136)."""
     import torch
-    lib = _lib.load()
     c = confusion.contiguous()
     R, G = c.shape
     rmin = torch.empty(R, dtype=torch.float32, device=c.device)
     gmin = torch.empty(G, dtype=torch.float32, device=c.device)
-    with torch.cuda.device(c.device):
-        _lib.check(lib.agdiff_matrix_minima(_lib.ptr(c), R, G, _lib.ptr(rmin), _lib.ptr(gmin), _lib.stream_ptr()),
-                   "agdiff_matrix_minima")
+    _lib.call("agdiff_matrix_minima", c, R, G, rmin, gmin)
     return rmin, gmin
 
 
@@ -288,9 +250,9 @@ class CovMatEvaluator(object):
                 continue
             if self.filter_disconnected and ("." in data.get("smiles", "")):
                 continue
-            n = int(np.asarray(data["atom_type"]).reshape(-1).shape[0])
-            ref = _as_conformers(data["pos_ref"], n)
-            gen = _as_conformers(data["pos_gen"], n)
+            n = num_atoms(data)
+            ref = _lib.conformers(data["pos_ref"], n)
+            gen = _lib.conformers(data["pos_gen"], n)
             num_gen = ref.shape[0] * self.ratio
             if gen.shape[0] < num_gen:
                 continue
@@ -361,23 +323,7 @@ def main(argv=None):
     ap.add_argument("--metric", default="rmsd", choices=["rmsd", "tfd"],
                     help="'tfd': COV / MAT over the torsion fingerprint deviation (thresholds 0.01 .. 0.60) instead of the RMSD")
     args = ap.parse_args(argv)
-    zs, zr = np.load(args.samples), np.load(args.refs)
-    items = []
-    for key in zr.files:
-        if not key.startswith("pos_ref_"):
-            continue
-        i = key[len("pos_ref_"):]
-        d = {"pos_ref": zr[key], "atom_type": zr["atom_type_" + i]}
-        if "smiles_" + i in zr.files:
-            d["smiles"] = str(zr["smiles_" + i])
-        if "perms_" + i in zr.files:
-            d["perms"] = zr["perms_" + i]
-        for k in ("bond_index", "bond_type", "edge_index", "edge_type"):
-            if "%s_%s" % (k, i) in zr.files:
-                d[k] = zr["%s_%s" % (k, i)]
-        if "pos_gen_" + i in zs.files:
-            d["pos_gen"] = zs["pos_gen_" + i]
-        items.append(d)
+    items = [item for _, item in reference_items(args.refs, args.samples)]
     res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand, metric=args.metric)(items)
     print_covmat_results(res)
     if args.either_hand:

@@ -17,31 +17,7 @@ filled in from any toolkit's chirality tags.
 import numpy as np
 
 from . import _lib
-
-
-def _bonded_neighbours(n, bond_index, bond_type):
-    """Per atom: {neighbour: bond type} over the bonds of type 1 .. 21 (the 2- / 3-hop entries of utils/transforms.py:12-71
-    have type >= 22 and are ignored, as evaluation.heavy_atom_automorphisms does)."""
-    bi = np.asarray(bond_index).reshape(2, -1).astype(np.int64)
-    bt = np.asarray(bond_type).reshape(-1).astype(np.int64)
-    adj = [dict() for _ in range(n)]
-    for (u, v), ty in zip(bi.T, bt):
-        if ty <= 0 or ty >= 22 or u == v:
-            continue
-        if not (0 <= u < n and 0 <= v < n):
-            raise ValueError("bond (%d, %d) outside the molecule's %d atoms" % (u, v, n))
-        adj[int(u)][int(v)] = int(ty)
-        adj[int(v)][int(u)] = int(ty)
-    return adj
-
-
-def _bonds_of(item):
-    get = (lambda k: item.get(k)) if isinstance(item, dict) else (lambda k: getattr(item, k, None))
-    b_idx = get("bond_index") if get("bond_index") is not None else get("edge_index")
-    b_typ = get("bond_type") if get("bond_type") is not None else get("edge_type")
-    if b_idx is None or b_typ is None:
-        raise ValueError("the item carries no bonds (bond_index + bond_type, or edge_index + edge_type)")
-    return b_idx, b_typ
+from .molecule import as_host, bonded_neighbours, bonds_of, field, num_atoms, refine_colours
 
 
 def tetrahedral_centres(atom_type, bond_index, bond_type):
@@ -52,16 +28,8 @@ def tetrahedral_centres(atom_type, bond_index, bond_type):
     substituents differ only beyond what 1-WL sees, which fixing the global hand does not need."""
     at = np.asarray(atom_type).reshape(-1).astype(np.int64)
     n = at.shape[0]
-    adj = _bonded_neighbours(n, bond_index, bond_type)
-    colour = [int(a) for a in at]
-    for _ in range(n):
-        sig = [(colour[i], tuple(sorted((colour[j], ty) for j, ty in adj[i].items()))) for i in range(n)]
-        ids = {s_: k for k, s_ in enumerate(sorted(set(sig)))}
-        new = [ids[s_] for s_ in sig]
-        stable = len(set(new)) == len(set(colour))
-        colour = new
-        if stable:
-            break
+    adj = bonded_neighbours(n, bond_index, bond_type)
+    colour = refine_colours(at, adj)
     centre, quads = [], []
     for i in range(n):
         nb = sorted(adj[i])
@@ -95,16 +63,15 @@ def parities_from_conformers(pos, quads):
 def stereo_quads(item):
     """(quads int32 [C, 4], target int8 [C]) of an item's `stereo` tags: one row per atom with stereo != 0, which must have
     exactly four bonded neighbours."""
-    get = (lambda k: item.get(k)) if isinstance(item, dict) else (lambda k: getattr(item, k, None))
-    stereo = get("stereo")
+    stereo = field(item, "stereo")
     if stereo is None:
         raise ValueError("the item carries no `stereo` tags (int8 [n]: target parity at the stereocentres, 0 elsewhere; "
                          "python -m agdiff_amd.stereo adds them to a test set from reference conformers)")
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    n = num_atoms(item)
     st = np.asarray(stereo).reshape(-1)
     if st.shape[0] != n:
         raise ValueError("stereo has %d entries for %d atoms" % (st.shape[0], n))
-    adj = _bonded_neighbours(n, *_bonds_of(item))
+    adj = bonded_neighbours(n, *bonds_of(item))
     quads, target = [], []
     for i in np.nonzero(st)[0]:
         nb = sorted(adj[int(i)])
@@ -120,13 +87,10 @@ def chiral_verdict(pos, quads, target, want_vol=True):
     """agdiff_chiral_verdict on pos [G, n, 3] (float32, contiguous, on the GPU): (verdict int32 [G], vol float32 [G, C] or None).
     quads int32 [C, 4] / target int8 [C]: numpy or tensors.  Atom indices are checked here, on the host."""
     import torch
-    lib = _lib.load()
     G, n = int(pos.shape[0]), int(pos.shape[1])
     dev = pos.device
-    q = quads.cpu().numpy() if hasattr(quads, "is_cuda") else np.asarray(quads)
-    q = np.ascontiguousarray(q.reshape(-1, 4), dtype=np.int32)
-    t = target.cpu().numpy() if hasattr(target, "is_cuda") else np.asarray(target)
-    t = np.ascontiguousarray(t.reshape(-1), dtype=np.int8)
+    q = as_host(quads, np.int32).reshape(-1, 4)
+    t = as_host(target, np.int8).reshape(-1)
     C = q.shape[0]
     if t.shape[0] != C:
         raise ValueError("%d quads but %d targets" % (C, t.shape[0]))
@@ -136,10 +100,7 @@ def chiral_verdict(pos, quads, target, want_vol=True):
     tt = torch.from_numpy(t).to(dev) if C else None
     verdict = torch.empty(G, dtype=torch.int32, device=dev)
     vol = torch.empty((G, C), dtype=torch.float32, device=dev) if want_vol else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.agdiff_chiral_verdict(_lib.ptr(pos), _lib.ptr(qt), _lib.ptr(tt), G, n, C,
-                                             _lib.ptr(vol if (vol is not None and vol.numel()) else None), _lib.ptr(verdict),
-                                             _lib.stream_ptr()), "agdiff_chiral_verdict")
+    _lib.call("agdiff_chiral_verdict", pos, qt, tt, G, n, C, vol if (vol is not None and vol.numel()) else None, verdict)
     return verdict, vol
 
 
@@ -147,40 +108,27 @@ def mirror_conformers(pos, flags):
     """agdiff_mirror_conformers: inverts, in place, every conformer g of pos [G, n, 3] (float32, contiguous, on the GPU) with
     flags[g] != 0 through the centroid of all its atoms.  Returns pos."""
     import torch
-    lib = _lib.load()
-    _device_conformers(pos)
+    _lib.require_device_conformers(pos)
     f = flags.to(device=pos.device, dtype=torch.int32).contiguous()
     if f.shape != (pos.shape[0],):
         raise ValueError("flags must have one entry per conformer")
-    with torch.cuda.device(pos.device):
-        _lib.check(lib.agdiff_mirror_conformers(_lib.ptr(pos), _lib.ptr(f), int(pos.shape[0]), int(pos.shape[1]),
-                                                _lib.stream_ptr()), "agdiff_mirror_conformers")
+    _lib.call("agdiff_mirror_conformers", pos, f, int(pos.shape[0]), int(pos.shape[1]))
     return pos
-
-
-def _device_conformers(pos):
-    import torch
-    if not (hasattr(pos, "is_cuda") and pos.is_cuda and pos.dtype == torch.float32 and pos.dim() == 3 and pos.shape[2] == 3
-            and pos.is_contiguous()):
-        raise ValueError("pos must be a contiguous float32 tensor [G, n, 3] on the GPU")
 
 
 def handedness(item, pos, device="cuda"):
     """(verdict int32 [G], vol float32 [G, C]) on the device for the conformers pos [G, n, 3] (or [G*n, 3]; numpy or tensor) of
     `item` (atom_type, bonds, stereo): + 1 every tagged centre has its target parity, - 1 every one is inverted (the conformer
     is the mirror image), 0 the centres disagree or one is flat -- a diastereomer, which reflection cannot fix."""
-    from .evaluation import _as_conformers
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
     quads, target = stereo_quads(item)
-    p = _as_conformers(pos, n).to(device).contiguous()
-    return chiral_verdict(p, quads, target)
+    return chiral_verdict(_lib.conformers(pos, num_atoms(item), device), quads, target)
 
 
 def fix_handedness(item, pos):
     """Mirrors, in place, the conformers of pos [G, n, 3] (contiguous float32 tensor on the GPU) whose verdict is - 1 and returns
     the verdict (int32 [G]) as it was BEFORE mirroring: - 1 was mirrored, 0 is left as sampled, + 1 was right."""
-    _device_conformers(pos)
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
+    _lib.require_device_conformers(pos)
+    n = num_atoms(item)
     if pos.shape[1] != n:
         raise ValueError("pos has %d atoms per conformer, the item %d" % (pos.shape[1], n))
     quads, target = stereo_quads(item)

@@ -5,7 +5,7 @@ changes and does not say which bond turned; the TFD (rdkit Chem.TorsionFingerpri
 rotatable bonds' dihedrals, lies in [0, 1] whatever the molecule's size, and one threshold (0.2, say) serves a whole test set.
 rdkit is not a dependency and the reference never computes a TFD, so the quantity is defined here in plain terms:
 
-  bonds       the item's bond list entries of type 1 .. 21 (stereo._bonded_neighbours), hydrogens dropped
+  bonds       the item's bond list entries of type 1 .. 21 (molecule.bonded_neighbours), hydrogens dropped
   rotatable   a heavy - heavy bond (u, v), u < v, of type 1 that is a bridge of the heavy-atom graph (in no ring), with at least two
               heavy neighbours at both ends, neither end carrying a type-3 (triple) bond; ordered by (u, v); T of them
   columns     for every rotatable bond every heavy neighbour a of u (a != v) and b of v (b != u): the quad (a, u, v, b); ordered by
@@ -28,8 +28,9 @@ Angles and matrices are computed on the GPU (csrc/eval.hip: agdiff_torsion_angle
 import numpy as np
 
 from . import _lib
-from .evaluation import _as_conformers, selection_of
-from .stereo import _bonded_neighbours, _bonds_of
+from .ensemble import bits_pitch
+from .evaluation import selection_of
+from .molecule import as_host, bonded_neighbours, bonds_of, check_threshold, num_atoms, sampled_items
 
 MAX_COLUMNS = _lib.DEFINES["AGDIFF_TFD_MAX_COLUMNS"]
 
@@ -38,7 +39,7 @@ def _heavy_graph(atom_type, bond_index, bond_type):
     """(heavy bool [n], adj: per atom {neighbour: type} over ALL bonded atoms, hadj: per atom the sorted heavy neighbours)"""
     at = np.asarray(atom_type).reshape(-1).astype(np.int64)
     n = at.shape[0]
-    adj = _bonded_neighbours(n, bond_index, bond_type)
+    adj = bonded_neighbours(n, bond_index, bond_type)
     heavy = at != 1
     hadj = [sorted(j for j in adj[i] if heavy[j]) if heavy[i] else [] for i in range(n)]
     return heavy, adj, hadj
@@ -102,7 +103,7 @@ def torsion_table(item):
     bond, and the distinct rows of the column mappings under the molecule's heavy-atom automorphisms (the item's `perms`, or its
     bonds through evaluation.selection_of, exactly as for the RMSD), row 0 = the canonical columns.  T = 0: ([0, 4], [1, 0])."""
     at = np.asarray(item["atom_type"]).reshape(-1)
-    bonds, per_bond = _columns(at, *_bonds_of(item))
+    bonds, per_bond = _columns(at, *bonds_of(item))
     T = len(bonds)
     cols = [q for qs in per_bond for q in qs]
     where = {q: k for k, q in enumerate(cols)}
@@ -131,28 +132,15 @@ def torsion_angles(pos, quads):
     (int32 [Q, 4], numpy or tensor) in radians in [-pi, pi]; NaN for a degenerate quad, a coordinate that is not finite or an atom
     index outside [0, n)."""
     import torch
-    from .stereo import _device_conformers
-    _device_conformers(pos)
-    lib = _lib.load()
+    _lib.require_device_conformers(pos)
     G, n = int(pos.shape[0]), int(pos.shape[1])
-    q = quads.cpu().numpy() if hasattr(quads, "is_cuda") else np.asarray(quads)
-    q = np.ascontiguousarray(q.reshape(-1, 4), dtype=np.int32)
+    q = as_host(quads, np.int32).reshape(-1, 4)
     Q = q.shape[0]
     out = torch.empty((G, Q), dtype=torch.float32, device=pos.device)
     if G == 0 or Q == 0:
         return out
-    qt = torch.from_numpy(q).to(pos.device)
-    with torch.cuda.device(pos.device):
-        _lib.check(lib.agdiff_torsion_angles(_lib.ptr(pos), _lib.ptr(qt), G, n, Q, _lib.ptr(out), _lib.stream_ptr()),
-                   "agdiff_torsion_angles")
+    _lib.call("agdiff_torsion_angles", pos, torch.from_numpy(q).to(pos.device), G, n, Q, out)
     return out
-
-
-def _check_threshold(threshold):
-    t = float(threshold)
-    if not t >= 0.0:
-        raise ValueError("the TFD threshold must be >= 0 (got %r)" % (threshold,))
-    return t
 
 
 def tfd_from_angles(ang_x, ang_y, tmap, weights=None, threshold=None, want_out=True, want_mirror=False):
@@ -161,12 +149,11 @@ def tfd_from_angles(ang_x, ang_y, tmap, weights=None, threshold=None, want_out=T
     layout of ensemble.bits_pitch(G) / ensemble.unpack_bits).  tmap int32 [P, T] (numpy), weights [T] > 0 or None.  The entries of
     tmap are checked against Q here, on the host; more than AGDIFF_TFD_MAX_COLUMNS columns: AgdiffLimitError."""
     import torch
-    from .ensemble import bits_pitch
-    lib = _lib.load()
-    dev = ang_x.device
     for a in (ang_x, ang_y):
-        if not (a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.is_contiguous() and a.device == dev):
-            raise ValueError("angle tables must be contiguous float32 tensors [conformers, Q] on one GPU")
+        _lib.require_device_table(a, "angle tables must be contiguous float32 tensors [conformers, Q] on one GPU")
+    dev = ang_x.device
+    if ang_y.device != dev:
+        raise ValueError("angle tables must be contiguous float32 tensors [conformers, Q] on one GPU")
     R, Q, G = int(ang_x.shape[0]), int(ang_x.shape[1]), int(ang_y.shape[0])
     if int(ang_y.shape[1]) != Q:
         raise ValueError("angle tables of %d and %d columns" % (Q, ang_y.shape[1]))
@@ -192,16 +179,13 @@ def tfd_from_angles(ang_x, ang_y, tmap, weights=None, threshold=None, want_out=T
     if R == 0 or G == 0:
         return out, mirror, bits
     tt = torch.from_numpy(tm).to(dev) if T else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.agdiff_tfd_matrix(_lib.ptr(ang_x if Q else None), _lib.ptr(ang_y if Q else None), _lib.ptr(tt), _lib.ptr(wt),
-                                         R, G, Q, T, P, 0.0 if threshold is None else _check_threshold(threshold), _lib.ptr(out),
-                                         _lib.ptr(mirror), _lib.ptr(bits), _lib.stream_ptr()), "agdiff_tfd_matrix")
+    _lib.call("agdiff_tfd_matrix", ang_x if Q else None, ang_y if Q else None, tt, wt, R, G, Q, T, P,
+              0.0 if threshold is None else check_threshold(threshold, "TFD"), out, mirror, bits)
     return out, mirror, bits
 
 
 def _angles_of(item, key, quads, device):
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
-    pos = _as_conformers(item[key], n).to(device).contiguous()
+    pos = _lib.conformers(item[key], num_atoms(item), device)
     return pos, torsion_angles(pos, quads)
 
 
@@ -226,7 +210,7 @@ def _self_tfd(item, device, threshold=None, weights=None, want_out=True):
 def tfd_self(item, threshold=None, weights=None, device="cuda"):
     """(out [G, G], bits): the TFD between the item's generated conformers -- exactly symmetric -- and, with a threshold, the packed
     adjacency `out <= threshold` (int64 [G, pitch / 8]; ensemble.unpack_bits, ensemble.leader_prune), else None."""
-    _, out, bits = _self_tfd(item, device, threshold=None if threshold is None else _check_threshold(threshold), weights=weights)
+    _, out, bits = _self_tfd(item, device, threshold=None if threshold is None else check_threshold(threshold, "TFD"), weights=weights)
     return out, bits
 
 
@@ -236,21 +220,17 @@ def main(argv=None):
     `torsion_quads_<i>` int32 [T, 4], the canonical quad (a, u, v, b) of each rotatable bond, and `torsion_<i>` float32 [G, T], their
     dihedrals in radians in every conformer (+ `name_<i>`): what a torsion histogram or a phi / psi plot is drawn from."""
     import argparse
-    from .driver import load_testset
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", required=True)
     ap.add_argument("--testset", required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
-    zs = np.load(args.samples)
     out, mols, total = {}, 0, 0
-    for mol in load_testset(args.testset):
+    for mol, item in sampled_items(args.testset, args.samples):
         i = mol["index"]
-        if "pos_gen_%d" % i not in zs.files:
-            continue
         _, quads = rotatable_bonds(mol["atom_type"], mol["edge_index"], mol["edge_type"])
-        pos = _as_conformers(zs["pos_gen_%d" % i], mol["atom_type"].shape[0]).to(args.device).contiguous()
+        pos = _lib.conformers(item["pos_gen"], num_atoms(item), args.device)
         out["torsion_quads_%d" % i] = quads
         out["torsion_%d" % i] = torsion_angles(pos, quads).cpu().numpy()
         out["name_%d" % i] = np.str_(mol["name"])

@@ -17,6 +17,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .molecule import as_host
 
 
 def ring_spans(done, ready, ring_rows):
@@ -54,8 +55,8 @@ def _selection(N, select, atom_type):
     if select is None:
         if atom_type is None:
             return np.ones(N, dtype=np.uint8)
-        select = np.asarray(atom_type.cpu() if hasattr(atom_type, "cpu") else atom_type).reshape(-1) != 1
-    sel = np.asarray(select.cpu() if hasattr(select, "cpu") else select).reshape(-1)
+        select = as_host(atom_type).reshape(-1) != 1
+    sel = as_host(select).reshape(-1)
     if sel.shape[0] != N:
         raise ValueError("the selection has %d entries for %d atoms" % (sel.shape[0], N))
     return np.ascontiguousarray(sel != 0, dtype=np.uint8)
@@ -76,14 +77,13 @@ class RmsdTracker:
 
     def __init__(self, target, select, graph_ptr, steps, device, mirror=False, atom_type=None):
         import torch
-        gp = np.ascontiguousarray(graph_ptr.cpu().numpy() if hasattr(graph_ptr, "cpu") else graph_ptr, dtype=np.int32).reshape(-1)
+        gp = as_host(graph_ptr, np.int32).reshape(-1)
         self.G, self.N = gp.shape[0] - 1, int(gp[-1])
-        tgt = torch.as_tensor(np.asarray(target.cpu() if hasattr(target, "cpu") else target, dtype=np.float32))
+        tgt = torch.from_numpy(as_host(target, np.float32))
         if tuple(tgt.shape) != (self.N, 3):
             raise ValueError("the target has shape %s, the batch %d atoms: expected [%d, 3]" % (tuple(tgt.shape), self.N, self.N))
         sel = _selection(self.N, select, atom_type)
         _check_selected(sel, gp)
-        self.lib = _lib.load()
         self.target = tgt.to(device).contiguous()
         self.select = torch.from_numpy(sel).to(device)
         self.graph_ptr = torch.from_numpy(gp).to(device)
@@ -97,9 +97,8 @@ class RmsdTracker:
             return
         out = self.rows[first_row:first_row + count]
         mir = self.rows_mirror[first_row:first_row + count] if self.rows_mirror is not None else None
-        _lib.check(self.lib.agdiff_traj_rmsd(_lib.ptr(frames), int(frame_stride), _lib.ptr(self.target), _lib.ptr(self.select),
-                                             _lib.ptr(self.graph_ptr), int(count), self.G, self.N, _lib.ptr(out), _lib.ptr(mir),
-                                             _lib.stream_ptr()), "agdiff_traj_rmsd")
+        _lib.call("agdiff_traj_rmsd", frames, int(frame_stride), self.target, self.select, self.graph_ptr, int(count), self.G, self.N,
+                  out, mir)
 
 
 def rmsd_to_target(frames, target, batch, select=None, atom_type=None, mirror=False, device="cuda"):
@@ -113,7 +112,7 @@ def rmsd_to_target(frames, target, batch, select=None, atom_type=None, mirror=Fa
     if fr.dim() != 3 or fr.shape[2] != 3:
         raise ValueError("frames must have shape [S, N, 3], got %s" % (tuple(fr.shape),))
     S, N = int(fr.shape[0]), int(fr.shape[1])
-    b = np.asarray(batch.cpu() if hasattr(batch, "cpu") else batch).reshape(-1)
+    b = as_host(batch).reshape(-1)
     if b.shape[0] != N:
         raise ValueError("batch has %d entries, the frames %d atoms" % (b.shape[0], N))
     gp, G = _graph_ptr(b)
@@ -128,12 +127,10 @@ def rmsd_to_target(frames, target, batch, select=None, atom_type=None, mirror=Fa
     if not (fr.stride(2) == 1 and fr.stride(1) == 3 and (S <= 1 or fr.stride(0) >= 3 * N)):
         fr = fr.contiguous()
     stride = int(fr.stride(0)) if S > 1 else 3 * N
-    with torch.cuda.device(fr.device):
-        tr = RmsdTracker(target, sel, gp, S, fr.device, mirror=mirror)
-        if S:
-            _lib.check(tr.lib.agdiff_traj_rmsd(ctypes.c_void_p(fr.data_ptr()), stride, _lib.ptr(tr.target), _lib.ptr(tr.select), _lib.ptr(tr.graph_ptr),
-                                               S, G, N, _lib.ptr(tr.rows), _lib.ptr(tr.rows_mirror), _lib.stream_ptr()),
-                       "agdiff_traj_rmsd")
+    tr = RmsdTracker(target, sel, gp, S, fr.device, mirror=mirror)
+    if S:       # (the address as it is: `ptr` would refuse the strided view)
+        _lib.call("agdiff_traj_rmsd", ctypes.c_void_p(fr.data_ptr()), stride, tr.target, tr.select, tr.graph_ptr, S, G, N, tr.rows,
+                  tr.rows_mirror)
     return (tr.rows, tr.rows_mirror) if mirror else tr.rows
 
 

@@ -28,8 +28,7 @@ false-positive rate is claimed.
 import numpy as np
 
 from . import _lib
-from .evaluation import _as_conformers
-from .stereo import _bonds_of
+from .molecule import as_host, bonds_of, field, num_atoms, sampled_items
 
 CLASH_SLICE = _lib.DEFINES["AGDIFF_CLASH_SLICE"]
 
@@ -98,8 +97,8 @@ def _check_exclusions(n, ex_ptr, ex_idx):
 
 def _bond_pairs(item, types):
     """sorted unique (i, j), i < j, of the item's edge entries whose type passes `types`; the item must carry bonds"""
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
-    i, j, t = _edges(n, *_bonds_of(item))
+    n = num_atoms(item)
+    i, j, t = _edges(n, *bonds_of(item))
     sel = types(t)
     a, b = np.minimum(i[sel], j[sel]), np.maximum(i[sel], j[sel])
     key = np.unique(a * n + b)
@@ -123,12 +122,10 @@ def bounds_from_references(item, slack=0.05):
     the references.  Host work in float64."""
     if not 0.0 <= float(slack) < 1.0:
         raise ValueError("slack must be in [0, 1) (got %r)" % (slack,))
-    get = (lambda k: item.get(k)) if isinstance(item, dict) else (lambda k: getattr(item, k, None))
-    if get("pos_ref") is None:
+    if field(item, "pos_ref") is None:
         raise ValueError("the item carries no reference conformers (pos_ref)")
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
-    ref = get("pos_ref")
-    ref = (ref.detach().cpu().numpy() if hasattr(ref, "detach") else np.asarray(ref)).astype(np.float64).reshape(-1, n, 3)
+    n = num_atoms(item)
+    ref = as_host(field(item, "pos_ref"), np.float64).reshape(-1, n, 3)
     if ref.shape[0] == 0 or not np.isfinite(ref).all():
         raise ValueError("pos_ref must hold at least one conformer and be finite")
     pairs = _bond_pairs(item, lambda t: ((t >= 1) & (t <= 21)) | (t == 23))
@@ -136,38 +133,30 @@ def bounds_from_references(item, slack=0.05):
     return pairs, ((1.0 - float(slack)) * d.min(0)).astype(np.float32), ((1.0 + float(slack)) * d.max(0)).astype(np.float32)
 
 
-def _host(a):
-    return a.cpu().numpy() if hasattr(a, "is_cuda") else np.asarray(a)
-
-
 def pair_bounds(pos, pairs, lo, hi, want_dist=False):
     """agdiff_pair_bounds on pos [G, n, 3] (float32, contiguous, on the GPU): (worst float32 [G], worst_pair int32 [G], n_bad int32
     [G], dist float32 [G, K] or None).  pairs int32 [K, 2], lo / hi [K] (numpy or tensors; no NaN, lo <= hi).  A pair naming an atom
     outside [0, n) is allowed: its violation is +inf and nothing is read."""
     import torch
-    from .stereo import _device_conformers
-    _device_conformers(pos)
+    _lib.require_device_conformers(pos)
     G, n = int(pos.shape[0]), int(pos.shape[1])
     if n == 0:
         raise ValueError("conformers without atoms")
-    pr = np.array(_host(pairs).reshape(-1, 2), dtype=np.int32)          # (copies: the caller's arrays may be read-only)
+    pr = as_host(pairs, np.int32).reshape(-1, 2)                        # (copies: the caller's arrays may be read-only)
     K = pr.shape[0]
-    lo_, hi_ = (np.array(_host(x).reshape(-1), dtype=np.float32) for x in (lo, hi))
+    lo_, hi_ = (as_host(x, np.float32).reshape(-1) for x in (lo, hi))
     if lo_.shape[0] != K or hi_.shape[0] != K:
         raise ValueError("%d pairs but %d lower and %d upper bounds" % (K, lo_.shape[0], hi_.shape[0]))
     if K and not (lo_ <= hi_).all():
         raise ValueError("every pair needs lo <= hi (and neither may be NaN)")
-    lib = _lib.load()
     dev = pos.device
     worst = torch.empty(G, dtype=torch.float32, device=dev)
     worst_pair, n_bad = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
     dist = torch.empty((G, K), dtype=torch.float32, device=dev) if want_dist else None
     if G:
         pt, lt, ht = ((torch.from_numpy(x).to(dev) if K else None) for x in (pr, lo_, hi_))
-        with torch.cuda.device(dev):
-            _lib.check(lib.agdiff_pair_bounds(_lib.ptr(pos), _lib.ptr(pt), _lib.ptr(lt), _lib.ptr(ht), G, n, K,
-                                              _lib.ptr(dist if (dist is not None and dist.numel()) else None), _lib.ptr(worst),
-                                              _lib.ptr(worst_pair), _lib.ptr(n_bad), _lib.stream_ptr()), "agdiff_pair_bounds")
+        _lib.call("agdiff_pair_bounds", pos, pt, lt, ht, G, n, K, dist if (dist is not None and dist.numel()) else None, worst,
+                  worst_pair, n_bad)
     return worst, worst_pair, n_bad, dist
 
 
@@ -177,20 +166,18 @@ def clash_scan(pos, radius, ex_ptr, ex_idx, thresh, want_scratch=False):
     int32 (numpy: `exclusions`) are checked here, on the host, for range, ascending rows and symmetry -- the kernel does not.  More than
     AGDIFF_MAX_ATOMS_LARGE atoms: AgdiffLimitError."""
     import torch
-    from .stereo import _device_conformers
-    _device_conformers(pos)
+    _lib.require_device_conformers(pos)
     G, n = int(pos.shape[0]), int(pos.shape[1])
     if n == 0:
         raise ValueError("conformers without atoms")
     th = float(thresh)
     if not (th >= 0.0 and np.isfinite(th)):
         raise ValueError("the clash threshold must be finite and >= 0 (got %r)" % (thresh,))
-    rad = np.array(_host(radius).reshape(-1), dtype=np.float32)
+    rad = as_host(radius, np.float32).reshape(-1)
     if rad.shape[0] != n or not (np.isfinite(rad).all() and (rad > 0).all()):
         raise ValueError("radius must hold %d finite numbers > 0" % n)
-    ptr, idx = _host(ex_ptr), _host(ex_idx)
+    ptr, idx = as_host(ex_ptr), as_host(ex_idx)
     _check_exclusions(n, ptr, idx)
-    lib = _lib.load()
     dev = pos.device
     S = (n + CLASH_SLICE - 1) // CLASH_SLICE
     scratch = torch.empty((G, S, 4), dtype=torch.int32, device=dev)
@@ -200,17 +187,14 @@ def clash_scan(pos, radius, ex_ptr, ex_idx, thresh, want_scratch=False):
     rt, pt = torch.from_numpy(rad).to(dev), torch.from_numpy(np.array(ptr)).to(dev)
     it = torch.from_numpy(np.array(idx)).to(dev) if idx.size else None
     if G:
-        with torch.cuda.device(dev):
-            _lib.check(lib.agdiff_clash_scan(_lib.ptr(pos), _lib.ptr(rt), _lib.ptr(pt), _lib.ptr(it), G, n, th, _lib.ptr(scratch),
-                                             _lib.ptr(min_ratio), _lib.ptr(min_pair), _lib.ptr(n_clash), _lib.stream_ptr()),
-                       "agdiff_clash_scan")
+        _lib.call("agdiff_clash_scan", pos, rt, pt, it, G, n, th, scratch, min_ratio, min_pair, n_clash)
     return (min_ratio, min_pair, n_clash, scratch) if want_scratch else (min_ratio, min_pair, n_clash)
 
 
 def _tables(item, bounds, table_kw):
     """(pairs, lo, hi, radius, ex_ptr, ex_idx) of an item: host work, and every ValueError an item can cause, before any launch"""
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
-    b_idx, b_typ = _bonds_of(item)                    # (an item without bonds: ValueError)
+    n = num_atoms(item)
+    b_idx, b_typ = bonds_of(item)                     # (an item without bonds: ValueError)
     if isinstance(bounds, str):
         if bounds == "table":
             pairs, lo, hi = bounds_from_table(item, **table_kw)
@@ -239,11 +223,10 @@ def check_geometry(item, bounds="table", clash=0.60, device="cuda", **table_kw):
         n_clash    int32 [G]      pairs below `clash`"""
     import torch
     pairs, lo, hi, radius, ex_ptr, ex_idx = _tables(item, bounds, table_kw)
-    n = np.asarray(item["atom_type"]).reshape(-1).shape[0]
-    pos = _as_conformers(item["pos_gen"], n).to(device).contiguous()
+    pos = _lib.conformers(item["pos_gen"], num_atoms(item), device)
     worst, worst_pair, n_bad, _ = pair_bounds(pos, pairs, lo, hi)
     min_ratio, min_pair, n_clash = clash_scan(pos, radius, ex_ptr, ex_idx, clash)
-    pt = torch.from_numpy(np.array(_host(pairs).reshape(-1, 2), dtype=np.int32)).to(pos.device)
+    pt = torch.from_numpy(as_host(pairs, np.int32).reshape(-1, 2)).to(pos.device)
     pt = torch.cat([pt, torch.full((1, 2), -1, dtype=torch.int32, device=pos.device)])      # (row -1 = K: no pair)
     return {"valid": (n_bad == 0) & (n_clash == 0), "bond_dev": worst, "bond_pair": pt[worst_pair.long()], "n_bad": n_bad,
             "clash": min_ratio, "clash_pair": min_pair, "n_clash": n_clash}
@@ -256,7 +239,6 @@ def main(argv=None):
     `clash_<i>` float32 [G], `clash_pair_<i>` int32 [G, 2], `n_clash_<i>` int32 [G] (+ `name_<i>`).  --refs (`pos_ref_<i>` [R, n, 3]):
     the bounds come from the molecule's reference conformers (bounds_from_references) instead of the covalent-radius table."""
     import argparse
-    from .driver import load_testset
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", required=True)
     ap.add_argument("--testset", required=True)
@@ -267,15 +249,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not (args.clash >= 0.0 and np.isfinite(args.clash)):
         ap.error("--clash must be finite and >= 0")
-    zs = np.load(args.samples)
     zr = np.load(args.refs, allow_pickle=False) if args.refs else None
     out, mols, confs, invalid, by_bond, by_clash = {}, 0, 0, 0, 0, 0
-    for mol in load_testset(args.testset):
+    for mol, item in sampled_items(args.testset, args.samples):
         i = mol["index"]
-        if "pos_gen_%d" % i not in zs.files:
-            continue
-        item = {"atom_type": mol["atom_type"], "pos_gen": zs["pos_gen_%d" % i], "edge_index": mol["edge_index"],
-                "edge_type": mol["edge_type"]}
         if zr is not None:
             if "pos_ref_%d" % i not in zr.files:
                 raise ValueError("--refs: %s has no pos_ref_%d" % (args.refs, i))

@@ -127,3 +127,55 @@ def test_rmsd_is_symmetry_aware_when_the_item_carries_its_bonds():
         want = CO.get_rmsd_confusion_matrix(ref, gen, heavy, list(perms))
         assert np.abs(sym - want).max() < ATOL, name
         assert sym[2, 1] < 1e-4 < plain[2, 1] and (sym <= plain + ATOL).all(), name
+
+
+def test_call_launches_on_the_current_stream():
+    """_lib.call, the launch path of the post-sampling modules: agdiff_matrix_minima on a 3 x 5 matrix equals torch.min along both
+    axes, on the default stream and on a side stream.  On the side stream the matrix is the end of a chain of kernels queued
+    there, and only that stream is synchronised: a launch on another stream would not be ordered after the chain."""
+    from agdiff_amd import _lib
+    base = torch.randn(3, 5, device="cuda")
+    rmin, gmin = torch.empty(3, device="cuda"), torch.empty(5, device="cuda")
+    assert _lib.call("agdiff_matrix_minima", base, 3, 5, rmin, gmin) is None
+    torch.cuda.synchronize()
+    assert torch.equal(rmin, base.min(1).values) and torch.equal(gmin, base.min(0).values)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        c = base
+        for k in range(64):
+            c = c * -1.0 + float(k)
+        rmin2, gmin2 = torch.full((3,), float("nan"), device="cuda"), torch.full((5,), float("nan"), device="cuda")
+        _lib.call("agdiff_matrix_minima", c, 3, 5, rmin2, gmin2)
+    side.synchronize()
+    assert torch.equal(rmin2, c.min(1).values) and torch.equal(gmin2, c.min(0).values)
+    torch.cuda.synchronize()
+
+
+def test_call_maps_a_limit_status_to_the_entry_points_name():
+    from agdiff_amd import _lib
+    from agdiff_amd.ensemble import bits_pitch
+    G = _lib.DEFINES["AGDIFF_PRUNE_MAX_CONFS"] + 1                           # refused on the host, before any launch
+    bits = torch.zeros((G, bits_pitch(G) // 8), dtype=torch.int64, device="cuda")
+    keep, leader, count = (torch.empty(G, dtype=torch.int32, device="cuda") for _ in range(3))
+    n_kept = torch.empty(1, dtype=torch.int32, device="cuda")
+    with pytest.raises(_lib.AgdiffLimitError, match="agdiff_leader_prune"):
+        _lib.call("agdiff_leader_prune", bits, G, keep, leader, count, n_kept)
+
+
+def test_rmsd_to_target_reads_a_strided_view_in_place():
+    """The one launch that hands _lib.call a raw address: frames [S, N, 3] cut from a [S, N + 2, 3] buffer give the bits of their
+    contiguous copy."""
+    from agdiff_amd.trajectory import rmsd_to_target
+    S, N = 3, 7
+    g = torch.Generator().manual_seed(4)
+    buf = (torch.randn(S, N + 2, 3, generator=g) * 2.0).cuda()
+    target = torch.randn(N, 3, generator=g) * 2.0
+    batch = np.array([0, 0, 0, 0, 1, 1, 1])
+    view = buf[:, :N]
+    assert not view.is_contiguous() and view.stride(0) == 3 * (N + 2)
+    got = rmsd_to_target(view, target, batch, mirror=True)
+    want = rmsd_to_target(view.contiguous(), target, batch, mirror=True)
+    for a, b in zip(got, want):
+        assert a.shape == (S, 2) and torch.isfinite(a).all() and torch.equal(a, b)
+    assert torch.equal(buf[:, :N], view) and (got[0] > 0).all()
