@@ -809,6 +809,186 @@ __global__ void __launch_bounds__(64) k_clash_finish(const int32_t* __restrict__
   }
 }
 
+// ---- geometry repair: the atoms of a conformer that fails the two checks above moved into its distance bounds (not MMFF: no
+// energies, no torsions, no electrostatics; include/agdiff_hip.h has the rule) --
+
+#define AG_RELAX_THREADS 256
+
+// (or of the flags, max of r) over the workgroup, in every thread: the xor butterfly in each wave, the four waves by thread 0 into
+// ONE LDS value each, which every thread reads after the second barrier -- what a uniform loop exit needs.  The barriers also
+// publish whatever the threads wrote to LDS before the call.
+__device__ __forceinline__ void ag_relax_reduce(int& flags, double& r, int* s_wf, double* s_wr, int* s_flags, double* s_r) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    flags |= __shfl_xor(flags, o);
+    r = fmax(r, __shfl_xor(r, o));
+  }
+  if ((t & 63) == 0) { s_wf[t >> 6] = flags; s_wr[t >> 6] = r; }
+  __syncthreads();
+  if (t == 0) {
+    int f = s_wf[0];
+    double m = s_wr[0];
+#pragma unroll
+    for (int w = 1; w < AG_RELAX_THREADS / 64; ++w) { f |= s_wf[w]; m = fmax(m, s_wr[w]); }
+    *s_flags = f;
+    *s_r = m;
+  }
+  __syncthreads();
+  flags = *s_flags;
+  r = *s_r;
+}
+
+// a += h u, u the unit vector of (dx, dy, dz) of length d; atoms closer than 1e-9 part along x, the lower index towards +x
+__device__ __forceinline__ void ag_relax_add(double& ax, double& ay, double& az, double h, double dx, double dy, double dz, double d,
+                                             bool lower) {
+  if (d < 1e-9) {
+    ax += lower ? h : -h;
+  } else {
+    const double q = h / d;
+    ax += q * dx; ay += q * dy; az += q * dz;
+  }
+}
+
+// One workgroup per conformer, positions in LDS as fp64 in two buffers (a Jacobi update: every move is computed from the old
+// positions), kCap atoms of room.  Atom i belongs to L consecutive lanes (L a power of two <= 64 with n L <= 256, so a group never
+// leaves its wave; L = 1 past 128 atoms, atoms then strided over the threads): lane `sub` of the group takes the entries
+// sub, sub + L, ... of the atom's bounded row and then the atoms j = sub, sub + L, ... -- every group of a wave reads the same L
+// LDS addresses, a broadcast -- merging the atom's ascending exclusion row as j ascends, as k_clash_scan does; the L partial sums
+// meet in the xor butterfly, offsets L / 2 ... 1.  The first pass also tests the conformer against the true bounds with the rules
+// of k_pair_bounds and k_clash_scan.  A pair with d^2 > T^2 (1 + 1e-6) has c = 0 and, as T >= clash (r_i + r_j), a ratio that is
+// not below `clash` after rounding either: it skips the square root.  Flags: 1 the stop rule is not met, 2 not valid at entry,
+// 4 a coordinate that is not finite.
+template <int kCap>
+__global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_bounds(const float* __restrict__ pos, const int32_t* __restrict__ bd_ptr,
+                                                                   const int32_t* __restrict__ bd_idx, const float* __restrict__ bd_lo,
+                                                                   const float* __restrict__ bd_hi, const float* __restrict__ radius,
+                                                                   const int32_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
+                                                                   int n, int L, float clash, float pad, float omega, int max_iter,
+                                                                   float* __restrict__ pos_out, int32_t* __restrict__ status,
+                                                                   int32_t* __restrict__ iters, float* __restrict__ resid,
+                                                                   float* __restrict__ moved) {
+  __shared__ double s_x[2][3][kCap];
+  __shared__ float s_rad[kCap];
+  __shared__ double s_wr[AG_RELAX_THREADS / 64], s_r;
+  __shared__ int s_wf[AG_RELAX_THREADS / 64], s_flags;
+  const int g = blockIdx.x, t = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  float* po = pos_out + (size_t)g * n * 3;
+  int flags = 0;
+  double rmax = 0.0;
+  for (int a = t; a < n; a += AG_RELAX_THREADS) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double v = p[3 * a + c];
+      s_x[0][c][a] = v;
+      flags |= ag_finite(v) ? 0 : 4;
+    }
+    s_rad[a] = radius[a];
+  }
+  ag_relax_reduce(flags, rmax, s_wf, s_wr, &s_flags, &s_r);
+  if (flags) {                                      // not finite: copied through, bit for bit
+    for (int e = t; e < 3 * n; e += AG_RELAX_THREADS) po[e] = p[e];
+    if (t == 0) { status[g] = 3; iters[g] = 0; resid[g] = INFINITY; moved[g] = 0.0f; }
+    return;
+  }
+  const int sub = t & (L - 1), slot = t / L, slots = AG_RELAX_THREADS / L;
+  const double cl = (double)clash, pd = (double)pad, om = (double)omega;
+  int cur = 0, it = 0, st = 0;
+  bool first = true;
+  for (;;) {
+    const double(*x)[kCap] = s_x[cur];
+    double(*y)[kCap] = s_x[cur ^ 1];
+    flags = 0;
+    rmax = 0.0;
+    for (int i = slot; i < n; i += slots) {         // (L > 1: n <= slots, one turn, whole groups in or out)
+      const double xi = x[0][i], yi = x[1][i], zi = x[2][i], ri = (double)s_rad[i];
+      double ax = 0.0, ay = 0.0, az = 0.0;
+      const int b0 = bd_ptr[i], b1 = bd_ptr[i + 1];
+      for (int k = b0 + sub; k < b1; k += L) {
+        const int j = bd_idx[k];
+        const double lo = (double)bd_lo[k], hi = (double)bd_hi[k];
+        const double dx = xi - x[0][j], dy = yi - x[1][j], dz = zi - x[2][j];
+        const double d = sqrt(dx * dx + dy * dy + dz * dz);
+        if (first) {
+          const double df = (double)(float)d;
+          if ((float)fmax(fmax(lo - df, df - hi), 0.0) > 0.0f) flags |= 2;
+        }
+        const double pk = fmin(pd, 0.5 * (hi - lo));
+        double s = 0.0;
+        if (d < lo + pk) s = lo + pk - d;
+        else if (d > hi - pk) s = hi - pk - d;
+        if (fabs(s) > 0.5 * pk) flags |= 1;
+        rmax = fmax(rmax, fabs(s));
+        if (s != 0.0) ag_relax_add(ax, ay, az, 0.5 * s, dx, dy, dz, d, i < j);
+      }
+      int c = ex_ptr[i];
+      const int e = ex_ptr[i + 1];
+      int nx = c < e ? ex_idx[c] : 0x7fffffff;
+      for (int j = sub; j < n; j += L) {
+        while (nx < j) {
+          ++c;
+          nx = c < e ? ex_idx[c] : 0x7fffffff;
+        }
+        if (j == i || j == nx) continue;
+        const double rs = ri + (double)s_rad[j], T = cl * rs + pd;
+        const double dx = xi - x[0][j], dy = yi - x[1][j], dz = zi - x[2][j];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        if (d2 > T * T * (1.0 + 1e-6)) continue;
+        const double d = sqrt(d2);
+        if (first && (float)(d / rs) < clash) flags |= 2;
+        const double cc = fmax(T - d, 0.0);
+        if (cc > 0.5 * pd) flags |= 1;
+        rmax = fmax(rmax, cc);
+        if (cc > 0.0) ag_relax_add(ax, ay, az, 0.5 * cc, dx, dy, dz, d, i < j);
+      }
+      for (int o = L >> 1; o > 0; o >>= 1) {
+        ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o);
+      }
+      if (sub == 0) {
+        const double w = om / (double)(b1 - b0 + 1);
+        y[0][i] = xi + w * ax; y[1][i] = yi + w * ay; y[2][i] = zi + w * az;
+      }
+    }
+    ag_relax_reduce(flags, rmax, s_wf, s_wr, &s_flags, &s_r);
+    if (first) {
+      first = false;
+      if (!(flags & 2)) { st = 0; break; }
+    }
+    if (!(flags & 1)) { st = 1; break; }
+    if (it == max_iter) { st = 2; break; }
+    cur ^= 1;                                       // the displacements are applied
+    ++it;
+  }
+  if (st == 0) {                                    // valid as it came: copied through, bit for bit
+    for (int e = t; e < 3 * n; e += AG_RELAX_THREADS) po[e] = p[e];
+    if (t == 0) { status[g] = 0; iters[g] = 0; resid[g] = 0.0f; moved[g] = 0.0f; }
+    return;
+  }
+  const double resid_out = rmax;
+  double m2 = 0.0;
+  for (int a = t; a < n; a += AG_RELAX_THREADS) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double v = s_x[cur][c][a], dv = v - (double)p[3 * a + c];
+      m2 += dv * dv;
+      po[3 * a + c] = (float)v;
+    }
+  }
+  ag_wave_sum(m2);
+  if ((t & 63) == 0) s_wr[t >> 6] = m2;             // (s_wr: last read before the second barrier of the last reduction)
+  __syncthreads();
+  if (t == 0) {
+    m2 = 0.0;
+#pragma unroll
+    for (int w = 0; w < AG_RELAX_THREADS / 64; ++w) m2 += s_wr[w];
+    status[g] = st;
+    iters[g] = it;
+    resid[g] = (float)resid_out;
+    moved[g] = (float)sqrt(m2 / n);
+  }
+}
+
 // ---- distance-distribution MMD (ConfGF / CGCF / GraphDG; include/agdiff_hip.h has the definition): Z = [X; Y], M = R + G rows of
 // K interatomic distances.  "all" is one problem over the rows, "single" one problem per column.  Everything is fp64 from the
 // stored fp32 values; every sum has a fixed order (thread-strided terms, the xor butterfly, then waves or tiles in index order).
@@ -1170,6 +1350,32 @@ extern "C" int agdiff_clash_scan(const float* pos, const float* radius, const in
     AG_CHECK_LAUNCH();
   }
   k_clash_finish<<<dim3((unsigned)G), dim3(64), 0, st>>>(scratch, S, min_ratio, min_pair, n_clash);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
+                                   const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, int32_t G, int32_t n, int32_t K,
+                                   float clash, float pad, float omega, int32_t max_iter, float* pos_out, int32_t* status, int32_t* iters,
+                                   float* resid, float* moved, void* stream) {
+  if (!pos || !bd_ptr || !radius || !ex_ptr || !pos_out || !status || !iters || !resid || !moved || pos_out == pos || G < 0 || n <= 0 ||
+      K < 0 || (K > 0 && (!bd_idx || !bd_lo || !bd_hi)))
+    return AGDIFF_ERR_ARG;
+  if (max_iter < 1 || max_iter > AGDIFF_RELAX_MAX_ITERS) return AGDIFF_ERR_ARG;
+  if (!(pad > 0.0f && pad <= 3.40282347e38f) || !(omega > 0.0f && omega < 2.0f) || !(clash >= 0.0f && clash <= 3.40282347e38f))
+    return AGDIFF_ERR_ARG;
+  if (n > AGDIFF_RELAX_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) return AGDIFF_OK;
+  int L = 1;                                        // lanes per atom: the largest power of two <= 64 with n L <= 256
+  while (L < 64 && 2 * L * n <= AG_RELAX_THREADS) L <<= 1;
+  const dim3 grid((unsigned)G), block(AG_RELAX_THREADS);
+  hipStream_t st = (hipStream_t)stream;
+  if (n <= 128)
+    k_relax_bounds<128><<<grid, block, 0, st>>>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash, pad, omega, max_iter,
+                                                pos_out, status, iters, resid, moved);
+  else
+    k_relax_bounds<AGDIFF_RELAX_MAX_ATOMS><<<grid, block, 0, st>>>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash,
+                                                                   pad, omega, max_iter, pos_out, status, iters, resid, moved);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

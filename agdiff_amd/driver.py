@@ -458,7 +458,8 @@ def merge_outputs(out_dir):
 
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
-            fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, check_geometry=False):
+            fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, repair_geometry=False,
+            check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -480,6 +481,13 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     a fraction of their van der Waals sum) -- agdiff_amd.validity.check_geometry with the table bounds, after the handedness fix
     and before the prune.  `pos_gen_<i>` is left as it is; with a prune switch the invalid conformers take no part in the walk
     (`cluster_<i>` is -1 for them).
+    repair_geometry=True: the conformers those two checks call invalid are not only marked: their atoms are moved by small steps
+    until every bond length and every contact is back inside the limits (agdiff_amd.validity.repair_geometry with the table bounds
+    and its defaults; a projection onto distance bounds, NOT MMFF: no energies, torsions or electrostatics) -- after the handedness
+    fix (a mirror image has the same distances) and before the check and the prune, which then describe the repaired conformers.
+    `pos_gen_<i>` holds the repaired conformers (a valid one is unchanged bit for bit), `repair_status_<i>` int8 [G] is 0 valid as
+    sampled, 1 repaired, 2 not repaired within the iteration limit, 3 not finite, and `repair_moved_<i>` float32 [G] the root mean
+    square displacement of the atoms in Angstrom.
     track_rmsd=True: every saved molecule also gets `rmsd_traj_<i>` float32 [steps, G]: each conformer's heavy-atom RMSD to the
     molecule's `pos_target` (load_testset: `pos_target_<i>`; a molecule without one is an error) after every denoising step,
     computed while the run samples (agdiff_amd.trajectory), with or without save_traj; track_rmsd_mirror=True adds
@@ -565,7 +573,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
                                 world, counter_seed, prune_rms, fix_handedness, prune_tfd,
-                                ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), check_geometry)
+                                ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -574,9 +582,10 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, check_geometry=False):
+                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, repair_geometry=False,
+                     check_geometry=False):
     import torch.distributed as dist
-    mirrored = undecided = checked = invalid = 0
+    mirrored = undecided = checked = invalid = repaired = stuck = seen = 0
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
         # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until here,
@@ -630,6 +639,17 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 out["hand_%d" % m["index"]] = hand
                 mirrored += int((hand < 0).sum())
                 undecided += int((hand == 0).sum())
+            if repair_geometry:
+                from .validity import repair_geometry as repair
+                res = repair(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
+                                  edge_type=m["edge_type"]), device=device)
+                status = res["status"].cpu().numpy()
+                out["pos_gen_%d" % m["index"]] = res["pos"].cpu().numpy()
+                out["repair_status_%d" % m["index"]] = status.astype(np.int8)
+                out["repair_moved_%d" % m["index"]] = res["moved"].cpu().numpy()
+                seen += int(status.shape[0])
+                repaired += int((status == 1).sum())
+                stuck += int((status == 2).sum())
             valid = None
             if check_geometry:
                 from .validity import check_geometry as check
@@ -656,6 +676,9 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
     if fix_handedness and (rank == 0 or mirrored or undecided):       # (the ranks that wrote files)
         log("rank %d: %d conformers were mirror images and were inverted; %d match neither hand (verdict 0) and stay as sampled"
             % (rank, mirrored, undecided))
+    if repair_geometry and (rank == 0 or seen):
+        log("rank %d: %d of %d conformers were repaired (moved into their distance bounds); %d more were not within the iteration limit "
+            "(repair_status_<i> = 2)" % (rank, repaired, seen, stuck))
     if check_geometry and (rank == 0 or checked):
         log("rank %d: %d of %d conformers are invalid (a bond length out of bounds or a steric clash) and are marked in valid_<i>"
             % (rank, invalid, checked))
@@ -708,6 +731,12 @@ def main(argv=None):
                     help="also save, per molecule, valid_<i>, bond_dev_<i> and clash_<i>: which conformers pass the bond-length bounds "
                          "and the steric clash scan of agdiff_amd.validity (pos_gen_<i> still holds them all); with --prune-rms / "
                          "--prune-tfd the invalid ones are left out of the walk (cluster_<i> = -1)")
+    ap.add_argument("--repair-geometry", action="store_true",
+                    help="move the atoms of the conformers that fail those two checks into their bounds before anything is saved "
+                         "(agdiff_amd.validity.repair_geometry: a projection onto distance bounds from the topology alone, NOT MMFF): "
+                         "pos_gen_<i> then holds the repaired conformers, repair_status_<i> (0 valid as sampled, 1 repaired, 2 not "
+                         "repaired, 3 not finite) and repair_moved_<i> say what was done; --check-geometry and the prunes see the "
+                         "repaired conformers")
     ap.add_argument("--track-rmsd", action="store_true",
                     help="also save, per molecule, rmsd_traj_<i> [steps, num_samples]: every conformer's heavy-atom RMSD to the "
                          "molecule's pos_target_<i> of the test set after every denoising step, computed while the run samples "
@@ -758,7 +787,7 @@ def main(argv=None):
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
             seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
-            check_geometry=args.check_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror)
+            check_geometry=args.check_geometry, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror)
     if own_pg:
         dist.destroy_process_group()
 

@@ -23,7 +23,13 @@ Bondi's van der Waals radii for the clash scan at clash = 0.60 of their sum (O..
 intramolecular hydrogen bond, so hydrogen bonds are not flagged).  Nobody has run them over GEOM's reference conformers: no
 false-positive rate is claimed.
 
+A conformer that fails can also be repaired instead of dropped: agdiff_relax_bounds (relax_bounds, repair_geometry, --repair) moves
+its atoms by small steps until every bounded distance and every contact is back inside the limits the two checks test, and leaves a
+valid conformer untouched bit for bit.  That is a projection onto distance bounds from the topology alone, NOT MMFF: no energies, no
+torsion terms, no electrostatics; agdiff_amd.evaluation's use_force_field=True still raises.
+
     python -m agdiff_amd.validity --samples out/samples_all.npz --testset test.npz [--refs refs.npz] [--clash 0.6] --out validity.npz
+                                  [--repair repaired.npz [--pad 0.02] [--omega 1.0] [--max-iter 200]]
 """
 import numpy as np
 
@@ -191,6 +197,77 @@ def clash_scan(pos, radius, ex_ptr, ex_idx, thresh, want_scratch=False):
     return (min_ratio, min_pair, n_clash, scratch) if want_scratch else (min_ratio, min_pair, n_clash)
 
 
+def bounds_csr(n, pairs, lo, hi):
+    """(bd_ptr int32 [n + 1], bd_idx int32 [2K], bd_lo float32 [2K], bd_hi float32 [2K]): the tables of agdiff_relax_bounds -- every
+    bounded pair once in the row of each of its two atoms (partner, lo, hi), within a row in the order of the pair list (a pair listed
+    twice appears twice).  ValueError: a pair that names an atom outside [0, n) or one atom twice (there is nothing to move), lo > hi
+    or a NaN bound."""
+    n = int(n)
+    pr = as_host(pairs, np.int32).reshape(-1, 2)
+    K = pr.shape[0]
+    lo_, hi_ = (as_host(x, np.float32).reshape(-1) for x in (lo, hi))
+    if lo_.shape[0] != K or hi_.shape[0] != K:
+        raise ValueError("%d pairs but %d lower and %d upper bounds" % (K, lo_.shape[0], hi_.shape[0]))
+    if K and not (lo_ <= hi_).all():
+        raise ValueError("every pair needs lo <= hi (and neither may be NaN)")
+    if K and (pr.min() < 0 or pr.max() >= n):
+        raise ValueError("a bounded pair names an atom outside the molecule's %d atoms" % n)
+    if K and (pr[:, 0] == pr[:, 1]).any():
+        raise ValueError("a bounded pair names one atom twice")
+    rows = pr.reshape(-1).astype(np.int64)                              # a_0 b_0 a_1 b_1 ...: a stable sort keeps the list's order
+    order = np.argsort(rows, kind="stable")
+    bd_ptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(bd_ptr, rows + 1, 1)
+    return (np.cumsum(bd_ptr).astype(np.int32), pr[:, ::-1].reshape(-1)[order].astype(np.int32), np.repeat(lo_, 2)[order],
+            np.repeat(hi_, 2)[order])
+
+
+def relax_tables(n, pairs, lo, hi, radius, ex_ptr, ex_idx, clash=0.60, pad=0.02, omega=1.0):
+    """Everything relax_bounds checks and builds on the host, before any launch: (bd_ptr, bd_idx, bd_lo, bd_hi, radius float32 [n],
+    ex_ptr, ex_idx, K).  ValueError for what bounds_csr, clash_scan's radius and exclusion checks refuse, and for a clash that is not
+    finite and >= 0, a pad that is not finite and > 0 or an omega outside (0, 2)."""
+    n = int(n)
+    if n <= 0:
+        raise ValueError("conformers without atoms")
+    if not (float(clash) >= 0.0 and np.isfinite(float(clash))):
+        raise ValueError("the clash threshold must be finite and >= 0 (got %r)" % (clash,))
+    if not (np.float32(pad) > 0.0 and np.isfinite(np.float32(pad))):
+        raise ValueError("pad must be finite and > 0 (got %r)" % (pad,))
+    if not 0.0 < np.float32(omega) < 2.0:
+        raise ValueError("omega must lie in (0, 2) (got %r)" % (omega,))
+    bd = bounds_csr(n, pairs, lo, hi)
+    rad = as_host(radius, np.float32).reshape(-1)
+    if rad.shape[0] != n or not (np.isfinite(rad).all() and (rad > 0).all()):
+        raise ValueError("radius must hold %d finite numbers > 0" % n)
+    ptr, idx = as_host(ex_ptr), as_host(ex_idx)
+    _check_exclusions(n, ptr, idx)
+    return bd + (rad, np.array(ptr), np.array(idx), bd[1].shape[0] // 2)
+
+
+def relax_bounds(pos, pairs, lo, hi, radius, ex_ptr, ex_idx, clash=0.60, pad=0.02, omega=1.0, max_iter=200):
+    """agdiff_relax_bounds on pos [G, n, 3] (float32, contiguous, on the GPU): every conformer that fails pair_bounds(pairs, lo, hi)
+    or clash_scan(radius, exclusions, clash) has its atoms moved by small steps until every bounded distance is inside
+    [lo + p, hi - p], p = min(pad, (hi - lo) / 2), and every pair not excluded at least clash x (r_i + r_j) + pad apart (to within
+    half a pad), or max_iter updates are spent; omega in (0, 2) scales the step.  Not MMFF: no energies, no torsions, no
+    electrostatics (include/agdiff_hip.h has the rule).  Returns (pos_out float32 [G, n, 3], status int32 [G]:
+    0 valid as it came and unchanged bit for bit, 1 repaired, 2 not within max_iter updates, 3 not finite and unchanged;
+    iters int32 [G]; resid float32 [G], what the stop rule last saw in Angstrom; moved float32 [G], the RMS displacement of the
+    atoms).  The tables are checked here, on the host (relax_tables); more than AGDIFF_RELAX_MAX_ATOMS atoms: AgdiffLimitError."""
+    import torch
+    _lib.require_device_conformers(pos)
+    G, n = int(pos.shape[0]), int(pos.shape[1])
+    bd_ptr, bd_idx, bd_lo, bd_hi, rad, ptr, idx, K = relax_tables(n, pairs, lo, hi, radius, ex_ptr, ex_idx, clash, pad, omega)
+    dev = pos.device
+    pos_out = torch.empty_like(pos)
+    status, iters = (torch.empty(G, dtype=torch.int32, device=dev) for _ in range(2))
+    resid, moved = (torch.empty(G, dtype=torch.float32, device=dev) for _ in range(2))
+    if G:
+        up = lambda x: torch.from_numpy(x).to(dev) if x.size else None
+        _lib.call("agdiff_relax_bounds", pos, torch.from_numpy(bd_ptr).to(dev), up(bd_idx), up(bd_lo), up(bd_hi), up(rad), up(ptr), up(idx),
+                  G, n, K, float(clash), float(pad), float(omega), int(max_iter), pos_out, status, iters, resid, moved)
+    return pos_out, status, iters, resid, moved
+
+
 def _tables(item, bounds, table_kw):
     """(pairs, lo, hi, radius, ex_ptr, ex_idx) of an item: host work, and every ValueError an item can cause, before any launch"""
     n = num_atoms(item)
@@ -232,12 +309,31 @@ def check_geometry(item, bounds="table", clash=0.60, device="cuda", **table_kw):
             "clash": min_ratio, "clash_pair": min_pair, "n_clash": n_clash}
 
 
+def repair_geometry(item, bounds="table", clash=0.60, pad=0.02, omega=1.0, max_iter=200, device="cuda", **table_kw):
+    """relax_bounds over the item's generated conformers with the tables check_geometry builds from the item (the same `bounds`,
+    `clash` and keywords): the conformers check_geometry calls invalid are moved into their bounds, the valid ones come back bit for
+    bit.  Not MMFF (no energies, torsions or electrostatics; evaluation.py's use_force_field=True still raises).  The defaults come
+    from a CPU prototype of the rule on hand-built molecules; none was tuned on a GPU.  Returns a dict of tensors on `device`:
+        pos     float32 [G, n, 3]   the repaired conformers
+        status  int32 [G]           0 valid as sampled, 1 repaired, 2 not repaired within max_iter updates, 3 not finite
+        iters   int32 [G]           updates applied
+        resid   float32 [G]         the largest distance still wanted by the stop rule, in Angstrom
+        moved   float32 [G]         the root mean square displacement of the atoms"""
+    pairs, lo, hi, radius, ex_ptr, ex_idx = _tables(item, bounds, table_kw)
+    pos = _lib.conformers(item["pos_gen"], num_atoms(item), device)
+    out = relax_bounds(pos, pairs, lo, hi, radius, ex_ptr, ex_idx, clash=clash, pad=pad, omega=omega, max_iter=max_iter)
+    return dict(zip(("pos", "status", "iters", "resid", "moved"), out))
+
+
 def main(argv=None):
     """python -m agdiff_amd.validity --samples samples_all.npz --testset test.npz [--refs refs.npz] [--clash 0.6] --out validity.npz
     Checks every molecule of a finished job (agdiff_amd.driver: `pos_gen_<i>`; the bonds come from the test set, extended to order 3).
     Writes per molecule `valid_<i>` int8 [G], `bond_dev_<i>` float32 [G], `bond_pair_<i>` int32 [G, 2], `n_bad_<i>` int32 [G],
     `clash_<i>` float32 [G], `clash_pair_<i>` int32 [G, 2], `n_clash_<i>` int32 [G] (+ `name_<i>`).  --refs (`pos_ref_<i>` [R, n, 3]):
-    the bounds come from the molecule's reference conformers (bounds_from_references) instead of the covalent-radius table."""
+    the bounds come from the molecule's reference conformers (bounds_from_references) instead of the covalent-radius table.
+    --repair REPAIRED.npz: every molecule's conformers first go through repair_geometry (the same bounds and --clash; --pad, --omega,
+    --max-iter); REPAIRED.npz is a copy of the samples file with every `pos_gen_<i>` repaired plus `repair_status_<i>` int8 [G] and
+    `repair_moved_<i>` float32 [G], and --out holds the verdicts on the repaired conformers.  Not MMFF: a projection onto the bounds."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", required=True)
@@ -245,19 +341,42 @@ def main(argv=None):
     ap.add_argument("--refs", default=None, help="bounds from these reference conformers instead of the covalent-radius table")
     ap.add_argument("--clash", type=float, default=0.60, help="fraction of the van der Waals sum below which a pair clashes")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--repair", default=None, metavar="REPAIRED.npz",
+                    help="move the invalid conformers into their bounds first (repair_geometry; not MMFF) and write the samples file "
+                         "with the repaired pos_gen_<i>, repair_status_<i> and repair_moved_<i> here; --out then judges the repaired ones")
+    ap.add_argument("--pad", type=float, default=0.02, help="--repair: how far inside its limits a repaired distance is aimed (Angstrom)")
+    ap.add_argument("--omega", type=float, default=1.0, help="--repair: the step's relaxation factor, in (0, 2)")
+    ap.add_argument("--max-iter", type=int, default=200, help="--repair: most updates per conformer")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
     if not (args.clash >= 0.0 and np.isfinite(args.clash)):
         ap.error("--clash must be finite and >= 0")
+    if not (args.pad > 0.0 and np.isfinite(args.pad)) or not 0.0 < args.omega < 2.0 or args.max_iter < 1:
+        ap.error("--pad must be finite and > 0, --omega in (0, 2) and --max-iter >= 1")
     zr = np.load(args.refs, allow_pickle=False) if args.refs else None
     out, mols, confs, invalid, by_bond, by_clash = {}, 0, 0, 0, 0, 0
+    repaired, fixed, stuck = None, 0, 0
+    if args.repair:
+        with np.load(args.samples, allow_pickle=False) as zs:
+            repaired = {k: zs[k] for k in zs.files}
     for mol, item in sampled_items(args.testset, args.samples):
         i = mol["index"]
         if zr is not None:
             if "pos_ref_%d" % i not in zr.files:
                 raise ValueError("--refs: %s has no pos_ref_%d" % (args.refs, i))
             item["pos_ref"] = zr["pos_ref_%d" % i]
-        res = check_geometry(item, bounds="references" if zr is not None else "table", clash=args.clash, device=args.device)
+        how = "references" if zr is not None else "table"
+        if repaired is not None:
+            rep = repair_geometry(item, bounds=how, clash=args.clash, pad=args.pad, omega=args.omega, max_iter=args.max_iter,
+                                  device=args.device)
+            status = rep["status"].cpu().numpy()
+            item["pos_gen"] = rep["pos"].cpu().numpy().reshape(np.shape(repaired["pos_gen_%d" % i]))
+            repaired["pos_gen_%d" % i] = item["pos_gen"]
+            repaired["repair_status_%d" % i] = status.astype(np.int8)
+            repaired["repair_moved_%d" % i] = rep["moved"].cpu().numpy()
+            fixed += int((status == 1).sum())
+            stuck += int((status == 2).sum())
+        res = check_geometry(item, bounds=how, clash=args.clash, device=args.device)
         for k, v in res.items():
             out["%s_%d" % (k, i)] = v.cpu().numpy().astype(np.int8) if k == "valid" else v.cpu().numpy()
         out["name_%d" % i] = np.str_(mol["name"])
@@ -268,6 +387,10 @@ def main(argv=None):
         by_bond += int(bad.sum())
         by_clash += int(hit.sum())
     np.savez_compressed(args.out, **out)
+    if repaired is not None:
+        np.savez_compressed(args.repair, **repaired)
+        print("%d conformers were repaired, %d were not within %d updates; the verdicts are on the repaired conformers"
+              % (fixed, stuck, args.max_iter))
     print("%d molecules, %d conformers, %d invalid (%d with a distance out of bounds, %d with a clash)"
           % (mols, confs, invalid, by_bond, by_clash))
     return out

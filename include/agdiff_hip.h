@@ -43,6 +43,9 @@ extern "C" {
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
 #define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
+#define AGDIFF_RELAX_MAX_ATOMS 1024 /* most atoms per conformer of agdiff_relax_bounds: two fp64 position buffers (48 KB) and the radii
+                                       (4 KB) fit the 64 KB of static LDS */
+#define AGDIFF_RELAX_MAX_ITERS 10000 /* most updates agdiff_relax_bounds may be asked for */
 #define AGDIFF_MMD_MAX_CONFS 8192 /* most reference + generated conformers of agdiff_mmd_single: one column of them is 32 KB of LDS */
 #define AGDIFF_POLY_MAX_KT 4      /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
@@ -889,6 +892,48 @@ int agdiff_pair_bounds(const float* pos, const int32_t* pairs, const float* lo, 
 int agdiff_clash_scan(const float* pos, const float* radius /* [n], > 0 */, const int32_t* ex_ptr, const int32_t* ex_idx,
                       int32_t G, int32_t n, float thresh, int32_t* scratch, float* min_ratio /* [G] */,
                       int32_t* min_pair /* [G][2] */, int32_t* n_clash /* [G] */, void* stream);
+
+/* agdiff_relax_bounds: repair.  The atoms of a conformer that fails the two checks above are moved by small amounts until every
+ * bounded distance and every contact of a pair not excluded is back inside the limits those checks test; a conformer that passes
+ * them comes back bit for bit.  This is NOT MMFF and no force field: no energies, no torsion terms, no electrostatics -- a
+ * projection onto distance bounds from the topology alone (evaluation.py's use_force_field=True still raises).
+ *   pos [G][n][3], n <= AGDIFF_RELAX_MAX_ATOMS (else AGDIFF_ERR_LIMIT)
+ *   bd_ptr [n + 1], bd_idx / bd_lo / bd_hi [2 K]   every bounded pair once in the row of each of its two atoms (partner, lo, hi),
+ *                          within a row in the order of the pair list; b_i = bd_ptr[i + 1] - bd_ptr[i].  The three arrays may be
+ *                          null when K = 0.  NOT checked here: the caller does (partners in [0, n), lo <= hi).
+ *   radius, ex_ptr, ex_idx exactly what agdiff_clash_scan takes (NOT checked here)
+ *   clash                  finite and >= 0;  pad finite and > 0;  omega in (0, 2);  max_iter in [1, AGDIFF_RELAX_MAX_ITERS]:
+ *                          else AGDIFF_ERR_ARG, as for a null pointer or pos_out == pos
+ * Targets, a little inside the true limits so that the fp32 result passes the checks with room to spare:
+ *   bounded entry k:       p_k = min(pad, (hi_k - lo_k) / 2), the interval [lo_k + p_k, hi_k - p_k]
+ *   pair (i, j) not excluded: T_ij = clash (r_i + r_j) + pad
+ * One iteration from the positions x, all in fp64 (the fp32 coordinates converted first), d = |x_i - x_j|:
+ *   u_ij = (x_i - x_j) / d; when d < 1e-9, (1, 0, 0) seen from the lower-indexed atom and (-1, 0, 0) from the other
+ *   s_k  = lo_k + p_k - d below the lower target, hi_k - p_k - d above the upper one, else 0  (the signed change of d wanted)
+ *   c_ij = max(T_ij - d, 0)
+ *   x_i <- x_i + omega / (b_i + 1) [ sum_{k in row i} s_k u_k / 2  +  sum_{j != i not excluded} c_ij u_ij / 2 ]
+ * for every atom from the OLD positions (a Jacobi update).  The weight depends on the topology only -- it is not divided by the
+ * number of constraints violated at the moment, which jumps when a distance sits exactly on its target, where a projection puts
+ * it: with the static weight the map is continuous and a rounding-level difference stays one.
+ * Stop rule, evaluated in the same pass as the displacements and before they are applied: done when every |s_k| <= p_k / 2 and
+ * every c_ij <= pad / 2.  Otherwise, after max_iter updates the evaluation of the positions they gave is the last one.
+ * Before the first iteration the conformer is tested against the true bounds with the exact rules of agdiff_pair_bounds (d as
+ * fp32 against lo, hi) and agdiff_clash_scan ((float)(d / (r_i + r_j)) < clash).
+ *   pos_out [G][n][3]      must not alias pos
+ *   status [G] int32       0 valid as it came, copied through unchanged; 1 repaired: the stop rule was met; 2 max_iter updates
+ *                          applied and the stop rule still not met; 3 a coordinate that is not finite, copied through unchanged
+ *   iters [G] int32        updates applied (status 2: max_iter)
+ *   resid [G]              the largest |s_k| or c_ij the stop rule saw in its last evaluation, in Angstrom; 0 for status 0, +inf for 3
+ *   moved [G]              the root mean square over the atoms of |x_final - x_input|, from the fp64 state before the final store
+ * One workgroup of 256 threads per conformer, the positions in LDS as fp64 in two buffers; an atom belongs to L lanes (a power of
+ * two chosen from n, 1 past 128 atoms where atoms are strided over the threads) whose partial sums meet in a fixed order; each
+ * lane merges the atom's ascending exclusion row as j ascends (no n x n mask).  No atomics, deterministic bit for bit; the loop's
+ * exit is decided from one LDS value the whole workgroup reads after a barrier. */
+int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
+                        const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, int32_t G, int32_t n, int32_t K,
+                        float clash, float pad, float omega, int32_t max_iter, float* pos_out /* [G][n][3] */,
+                        int32_t* status /* [G] */, int32_t* iters /* [G] */, float* resid /* [G] */, float* moved /* [G] */,
+                        void* stream);
 
 /* ---- trajectory tracking ---------------------------------------------------------------------------------------------
  * The convergence curve of examples/test_alanine_dipeptide.py:106-164 (every frame of the denoising run superposed on a target
