@@ -649,6 +649,18 @@ __device__ __forceinline__ double ag_pair_dist(const float* __restrict__ p, int 
   return sqrt(dx * dx + dy * dy + dz * dz);
 }
 
+// (best, best_k) of a lane = its largest value and the lowest index attaining it, best_k < 0 when it has none: afterwards every
+// lane holds the wave's largest value with the lowest index attaining it, and the sum of `count` over the lanes
+__device__ __forceinline__ void ag_wave_worst(float& best, int& best_k, int& count) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o);
+    const int ok = __shfl_xor(best_k, o);
+    count += __shfl_xor(count, o);
+    if (ok >= 0 && (ov > best || (ov == best && ok < best_k))) { best = ov; best_k = ok; }
+  }
+}
+
 // one wave per conformer, lanes over the pairs (strided past 64), shaped like k_torsion_angles: d as fp32, the violation
 // v = max(lo - d, d - hi, 0) on that fp32 d (+inf when d is not finite), then max / lowest index / count across the lanes by
 // shuffles.  A pair that names an atom outside [0, n) has d = NaN, v = +inf and reads nothing.
@@ -670,17 +682,101 @@ __global__ void __launch_bounds__(64) k_pair_bounds(const float* __restrict__ po
     bad += v > 0.0f ? 1 : 0;
     if (v > best) { best = v; best_k = k; }         // (k ascends: the lane keeps its lowest k)
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int ok = __shfl_xor(best_k, o);
-    bad += __shfl_xor(bad, o);
-    if (ok >= 0 && (ov > best || (ov == best && ok < best_k))) { best = ov; best_k = ok; }
-  }
+  ag_wave_worst(best, best_k, bad);
   if (lane == 0) {
     worst[g] = best_k < 0 ? 0.0f : best;
     worst_pair[g] = best_k;
     n_bad[g] = bad;
+  }
+}
+
+// ---- planarity: a conformer can keep every bond length and every contact legal and still fold an aromatic ring into a boat or
+// twist the two ends of a double bond against each other.  The host names the groups of atoms that must lie in one plane
+// (agdiff_amd/planarity.py); the check is each member's distance from the group's best plane --
+
+// unit normal of the best plane through centred points with the covariance A = (xx xy xz yy yz zz): the eigenvector of A's smallest
+// eigenvalue.  The 3x3 problem sits in the 4x4 key of ag_jacobi4 with a fourth diagonal entry no rotation touches (its row and
+// column are exactly zero, ag_jacobi4 skips a zero pivot and a rotation of two other columns leaves them zero), so d[3], column 3
+// and the fourth component of the other columns stay (0, e_4, 0) and are not read.
+__device__ void ag_plane_normal(const double (&A)[6], double (&nrm)[3]) {
+  const double k[10] = {A[0], A[1], A[2], 0.0, A[3], A[4], 0.0, A[5], 0.0, 0.0};
+  double d[4], V[4][4];
+  ag_jacobi4<true>(k, d, V);
+  double lam = d[0];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) nrm[r] = V[r][0];
+#pragma unroll
+  for (int j = 1; j < 3; ++j) {
+    const bool down = d[j] < lam;
+    lam = down ? d[j] : lam;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) nrm[r] = down ? V[r][j] : nrm[r];
+  }
+  const double s = 1.0 / sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) nrm[r] *= s;
+}
+
+// one wave per conformer, lanes over the groups (strided past 64), shaped like k_pair_bounds.  A lane walks its group's m <= 8
+// members twice, so that no 24-double array lives in registers: once for the sums of u_k = x_k - x_0 and of u_k u_k^T (relative to
+// the first member, so that the covariance A = sum u u^T / m - ubar ubar^T cancels over the group's extent and not over its
+// distance from the origin), once for the projections normal . (u_k - ubar) = normal . (x_k - centroid).  All in fp64 from the fp32
+// coordinates; dev = the largest |projection| as fp32, +inf when a member coordinate is not finite.  A group of fewer than 3 or more
+// than AGDIFF_PLANAR_MAX_ATOMS members, or one that names an atom outside [0, n), has dev = NaN, reads no coordinate and enters
+// neither the maximum nor the count.
+__global__ void __launch_bounds__(64) k_planar_groups(const float* __restrict__ pos, const int32_t* __restrict__ grp_ptr,
+                                                      const int32_t* __restrict__ grp_idx, int n, int P, float thresh,
+                                                      float* __restrict__ dev, float* __restrict__ worst,
+                                                      int32_t* __restrict__ worst_group, int32_t* __restrict__ n_bent) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  float best = -1.0f;                               // (below every deviation: the lane's first group is taken)
+  int best_k = -1, bent = 0;
+  for (int k = lane; k < P; k += 64) {
+    const int b = grp_ptr[k], m = grp_ptr[k + 1] - b;
+    bool ok = m >= 3 && m <= AGDIFF_PLANAR_MAX_ATOMS;
+    for (int j = 0; ok && j < m; ++j) ok = ag_atoms_in_range(n, grp_idx[b + j]);
+    float d = NAN;
+    if (ok) {
+      const int a0 = grp_idx[b];
+      const double ox = p[3 * a0], oy = p[3 * a0 + 1], oz = p[3 * a0 + 2];
+      double s[3] = {0, 0, 0}, S[6] = {0, 0, 0, 0, 0, 0};
+      bool fin = ag_finite(ox) && ag_finite(oy) && ag_finite(oz);
+      for (int j = 1; j < m; ++j) {
+        const int a = grp_idx[b + j];
+        const double x = p[3 * a], y = p[3 * a + 1], z = p[3 * a + 2];
+        fin = fin && ag_finite(x) && ag_finite(y) && ag_finite(z);
+        const double ux = x - ox, uy = y - oy, uz = z - oz;
+        s[0] += ux; s[1] += uy; s[2] += uz;
+        S[0] += ux * ux; S[1] += ux * uy; S[2] += ux * uz; S[3] += uy * uy; S[4] += uy * uz; S[5] += uz * uz;
+      }
+      d = INFINITY;
+      if (fin) {
+        const double inv = 1.0 / m, cx = s[0] * inv, cy = s[1] * inv, cz = s[2] * inv;
+        const double A[6] = {S[0] * inv - cx * cx, S[1] * inv - cx * cy, S[2] * inv - cx * cz,
+                             S[3] * inv - cy * cy, S[4] * inv - cy * cz, S[5] * inv - cz * cz};
+        double nrm[3];
+        ag_plane_normal(A, nrm);
+        double far = 0.0;
+        for (int j = 0; j < m; ++j) {
+          const int a = grp_idx[b + j];
+          const double ux = (double)p[3 * a] - ox - cx, uy = (double)p[3 * a + 1] - oy - cy, uz = (double)p[3 * a + 2] - oz - cz;
+          far = fmax(far, fabs(nrm[0] * ux + nrm[1] * uy + nrm[2] * uz));
+        }
+        d = (float)far;
+      }
+    }
+    if (dev) dev[(size_t)g * P + k] = d;
+    if (d == d) {                                   // (a NaN group takes no part)
+      bent += d > thresh ? 1 : 0;
+      if (d > best) { best = d; best_k = k; }       // (k ascends: the lane keeps its lowest k)
+    }
+  }
+  ag_wave_worst(best, best_k, bent);
+  if (lane == 0) {
+    worst[g] = best_k < 0 ? 0.0f : best;
+    worst_group[g] = best_k;
+    n_bent[g] = bent;
   }
 }
 
@@ -1331,6 +1427,17 @@ extern "C" int agdiff_pair_bounds(const float* pos, const int32_t* pairs, const 
   if (!pos || !worst || !worst_pair || !n_bad || G < 0 || n <= 0 || K < 0 || (K > 0 && (!pairs || !lo || !hi))) return AGDIFF_ERR_ARG;
   if (G == 0) return AGDIFF_OK;
   k_pair_bounds<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, pairs, lo, hi, n, K, dist, worst, worst_pair, n_bad);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_planar_groups(const float* pos, const int32_t* grp_ptr, const int32_t* grp_idx, int32_t G, int32_t n, int32_t P,
+                                    float thresh, float* dev, float* worst, int32_t* worst_group, int32_t* n_bent, void* stream) {
+  if (!pos || !worst || !worst_group || !n_bent || G < 0 || n <= 0 || P < 0 || (P > 0 && (!grp_ptr || !grp_idx))) return AGDIFF_ERR_ARG;
+  if (!(thresh >= 0.0f && thresh <= 3.40282347e38f)) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_planar_groups<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, grp_ptr, grp_idx, n, P, thresh, dev, worst, worst_group,
+                                                                           n_bent);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -459,7 +459,7 @@ def merge_outputs(out_dir):
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
             fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, repair_geometry=False,
-            check_geometry=False):
+            check_planarity=False, check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -481,6 +481,11 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     a fraction of their van der Waals sum) -- agdiff_amd.validity.check_geometry with the table bounds, after the handedness fix
     and before the prune.  `pos_gen_<i>` is left as it is; with a prune switch the invalid conformers take no part in the walk
     (`cluster_<i>` is -1 for them).
+    check_planarity=True: every saved molecule also gets `flat_<i>` int8 [G] and `flat_dev_<i>` float32 [G] (the largest distance of
+    an atom from the best plane of its aromatic ring or of its double bond and that bond's neighbours, in Angstrom) --
+    agdiff_amd.planarity.check_planarity with its defaults, after the handedness fix and the repair, next to check_geometry, whose
+    `valid_<i>` does not change.  With a prune switch the bent conformers take no part in the walk either (`cluster_<i>` is -1 for
+    them): the mask handed to the prune is `flat`, and `flat & valid` with check_geometry.
     repair_geometry=True: the conformers those two checks call invalid are not only marked: their atoms are moved by small steps
     until every bond length and every contact is back inside the limits (agdiff_amd.validity.repair_geometry with the table bounds
     and its defaults; a projection onto distance bounds, NOT MMFF: no energies, torsions or electrostatics) -- after the handedness
@@ -573,7 +578,8 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     try:
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
                                 world, counter_seed, prune_rms, fix_handedness, prune_tfd,
-                                ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_geometry)
+                                ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_planarity,
+                                check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -583,9 +589,9 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
                      counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, repair_geometry=False,
-                     check_geometry=False):
+                     check_planarity=False, check_geometry=False):
     import torch.distributed as dist
-    mirrored = undecided = checked = invalid = repaired = stuck = seen = 0
+    mirrored = undecided = checked = invalid = repaired = stuck = seen = judged = bent = 0
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
         # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until here,
@@ -661,6 +667,15 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 out["clash_%d" % m["index"]] = res["clash"].cpu().numpy()
                 checked += int(valid.shape[0])
                 invalid += int((~valid).sum())
+            if check_planarity:
+                from .planarity import check_planarity as planar
+                res = planar(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
+                                  edge_type=m["edge_type"]), device=device)
+                out["flat_%d" % m["index"]] = res["flat"].cpu().numpy().astype(np.int8)
+                out["flat_dev_%d" % m["index"]] = res["flat_dev"].cpu().numpy()
+                judged += int(res["flat"].shape[0])
+                bent += int((~res["flat"]).sum())
+                valid = res["flat"] if valid is None else valid & res["flat"]      # (the prune's mask; valid_<i> is already saved)
             if prune_rms is not None or prune_tfd is not None:
                 from .ensemble import prune_conformers
                 res = prune_conformers(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
@@ -682,6 +697,9 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
     if check_geometry and (rank == 0 or checked):
         log("rank %d: %d of %d conformers are invalid (a bond length out of bounds or a steric clash) and are marked in valid_<i>"
             % (rank, invalid, checked))
+    if check_planarity and (rank == 0 or judged):
+        log("rank %d: %d of %d conformers are bent (an aromatic ring or a double bond out of plane) and are marked in flat_<i>"
+            % (rank, bent, judged))
     if world > 1:
         dist.barrier()                       # every rank's batch files are on disk
     if SAMPLE_STATS["range_trips"]:
@@ -731,6 +749,10 @@ def main(argv=None):
                     help="also save, per molecule, valid_<i>, bond_dev_<i> and clash_<i>: which conformers pass the bond-length bounds "
                          "and the steric clash scan of agdiff_amd.validity (pos_gen_<i> still holds them all); with --prune-rms / "
                          "--prune-tfd the invalid ones are left out of the walk (cluster_<i> = -1)")
+    ap.add_argument("--check-planarity", action="store_true",
+                    help="also save, per molecule, flat_<i> and flat_dev_<i>: which conformers keep their aromatic rings and double "
+                         "bonds planar (agdiff_amd.planarity; distances cannot see a folded ring or a twisted C=C, so valid_<i> says "
+                         "nothing about them); with --prune-rms / --prune-tfd the bent ones are left out of the walk (cluster_<i> = -1)")
     ap.add_argument("--repair-geometry", action="store_true",
                     help="move the atoms of the conformers that fail those two checks into their bounds before anything is saved "
                          "(agdiff_amd.validity.repair_geometry: a projection onto distance bounds from the topology alone, NOT MMFF): "
@@ -787,7 +809,7 @@ def main(argv=None):
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
             seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
-            check_geometry=args.check_geometry, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror)
+            check_geometry=args.check_geometry, check_planarity=args.check_planarity, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror)
     if own_pg:
         dist.destroy_process_group()
 

@@ -13,7 +13,7 @@ heavy-atom self-matches (GetBestRMS), without them the identity mapping only.  H
 along in the alignment.
 
     python -m agdiff_amd.ensemble --samples out/samples_all.npz --testset test.npz --prune-rms 0.5 [--align] [--fix-handedness]
-                                  [--drop-invalid] --out pruned.npz
+                                  [--drop-invalid] [--drop-bent] --out pruned.npz
     (--prune-tfd 0.2 in --prune-rms's place: the same walk over the torsion fingerprint deviation, agdiff_amd.torsions)
 """
 import numpy as np
@@ -21,6 +21,7 @@ import numpy as np
 from . import _lib
 from .evaluation import selection_of, selection_on_device
 from .molecule import as_host, check_threshold, heavy_atoms, num_atoms, sampled_items
+from .planarity import check_planarity
 from .stereo import fix_handedness as _fix_handedness
 from .validity import check_geometry
 
@@ -191,7 +192,8 @@ def main(argv=None):
     (+ `name_<i>`).  Exactly one of --prune-rms / --prune-tfd T (the torsion fingerprint deviation, in [0, 1]).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
     python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix.  --drop-invalid: the conformers that fail
     agdiff_amd.validity.check_geometry (table bounds, default clash ratio) take no part in the walk: `cluster_<i>` is -1 for them;
-    also writes `valid_<i>` int8 [G]."""
+    also writes `valid_<i>` int8 [G].  --drop-bent: the same for the conformers that fail agdiff_amd.planarity.check_planarity (an
+    aromatic ring or a double bond out of plane, default threshold); also writes `flat_<i>` int8 [G]."""
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--samples", required=True)
@@ -204,6 +206,8 @@ def main(argv=None):
     ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
     ap.add_argument("--drop-invalid", action="store_true",
                     help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the walk")
+    ap.add_argument("--drop-bent", action="store_true",
+                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out of the walk")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -220,6 +224,10 @@ def main(argv=None):
         if args.drop_invalid:
             valid = check_geometry(item, device=args.device)["valid"]       # (mirroring keeps every distance: before or after the fix)
             out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
+        if args.drop_bent:
+            flat = check_planarity(item, device=args.device)["flat"]       # (mirroring keeps every plane too)
+            out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
+            valid = flat if valid is None else valid & flat
         res = prune_conformers(item, threshold, align=args.align, device=args.device, fix_handedness=args.fix_handedness,
                                metric=metric, valid=valid)
         out["pos_%d" % i] = res["pos"].cpu().numpy()

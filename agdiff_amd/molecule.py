@@ -1,4 +1,4 @@
-"""What the modules that run after the sampler (evaluation, ensemble, stereo, torsions, validity, trajectory, distances) share on
+"""What the modules that run after the sampler (evaluation, ensemble, stereo, torsions, validity, planarity, trajectory, distances) share on
 the host: how an item's fields, atoms and bonds are read, the bonded-neighbour graph, colour refinement, and the item loops of
 their command lines.  numpy only; the device-side counterparts (`call`, `conformers`, ...) are in _lib.py.
 

@@ -43,6 +43,8 @@ extern "C" {
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
 #define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
+#define AGDIFF_PLANAR_MAX_ATOMS 8 /* most atoms of one planar group of agdiff_planar_groups: a double bond with three neighbours at
+                                     each end (planarity.py's rules give no more; an aromatic ring has 5 or 6) */
 #define AGDIFF_RELAX_MAX_ATOMS 1024 /* most atoms per conformer of agdiff_relax_bounds: two fp64 position buffers (48 KB) and the radii
                                        (4 KB) fit the 64 KB of static LDS */
 #define AGDIFF_RELAX_MAX_ITERS 10000 /* most updates agdiff_relax_bounds may be asked for */
@@ -934,6 +936,29 @@ int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* 
                         float clash, float pad, float omega, int32_t max_iter, float* pos_out /* [G][n][3] */,
                         int32_t* status /* [G] */, int32_t* iters /* [G] */, float* resid /* [G] */, float* moved /* [G] */,
                         void* stream);
+
+/* agdiff_planar_groups: planarity.  Bent aromatic rings, pyramidal sp2 centres and twisted double bonds keep every distance the
+ * checks above test legal; this one measures, for P named groups of atoms that should lie in one plane (the host names them from
+ * the bond types: agdiff_amd/planarity.py), how far the members are from the group's best plane.
+ *   pos [G][n][3]
+ *   grp_ptr [P + 1], grp_idx [grp_ptr[P]] int32   the members of every group as a CSR (both may be null when P = 0).  grp_ptr is
+ *                          NOT checked here: the caller does (starts at 0, does not decrease, ends at the length of grp_idx)
+ *   thresh                 finite and >= 0, else AGDIFF_ERR_ARG
+ * Per (conformer, group) of m members, in fp64 from the fp32 coordinates: centroid c, y_k = x_k - c, A = (1 / m) sum_k y_k y_k^T,
+ * unit normal = the eigenvector of A's smallest eigenvalue (cyclic Jacobi sweeps, the solver of the RMSD kernels),
+ *   dev [G][P] or null     (float)max_k |normal . y_k|: the largest distance of a member from the best plane, in Angstrom; +inf when a
+ *                          member coordinate is not finite; NaN for a group of fewer than 3 or more than AGDIFF_PLANAR_MAX_ATOMS
+ *                          members or one that names an atom outside [0, n): such a group reads no coordinate and enters neither
+ *                          worst nor n_bent
+ *   worst [G]              the maximum of the fp32 dev values as stored; 0 when P = 0 or every group is NaN
+ *   worst_group [G] int32  the lowest group index attaining worst; -1 when P = 0 or every group is NaN
+ *   n_bent [G] int32       the number of groups with dev > thresh (+inf counts)
+ * dev is defined through the projections and not as sqrt(lambda_min): on an exactly planar group the eigenvalue is rounding noise
+ * of A (sqrt of 1e-15 is 3e-8 A) while the projections on the computed normal are not.
+ * One wave per conformer, lanes over the groups.  No atomics, deterministic bit for bit. */
+int agdiff_planar_groups(const float* pos, const int32_t* grp_ptr /* [P + 1] */, const int32_t* grp_idx, int32_t G, int32_t n, int32_t P,
+                         float thresh, float* dev /* [G][P] or null */, float* worst /* [G] */, int32_t* worst_group /* [G] */,
+                         int32_t* n_bent /* [G] */, void* stream);
 
 /* ---- trajectory tracking ---------------------------------------------------------------------------------------------
  * The convergence curve of examples/test_alanine_dipeptide.py:106-164 (every frame of the denoising run superposed on a target
