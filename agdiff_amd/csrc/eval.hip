@@ -717,13 +717,48 @@ __device__ void ag_plane_normal(const double (&A)[6], double (&nrm)[3]) {
   for (int r = 0; r < 3; ++r) nrm[r] *= s;
 }
 
-// one wave per conformer, lanes over the groups (strided past 64), shaped like k_pair_bounds.  A lane walks its group's m <= 8
-// members twice, so that no 24-double array lives in registers: once for the sums of u_k = x_k - x_0 and of u_k u_k^T (relative to
+// The best plane of one group, members mem[0 .. m), coordinate c of atom a = at(a, c) as fp64: the ONE copy of the per-group
+// computation, called by k_planar_groups (coordinates from global memory) and by the repair's phase A (from LDS).  The members are
+// walked twice, so that no 24-double array lives in registers: once for the sums of u_k = x_k - x_0 and of u_k u_k^T (relative to
 // the first member, so that the covariance A = sum u u^T / m - ubar ubar^T cancels over the group's extent and not over its
-// distance from the origin), once for the projections normal . (u_k - ubar) = normal . (x_k - centroid).  All in fp64 from the fp32
-// coordinates; dev = the largest |projection| as fp32, +inf when a member coordinate is not finite.  A group of fewer than 3 or more
-// than AGDIFF_PLANAR_MAX_ATOMS members, or one that names an atom outside [0, n), has dev = NaN, reads no coordinate and enters
-// neither the maximum nor the count.
+// distance from the origin), once for the projections normal . (u_k - ubar) = normal . (x_k - centroid).  org = x_0, ubar = the
+// centroid relative to it, nrm = the unit normal, far = the largest |projection|.  false, and only org written, when a member
+// coordinate is not finite.
+template <typename F>
+__device__ __forceinline__ bool ag_group_plane(F at, const int32_t* __restrict__ mem, int m, double (&org)[3], double (&ubar)[3],
+                                               double (&nrm)[3], double& far) {
+  const int a0 = mem[0];
+  const double ox = at(a0, 0), oy = at(a0, 1), oz = at(a0, 2);
+  org[0] = ox; org[1] = oy; org[2] = oz;
+  double s[3] = {0, 0, 0}, S[6] = {0, 0, 0, 0, 0, 0};
+  bool fin = ag_finite(ox) && ag_finite(oy) && ag_finite(oz);
+  for (int j = 1; j < m; ++j) {
+    const int a = mem[j];
+    const double x = at(a, 0), y = at(a, 1), z = at(a, 2);
+    fin = fin && ag_finite(x) && ag_finite(y) && ag_finite(z);
+    const double ux = x - ox, uy = y - oy, uz = z - oz;
+    s[0] += ux; s[1] += uy; s[2] += uz;
+    S[0] += ux * ux; S[1] += ux * uy; S[2] += ux * uz; S[3] += uy * uy; S[4] += uy * uz; S[5] += uz * uz;
+  }
+  if (!fin) return false;
+  const double inv = 1.0 / m, cx = s[0] * inv, cy = s[1] * inv, cz = s[2] * inv;
+  const double A[6] = {S[0] * inv - cx * cx, S[1] * inv - cx * cy, S[2] * inv - cx * cz,
+                       S[3] * inv - cy * cy, S[4] * inv - cy * cz, S[5] * inv - cz * cz};
+  ag_plane_normal(A, nrm);
+  ubar[0] = cx; ubar[1] = cy; ubar[2] = cz;
+  far = 0.0;
+  for (int j = 0; j < m; ++j) {
+    const int a = mem[j];
+    const double ux = at(a, 0) - ox - cx, uy = at(a, 1) - oy - cy, uz = at(a, 2) - oz - cz;
+    far = fmax(far, fabs(nrm[0] * ux + nrm[1] * uy + nrm[2] * uz));
+  }
+  return true;
+}
+
+// one wave per conformer, lanes over the groups (strided past 64), shaped like k_pair_bounds; the plane of a lane's group comes
+// from ag_group_plane.  All in fp64 from the fp32 coordinates; dev = the largest |projection| as fp32, +inf when a member
+// coordinate is not finite.  A group of fewer than 3 or more than AGDIFF_PLANAR_MAX_ATOMS members, or one that names an atom
+// outside [0, n), has dev = NaN, reads no coordinate and enters neither the maximum nor the count.
 __global__ void __launch_bounds__(64) k_planar_groups(const float* __restrict__ pos, const int32_t* __restrict__ grp_ptr,
                                                       const int32_t* __restrict__ grp_idx, int n, int P, float thresh,
                                                       float* __restrict__ dev, float* __restrict__ worst,
@@ -738,33 +773,9 @@ __global__ void __launch_bounds__(64) k_planar_groups(const float* __restrict__ 
     for (int j = 0; ok && j < m; ++j) ok = ag_atoms_in_range(n, grp_idx[b + j]);
     float d = NAN;
     if (ok) {
-      const int a0 = grp_idx[b];
-      const double ox = p[3 * a0], oy = p[3 * a0 + 1], oz = p[3 * a0 + 2];
-      double s[3] = {0, 0, 0}, S[6] = {0, 0, 0, 0, 0, 0};
-      bool fin = ag_finite(ox) && ag_finite(oy) && ag_finite(oz);
-      for (int j = 1; j < m; ++j) {
-        const int a = grp_idx[b + j];
-        const double x = p[3 * a], y = p[3 * a + 1], z = p[3 * a + 2];
-        fin = fin && ag_finite(x) && ag_finite(y) && ag_finite(z);
-        const double ux = x - ox, uy = y - oy, uz = z - oz;
-        s[0] += ux; s[1] += uy; s[2] += uz;
-        S[0] += ux * ux; S[1] += ux * uy; S[2] += ux * uz; S[3] += uy * uy; S[4] += uy * uz; S[5] += uz * uz;
-      }
-      d = INFINITY;
-      if (fin) {
-        const double inv = 1.0 / m, cx = s[0] * inv, cy = s[1] * inv, cz = s[2] * inv;
-        const double A[6] = {S[0] * inv - cx * cx, S[1] * inv - cx * cy, S[2] * inv - cx * cz,
-                             S[3] * inv - cy * cy, S[4] * inv - cy * cz, S[5] * inv - cz * cz};
-        double nrm[3];
-        ag_plane_normal(A, nrm);
-        double far = 0.0;
-        for (int j = 0; j < m; ++j) {
-          const int a = grp_idx[b + j];
-          const double ux = (double)p[3 * a] - ox - cx, uy = (double)p[3 * a + 1] - oy - cy, uz = (double)p[3 * a + 2] - oz - cz;
-          far = fmax(far, fabs(nrm[0] * ux + nrm[1] * uy + nrm[2] * uz));
-        }
-        d = (float)far;
-      }
+      double org[3], ubar[3], nrm[3], far;
+      const bool fin = ag_group_plane([p](int a, int c) { return (double)p[3 * a + c]; }, grp_idx + b, m, org, ubar, nrm, far);
+      d = fin ? (float)far : INFINITY;
     }
     if (dev) dev[(size_t)g * P + k] = d;
     if (d == d) {                                   // (a NaN group takes no part)
@@ -955,17 +966,31 @@ __device__ __forceinline__ void ag_relax_add(double& ax, double& ay, double& az,
 // of k_pair_bounds and k_clash_scan.  A pair with d^2 > T^2 (1 + 1e-6) has c = 0 and, as T >= clash (r_i + r_j), a ratio that is
 // not below `clash` after rounding either: it skips the square root.  Flags: 1 the stop rule is not met, 2 not valid at entry,
 // 4 a coordinate that is not finite.
-template <int kCap>
-__global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_bounds(const float* __restrict__ pos, const int32_t* __restrict__ bd_ptr,
-                                                                   const int32_t* __restrict__ bd_idx, const float* __restrict__ bd_lo,
-                                                                   const float* __restrict__ bd_hi, const float* __restrict__ radius,
-                                                                   const int32_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
-                                                                   int n, int L, float clash, float pad, float omega, int max_iter,
-                                                                   float* __restrict__ pos_out, int32_t* __restrict__ status,
-                                                                   int32_t* __restrict__ iters, float* __restrict__ resid,
-                                                                   float* __restrict__ moved) {
+//
+// kPlanes (k_relax_planar; without it every plane line below is compiled out and this is k_relax_bounds as it was): each iteration
+// gets a phase A before the atom loop, thread k < P over group k: ag_group_plane on the current positions, the unit normal and
+// the centroid to LDS as six doubles, structure of arrays (consecutive threads write consecutive doubles: no bank conflict), and on
+// the first pass k_planar_groups' own verdict (float)dev > thresh into flag 2.  After a barrier the atom loop adds, for the groups
+// of the atom's membership row mb_grp[mb_ptr[i] .. mb_ptr[i + 1]) (lane `sub` takes sub, sub + L, ...: a fixed order), the whole
+// step -sign(h) e n onto the plane's target slab, h = n . (x_i - c), e = max(|h| - flat_to, 0), and the weight's denominator grows
+// by the row's length q_i.  The next phase A overwrites the planes only after the two barriers of the reduction.
+struct ag_planes_t {
+  const int32_t *grp_ptr, *grp_idx, *mb_ptr, *mb_grp;
+  int P;
+  float thresh, flat_to;
+};
+
+template <int kCap, bool kPlanes>
+__device__ __forceinline__ void ag_relax(const float* __restrict__ pos, const int32_t* __restrict__ bd_ptr,
+                                         const int32_t* __restrict__ bd_idx, const float* __restrict__ bd_lo,
+                                         const float* __restrict__ bd_hi, const float* __restrict__ radius,
+                                         const int32_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx, int n, int L, float clash,
+                                         float pad, float omega, int max_iter, const ag_planes_t& pl, float* __restrict__ pos_out,
+                                         int32_t* __restrict__ status, int32_t* __restrict__ iters, float* __restrict__ resid,
+                                         float* __restrict__ moved) {
   __shared__ double s_x[2][3][kCap];
   __shared__ float s_rad[kCap];
+  __shared__ double s_pl[kPlanes ? 6 : 1][kPlanes ? AGDIFF_FLATTEN_MAX_GROUPS : 1];   // (not referenced without kPlanes: no LDS)
   __shared__ double s_wr[AG_RELAX_THREADS / 64], s_r;
   __shared__ int s_wf[AG_RELAX_THREADS / 64], s_flags;
   const int g = blockIdx.x, t = threadIdx.x;
@@ -997,6 +1022,20 @@ __global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_bounds(const float* 
     double(*y)[kCap] = s_x[cur ^ 1];
     flags = 0;
     rmax = 0.0;
+    if constexpr (kPlanes) {                        // phase A: the plane of group t from the current positions
+      if (t < pl.P) {
+        const int b = pl.grp_ptr[t];
+        double org[3], ubar[3], nrm[3] = {0.0, 0.0, 0.0}, far = 0.0;
+        const bool fin = ag_group_plane([x](int a, int c) { return x[c][a]; }, pl.grp_idx + b, pl.grp_ptr[t + 1] - b, org, ubar, nrm, far);
+        if (first && (float)far > pl.thresh) flags |= 2;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {               // (positions that left the finite range: a zero normal, the group moves nothing)
+          s_pl[c][t] = fin ? nrm[c] : 0.0;
+          s_pl[3 + c][t] = fin ? org[c] + ubar[c] : 0.0;
+        }
+      }
+      __syncthreads();
+    }
     for (int i = slot; i < n; i += slots) {         // (L > 1: n <= slots, one turn, whole groups in or out)
       const double xi = x[0][i], yi = x[1][i], zi = x[2][i], ri = (double)s_rad[i];
       double ax = 0.0, ay = 0.0, az = 0.0;
@@ -1038,11 +1077,29 @@ __global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_bounds(const float* 
         rmax = fmax(rmax, cc);
         if (cc > 0.0) ag_relax_add(ax, ay, az, 0.5 * cc, dx, dy, dz, d, i < j);
       }
+      int q = 0;
+      if constexpr (kPlanes) {
+        const int m0 = pl.mb_ptr[i], m1 = pl.mb_ptr[i + 1];
+        q = m1 - m0;
+        const double ft = (double)pl.flat_to;
+        for (int k = m0 + sub; k < m1; k += L) {
+          const int gk = pl.mb_grp[k];
+          const double nx_ = s_pl[0][gk], ny_ = s_pl[1][gk], nz_ = s_pl[2][gk];
+          const double h = nx_ * (xi - s_pl[3][gk]) + ny_ * (yi - s_pl[4][gk]) + nz_ * (zi - s_pl[5][gk]);
+          const double ee = fmax(fabs(h) - ft, 0.0);
+          if (ee > 0.5 * pd) flags |= 1;
+          rmax = fmax(rmax, ee);
+          if (ee > 0.0) {
+            const double mv = h > 0.0 ? -ee : ee;
+            ax += mv * nx_; ay += mv * ny_; az += mv * nz_;
+          }
+        }
+      }
       for (int o = L >> 1; o > 0; o >>= 1) {
         ax += __shfl_xor(ax, o); ay += __shfl_xor(ay, o); az += __shfl_xor(az, o);
       }
       if (sub == 0) {
-        const double w = om / (double)(b1 - b0 + 1);
+        const double w = om / (double)(b1 - b0 + q + 1);
         y[0][i] = xi + w * ax; y[1][i] = yi + w * ay; y[2][i] = zi + w * az;
       }
     }
@@ -1083,6 +1140,34 @@ __global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_bounds(const float* 
     resid[g] = (float)resid_out;
     moved[g] = (float)sqrt(m2 / n);
   }
+}
+
+template <int kCap>
+__global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_bounds(const float* __restrict__ pos, const int32_t* __restrict__ bd_ptr,
+                                                                   const int32_t* __restrict__ bd_idx, const float* __restrict__ bd_lo,
+                                                                   const float* __restrict__ bd_hi, const float* __restrict__ radius,
+                                                                   const int32_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
+                                                                   int n, int L, float clash, float pad, float omega, int max_iter,
+                                                                   float* __restrict__ pos_out, int32_t* __restrict__ status,
+                                                                   int32_t* __restrict__ iters, float* __restrict__ resid,
+                                                                   float* __restrict__ moved) {
+  ag_relax<kCap, false>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash, pad, omega, max_iter, ag_planes_t{},
+                        pos_out, status, iters, resid, moved);
+}
+
+// k_relax_bounds plus the planes of P <= AGDIFF_FLATTEN_MAX_GROUPS groups (one group per thread in phase A); P = 0 gives
+// k_relax_bounds' results
+template <int kCap>
+__global__ void __launch_bounds__(AG_RELAX_THREADS) k_relax_planar(const float* __restrict__ pos, const int32_t* __restrict__ bd_ptr,
+                                                                   const int32_t* __restrict__ bd_idx, const float* __restrict__ bd_lo,
+                                                                   const float* __restrict__ bd_hi, const float* __restrict__ radius,
+                                                                   const int32_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_idx,
+                                                                   int n, int L, float clash, float pad, float omega, int max_iter,
+                                                                   ag_planes_t pl, float* __restrict__ pos_out,
+                                                                   int32_t* __restrict__ status, int32_t* __restrict__ iters,
+                                                                   float* __restrict__ resid, float* __restrict__ moved) {
+  ag_relax<kCap, true>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash, pad, omega, max_iter, pl, pos_out, status,
+                       iters, resid, moved);
 }
 
 // ---- distance-distribution MMD (ConfGF / CGCF / GraphDG; include/agdiff_hip.h has the definition): Z = [X; Y], M = R + G rows of
@@ -1461,30 +1546,64 @@ extern "C" int agdiff_clash_scan(const float* pos, const float* radius, const in
   return AGDIFF_OK;
 }
 
-extern "C" int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
-                                   const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, int32_t G, int32_t n, int32_t K,
-                                   float clash, float pad, float omega, int32_t max_iter, float* pos_out, int32_t* status, int32_t* iters,
-                                   float* resid, float* moved, void* stream) {
+// the argument checks and the launch of both repairs; groups == nullptr or P = 0: k_relax_bounds
+static int ag_relax_launch(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
+                           const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, int32_t G, int32_t n, int32_t K, float clash,
+                           float pad, float omega, int32_t max_iter, const ag_planes_t* groups, float* pos_out, int32_t* status,
+                           int32_t* iters, float* resid, float* moved, void* stream) {
   if (!pos || !bd_ptr || !radius || !ex_ptr || !pos_out || !status || !iters || !resid || !moved || pos_out == pos || G < 0 || n <= 0 ||
       K < 0 || (K > 0 && (!bd_idx || !bd_lo || !bd_hi)))
     return AGDIFF_ERR_ARG;
   if (max_iter < 1 || max_iter > AGDIFF_RELAX_MAX_ITERS) return AGDIFF_ERR_ARG;
   if (!(pad > 0.0f && pad <= 3.40282347e38f) || !(omega > 0.0f && omega < 2.0f) || !(clash >= 0.0f && clash <= 3.40282347e38f))
     return AGDIFF_ERR_ARG;
-  if (n > AGDIFF_RELAX_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
+  if (groups) {
+    const ag_planes_t& pl = *groups;
+    if (pl.P < 0 || (pl.P > 0 && (!pl.grp_ptr || !pl.grp_idx || !pl.mb_ptr || !pl.mb_grp))) return AGDIFF_ERR_ARG;
+    if (!(pl.thresh >= 0.0f && pl.thresh <= 3.40282347e38f) || !(pl.flat_to >= 0.0f && pl.flat_to <= 3.40282347e38f))
+      return AGDIFF_ERR_ARG;
+    if ((double)pl.flat_to + (double)pad > (double)pl.thresh) return AGDIFF_ERR_ARG;
+  }
+  if (n > AGDIFF_RELAX_MAX_ATOMS || (groups && groups->P > AGDIFF_FLATTEN_MAX_GROUPS)) return AGDIFF_ERR_LIMIT;
   if (G == 0) return AGDIFF_OK;
   int L = 1;                                        // lanes per atom: the largest power of two <= 64 with n L <= 256
   while (L < 64 && 2 * L * n <= AG_RELAX_THREADS) L <<= 1;
   const dim3 grid((unsigned)G), block(AG_RELAX_THREADS);
   hipStream_t st = (hipStream_t)stream;
-  if (n <= 128)
+  if (groups && groups->P > 0) {
+    if (n <= 128)
+      k_relax_planar<128><<<grid, block, 0, st>>>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash, pad, omega,
+                                                  max_iter, *groups, pos_out, status, iters, resid, moved);
+    else
+      k_relax_planar<AGDIFF_RELAX_MAX_ATOMS><<<grid, block, 0, st>>>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash,
+                                                                     pad, omega, max_iter, *groups, pos_out, status, iters, resid, moved);
+  } else if (n <= 128) {
     k_relax_bounds<128><<<grid, block, 0, st>>>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash, pad, omega, max_iter,
                                                 pos_out, status, iters, resid, moved);
-  else
+  } else {
     k_relax_bounds<AGDIFF_RELAX_MAX_ATOMS><<<grid, block, 0, st>>>(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, n, L, clash,
                                                                    pad, omega, max_iter, pos_out, status, iters, resid, moved);
+  }
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
+}
+
+extern "C" int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
+                                   const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, int32_t G, int32_t n, int32_t K,
+                                   float clash, float pad, float omega, int32_t max_iter, float* pos_out, int32_t* status, int32_t* iters,
+                                   float* resid, float* moved, void* stream) {
+  return ag_relax_launch(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, G, n, K, clash, pad, omega, max_iter, nullptr, pos_out,
+                         status, iters, resid, moved, stream);
+}
+
+extern "C" int agdiff_relax_planar(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
+                                   const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, const int32_t* grp_ptr,
+                                   const int32_t* grp_idx, const int32_t* mb_ptr, const int32_t* mb_grp, int32_t G, int32_t n, int32_t K,
+                                   int32_t P, float clash, float pad, float omega, int32_t max_iter, float thresh, float flat_to,
+                                   float* pos_out, int32_t* status, int32_t* iters, float* resid, float* moved, void* stream) {
+  const ag_planes_t groups = {grp_ptr, grp_idx, mb_ptr, mb_grp, P, thresh, flat_to};
+  return ag_relax_launch(pos, bd_ptr, bd_idx, bd_lo, bd_hi, radius, ex_ptr, ex_idx, G, n, K, clash, pad, omega, max_iter, &groups, pos_out,
+                         status, iters, resid, moved, stream);
 }
 
 extern "C" int agdiff_traj_rmsd(const float* frames, int64_t frame_stride, const float* target, const uint8_t* select,

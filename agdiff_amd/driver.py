@@ -459,7 +459,7 @@ def merge_outputs(out_dir):
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
             fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, repair_geometry=False,
-            check_planarity=False, check_geometry=False):
+            check_planarity=False, repair_planarity=False, check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -493,6 +493,12 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     `pos_gen_<i>` holds the repaired conformers (a valid one is unchanged bit for bit), `repair_status_<i>` int8 [G] is 0 valid as
     sampled, 1 repaired, 2 not repaired within the iteration limit, 3 not finite, and `repair_moved_<i>` float32 [G] the root mean
     square displacement of the atoms in Angstrom.
+    repair_planarity=True: repair_geometry's step with planes -- one launch of agdiff_amd.planarity.repair_planarity with the table
+    bounds and its defaults at the same place: the conformers check_planarity calls bent are flattened (every atom of an aromatic
+    ring or of a double bond and its neighbours to within 0.10 Angstrom of the group's best plane) while the bond lengths and
+    contacts are held or repaired as repair_geometry does; still NOT MMFF, and E or Z is not chosen.  A superset of repair_geometry:
+    giving both switches equals giving this one.  The same keys, `repair_status_<i>` (0: valid AND flat as sampled) and
+    `repair_moved_<i>`; both checks and the prune then describe the repaired conformers.
     track_rmsd=True: every saved molecule also gets `rmsd_traj_<i>` float32 [steps, G]: each conformer's heavy-atom RMSD to the
     molecule's `pos_target` (load_testset: `pos_target_<i>`; a molecule without one is an error) after every denoising step,
     computed while the run samples (agdiff_amd.trajectory), with or without save_traj; track_rmsd_mirror=True adds
@@ -579,7 +585,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
                                 world, counter_seed, prune_rms, fix_handedness, prune_tfd,
                                 ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_planarity,
-                                check_geometry)
+                                repair_planarity, check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -589,7 +595,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
                      counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, repair_geometry=False,
-                     check_planarity=False, check_geometry=False):
+                     check_planarity=False, repair_planarity=False, check_geometry=False):
     import torch.distributed as dist
     mirrored = undecided = checked = invalid = repaired = stuck = seen = judged = bent = 0
     for pos_in_mine, bidx in enumerate(mine):
@@ -645,8 +651,11 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 out["hand_%d" % m["index"]] = hand
                 mirrored += int((hand < 0).sum())
                 undecided += int((hand == 0).sum())
-            if repair_geometry:
-                from .validity import repair_geometry as repair
+            if repair_geometry or repair_planarity:
+                if repair_planarity:                   # (holds the bonds too: the distance repair is part of it)
+                    from .planarity import repair_planarity as repair
+                else:
+                    from .validity import repair_geometry as repair
                 res = repair(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
                                   edge_type=m["edge_type"]), device=device)
                 status = res["status"].cpu().numpy()
@@ -691,9 +700,10 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
     if fix_handedness and (rank == 0 or mirrored or undecided):       # (the ranks that wrote files)
         log("rank %d: %d conformers were mirror images and were inverted; %d match neither hand (verdict 0) and stay as sampled"
             % (rank, mirrored, undecided))
-    if repair_geometry and (rank == 0 or seen):
-        log("rank %d: %d of %d conformers were repaired (moved into their distance bounds); %d more were not within the iteration limit "
-            "(repair_status_<i> = 2)" % (rank, repaired, seen, stuck))
+    if (repair_geometry or repair_planarity) and (rank == 0 or seen):
+        log("rank %d: %d of %d conformers were repaired (%s); %d more were not within the iteration limit (repair_status_<i> = 2)"
+            % (rank, repaired, seen, "flattened and moved into their distance bounds" if repair_planarity else
+               "moved into their distance bounds", stuck))
     if check_geometry and (rank == 0 or checked):
         log("rank %d: %d of %d conformers are invalid (a bond length out of bounds or a steric clash) and are marked in valid_<i>"
             % (rank, invalid, checked))
@@ -759,6 +769,13 @@ def main(argv=None):
                          "pos_gen_<i> then holds the repaired conformers, repair_status_<i> (0 valid as sampled, 1 repaired, 2 not "
                          "repaired, 3 not finite) and repair_moved_<i> say what was done; --check-geometry and the prunes see the "
                          "repaired conformers")
+    ap.add_argument("--repair-planarity", action="store_true",
+                    help="--repair-geometry plus planes, in the same launch (agdiff_amd.planarity.repair_planarity; NOT MMFF): a folded "
+                         "aromatic ring, a pyramidal sp2 centre and a twisted double bond are flattened while the bond lengths and "
+                         "contacts are held, so a conformer that is bent but otherwise fine comes back usable instead of being dropped "
+                         "by --check-planarity; includes --repair-geometry (giving both equals giving this one); the same keys "
+                         "repair_status_<i> and repair_moved_<i>; E or Z is not chosen: a double bond twisted past 90 degrees flattens "
+                         "into the other isomer")
     ap.add_argument("--track-rmsd", action="store_true",
                     help="also save, per molecule, rmsd_traj_<i> [steps, num_samples]: every conformer's heavy-atom RMSD to the "
                          "molecule's pos_target_<i> of the test set after every denoising step, computed while the run samples "
@@ -809,7 +826,8 @@ def main(argv=None):
     run_job(model, mols, args.out, num_confs(args.num_confs), args.max_atoms, kw, device, save_traj=args.save_traj,
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
             seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
-            check_geometry=args.check_geometry, check_planarity=args.check_planarity, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror)
+            check_geometry=args.check_geometry, check_planarity=args.check_planarity, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror,
+            repair_planarity=args.repair_planarity)
     if own_pg:
         dist.destroy_process_group()
 

@@ -48,6 +48,9 @@ extern "C" {
 #define AGDIFF_RELAX_MAX_ATOMS 1024 /* most atoms per conformer of agdiff_relax_bounds: two fp64 position buffers (48 KB) and the radii
                                        (4 KB) fit the 64 KB of static LDS */
 #define AGDIFF_RELAX_MAX_ITERS 10000 /* most updates agdiff_relax_bounds may be asked for */
+#define AGDIFF_FLATTEN_MAX_GROUPS 192 /* most planar groups of agdiff_relax_planar: one group per thread of the 256, and six fp64 per
+                                         group in LDS (9 KB) next to agdiff_relax_bounds' 52 KB -- 61 KB of the 64 KB of static LDS;
+                                         256 groups would not fit */
 #define AGDIFF_MMD_MAX_CONFS 8192 /* most reference + generated conformers of agdiff_mmd_single: one column of them is 32 KB of LDS */
 #define AGDIFF_POLY_MAX_KT 4      /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
@@ -936,6 +939,39 @@ int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* 
                         float clash, float pad, float omega, int32_t max_iter, float* pos_out /* [G][n][3] */,
                         int32_t* status /* [G] */, int32_t* iters /* [G] */, float* resid /* [G] */, float* moved /* [G] */,
                         void* stream);
+
+/* agdiff_relax_planar: agdiff_relax_bounds with one more constraint type, the planes of agdiff_planar_groups' groups (below), in
+ * the same launch: a folded aromatic ring, a pyramidal sp2 centre and a twisted double bond are flattened while the bonds are
+ * held -- a projection onto a plane shortens them, so this is a superset of agdiff_relax_bounds.  Still NOT MMFF: no energies, no
+ * torsion terms, no electrostatics.  It does not choose E or Z either: a double bond twisted past 90 degrees flattens into the
+ * other isomer, because nothing here knows which one the molecule is.
+ *   pos ... ex_idx, G, n, K, clash, pad, omega, max_iter, pos_out ... moved   as agdiff_relax_bounds, the same checks
+ *   grp_ptr [P + 1], grp_idx   the planar groups as agdiff_planar_groups takes them, 3 .. AGDIFF_PLANAR_MAX_ATOMS members each, P <=
+ *                          AGDIFF_FLATTEN_MAX_GROUPS (else AGDIFF_ERR_LIMIT).  NOT checked here: the caller does (members in [0, n))
+ *   mb_ptr [n + 1], mb_grp [grp_ptr[P]]   the same memberships by atom: the groups that contain atom i, ascending;
+ *                          q_i = mb_ptr[i + 1] - mb_ptr[i].  NOT checked here either
+ *                          P = 0: the four tables may be null, and the results are agdiff_relax_bounds'
+ *   thresh, flat_to        finite and >= 0, and flat_to + pad <= thresh: else AGDIFF_ERR_ARG, as for P < 0
+ * Per group k and iteration, from the positions x in fp64: centroid c_k and unit normal n_k of the best plane exactly as
+ * agdiff_planar_groups computes them (one device routine serves both); for a member i the signed distance h = n_k . (x_i - c_k) and
+ * the excess e = max(|h| - flat_to, 0): a member already within flat_to of the plane is not moved by that group, so the term is
+ * continuous in x like s_k and c_ij.  The update is
+ *   x_i <- x_i + omega / (b_i + q_i + 1) [ sum s_k u_k / 2  +  sum c_ij u_ij / 2  -  sum_{groups k with i} sign(h) e n_k ]
+ * (the plane term whole: an atom moves alone towards its plane, no partner takes the other half; the sign of n_k cancels).
+ * Stop rule: agdiff_relax_bounds' and every e <= pad / 2, so a repaired group has dev <= flat_to + pad / 2 and passes
+ * agdiff_planar_groups at thresh with pad / 2 to spare.  Entry test: agdiff_relax_bounds' or (float)dev > thresh for any group,
+ * agdiff_planar_groups' own comparison.
+ *   status [G] int32       0 valid and flat as it came, copied through unchanged; 1 repaired; 2 max_iter updates applied and the stop
+ *                          rule still not met; 3 a coordinate that is not finite, copied through unchanged
+ *   resid [G]              the largest |s_k|, c_ij or e of the last evaluation; iters and moved as agdiff_relax_bounds
+ * agdiff_relax_bounds' kernel with two phases per iteration: thread k computes the plane of group k into LDS (six fp64), a barrier,
+ * then the atom loop with the plane terms of the atom's membership row.  No atomics, deterministic bit for bit. */
+int agdiff_relax_planar(const float* pos, const int32_t* bd_ptr, const int32_t* bd_idx, const float* bd_lo, const float* bd_hi,
+                        const float* radius, const int32_t* ex_ptr, const int32_t* ex_idx, const int32_t* grp_ptr /* [P + 1] */,
+                        const int32_t* grp_idx, const int32_t* mb_ptr /* [n + 1] */, const int32_t* mb_grp, int32_t G, int32_t n,
+                        int32_t K, int32_t P, float clash, float pad, float omega, int32_t max_iter, float thresh, float flat_to,
+                        float* pos_out /* [G][n][3] */, int32_t* status /* [G] */, int32_t* iters /* [G] */, float* resid /* [G] */,
+                        float* moved /* [G] */, void* stream);
 
 /* agdiff_planar_groups: planarity.  Bent aromatic rings, pyramidal sp2 centres and twisted double bonds keep every distance the
  * checks above test legal; this one measures, for P named groups of atoms that should lie in one plane (the host names them from
