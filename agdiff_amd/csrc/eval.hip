@@ -478,6 +478,84 @@ __global__ void __launch_bounds__(64) k_align_conformers(const float* __restrict
   if (lane == 0) rmsd[g] = (float)sqrt(d2 / m);
 }
 
+// Rigid core hold of the sampler: the selected atoms of graph g are replaced by the template's selected atoms,
+// superposed on where they are now -- k_traj_rmsd's walk over a packed batch (one wave per graph, lanes striding over the graph's
+// atoms whatever their number) with k_align_conformers' rotation and write-back.  Centroids, cross-covariance and norms in fp64
+// from the stored fp32 coordinates; S = sum t x^T, so that Horn's quaternion of lambda_max is the proper rotation R that takes the
+// centred template onto the centred core: fit = R (t - c_t) + c_x, and pos <- pos + weight (fit - pos) for the selected atoms
+// only, rounded to fp32 once (weight == 1: fit itself).  pos is read AND written, through one pointer: every load that feeds the
+// sums is consumed by ag_wave_sum before R exists, and the stores need R; the blend reads an atom in the lane that writes it.
+// A graph with skip[g] != 0, without a selected atom or with a selected coordinate of either side that is not finite is not
+// written at all and gets dev = NaN.
+__global__ void __launch_bounds__(64) k_hold_core(float* pos, const float* __restrict__ core, const uint8_t* __restrict__ select,
+                                                  const int32_t* __restrict__ graph_ptr, const int32_t* __restrict__ skip, int N,
+                                                  float weight, float* copy_out, float* __restrict__ dev) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float nan = __int_as_float(0x7fc00000);
+  if (skip && skip[g] != 0) {                     // (wave-uniform)
+    if (dev && lane == 0) dev[g] = nan;
+    return;
+  }
+  const int a0 = max(graph_ptr[g], 0), a1 = min(graph_ptr[g + 1], N);       // (a graph_ptr that is not one touches nothing outside)
+  double c[7] = {0, 0, 0, 0, 0, 0, 0};            // sums of the core's and the template's selected atoms, and their number
+  for (int a = a0 + lane; a < a1; a += 64) {
+    if (!select[a]) continue;
+    const size_t o = (size_t)3 * a;
+    c[0] += pos[o]; c[1] += pos[o + 1]; c[2] += pos[o + 2];
+    c[3] += core[o]; c[4] += core[o + 1]; c[5] += core[o + 2];
+    c[6] += 1.0;
+  }
+  ag_wave_sum(c);
+  const double m = c[6];
+  bool ok = m > 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) ok = ok && ag_finite(c[e]);
+  double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, gsum = 0.0;
+  const double cx = c[0] / m, cy = c[1] / m, cz = c[2] / m, tx = c[3] / m, ty = c[4] / m, tz = c[5] / m;
+  if (ok) {                                       // (wave-uniform: every lane holds the same sums)
+    for (int a = a0 + lane; a < a1; a += 64) {
+      if (!select[a]) continue;
+      const size_t o = (size_t)3 * a;
+      const double x0 = pos[o] - cx, x1 = pos[o + 1] - cy, x2 = pos[o + 2] - cz;
+      const double t0 = core[o] - tx, t1 = core[o + 1] - ty, t2 = core[o + 2] - tz;
+      ag_cov_add(S, t0, t1, t2, x0, x1, x2);
+      gsum += (x0 * x0 + x1 * x1 + x2 * x2) + (t0 * t0 + t1 * t1 + t2 * t2);
+    }
+    ag_wave_sum(S);
+    ag_wave_sum(gsum);
+    ok = ag_finite(gsum);
+  }
+  if (!ok) {
+    if (dev && lane == 0) dev[g] = nan;
+    return;
+  }
+  double K[10], q[4];
+  ag_horn_key(S, K);
+  const double lam = ag_eigvec_max4(K, q);
+  const double q0 = q[0], qx = q[1], qy = q[2], qz = q[3];
+  const double R[9] = {q0 * q0 + qx * qx - qy * qy - qz * qz, 2.0 * (qx * qy - q0 * qz), 2.0 * (qx * qz + q0 * qy),
+                       2.0 * (qy * qx + q0 * qz), q0 * q0 - qx * qx + qy * qy - qz * qz, 2.0 * (qy * qz - q0 * qx),
+                       2.0 * (qz * qx - q0 * qy), 2.0 * (qz * qy + q0 * qx), q0 * q0 - qx * qx - qy * qy + qz * qz};
+  const bool hard = weight == 1.0f;
+  const double w = weight;
+  for (int a = a0 + lane; a < a1; a += 64) {
+    if (!select[a]) continue;
+    const size_t o = (size_t)3 * a;
+    const double t0 = core[o] - tx, t1 = core[o + 1] - ty, t2 = core[o + 2] - tz;
+    double f0 = R[0] * t0 + R[1] * t1 + R[2] * t2 + cx;
+    double f1 = R[3] * t0 + R[4] * t1 + R[5] * t2 + cy;
+    double f2 = R[6] * t0 + R[7] * t1 + R[8] * t2 + cz;
+    if (!hard) {
+      const double p0 = pos[o], p1 = pos[o + 1], p2 = pos[o + 2];
+      f0 = p0 + w * (f0 - p0); f1 = p1 + w * (f1 - p1); f2 = p2 + w * (f2 - p2);
+    }
+    const float v0 = (float)f0, v1 = (float)f1, v2 = (float)f2;
+    pos[o] = v0; pos[o + 1] = v1; pos[o + 2] = v2;
+    if (copy_out) { copy_out[o] = v0; copy_out[o + 1] = v1; copy_out[o + 2] = v2; }
+  }
+  if (dev && lane == 0) dev[g] = (float)sqrt(fmax((gsum - 2.0 * lam) / m, 0.0));
+}
+
 // ---- handedness: the sampler cannot tell a molecule from its mirror image (the score network sees distances only), so the RMSD
 // to the mirror image, the parity of the stereocentres and the inversion of a wrong-handed conformer live here ----------------
 
@@ -1623,6 +1701,16 @@ extern "C" int agdiff_traj_rmsd(const float* frames, int64_t frame_stride, const
       k_traj_rmsd<false><<<dim3((unsigned)G, (unsigned)sc), dim3(64), 0, st>>>(f, frame_stride, target, select, graph_ptr, G, N, o, nullptr);
     AG_CHECK_LAUNCH();
   }
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_hold_core(float* pos, const float* core_pos, const uint8_t* select, const int32_t* graph_ptr, const int32_t* skip,
+                                int32_t G, int32_t N, float weight, float* copy_out, float* dev, void* stream) {
+  if (!pos || !core_pos || !select || !graph_ptr || G < 0 || N <= 0 || !(weight > 0.0f && weight <= 1.0f)) return AGDIFF_ERR_ARG;
+  if (copy_out == pos || core_pos == pos || (copy_out && copy_out == core_pos)) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_hold_core<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, core_pos, select, graph_ptr, skip, N, weight, copy_out, dev);
+  AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
 

@@ -13,7 +13,8 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
 --save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T; + `hand_<i>` [num_samples] with --fix-handedness, which needs
 `stereo_<i>` in the test set; + `valid_<i>`, `bond_dev_<i>` and `clash_<i>` [num_samples] with --check-geometry; + `rmsd_traj_<i>` [steps, num_samples] with --track-rmsd, which needs `pos_target_<i>` in the test set: every
-conformer's heavy-atom RMSD to that target after every step, + `rmsd_mirror_traj_<i>` with --track-rmsd-mirror) and the merged
+conformer's heavy-atom RMSD to that target after every step, + `rmsd_mirror_traj_<i>` with --track-rmsd-mirror; + `core_rmsd_<i>`
+[num_samples] with --hold-core for the molecules with `core_pos_<i>` / `core_mask_<i>` in the test set) and the merged
 `samples_all.npz`, written by rank 0 after a barrier.
 
 `--noise counter` draws every conformer's pos_init and noise from the counter-based generator under `--seed` and the conformer's
@@ -42,7 +43,9 @@ def num_confs(spec):
 def save_testset(path, molecules):
     """molecules: list of dicts with atom_type, edge_index, edge_type, num_refs, name; optionally stereo (int8 [n]: the target
     parity at the stereocentres, 0 elsewhere -- agdiff_amd.stereo), saved as `stereo_<i>` when present, and pos_target (float32
-    [n, 3]: the structure --track-rmsd follows every conformer's RMSD to -- agdiff_amd.trajectory), saved as `pos_target_<i>`."""
+    [n, 3]: the structure --track-rmsd follows every conformer's RMSD to -- agdiff_amd.trajectory), saved as `pos_target_<i>`, and
+    core_pos (float32 [n, 3]) with core_mask ([n], non-zero = the atom belongs to the core: the template --hold-core keeps those
+    atoms on -- agdiff_amd.core; rows of core_pos outside the mask are not read), saved as `core_pos_<i>` and `core_mask_<i>` (uint8)."""
     out = {"count": np.int64(len(molecules))}
     for i, m in enumerate(molecules):
         out["atom_type_%d" % i] = np.asarray(m["atom_type"], dtype=np.int64)
@@ -58,6 +61,16 @@ def save_testset(path, molecules):
             if target.shape != (n, 3):
                 raise ValueError("pos_target of molecule %d has shape %s, expected (%d, 3)" % (i, target.shape, n))
             out["pos_target_%d" % i] = target
+        if m.get("core_pos") is not None or m.get("core_mask") is not None:
+            n = np.asarray(m["atom_type"]).reshape(-1).shape[0]
+            if m.get("core_pos") is None or m.get("core_mask") is None:
+                raise ValueError("molecule %d: core_pos and core_mask come together" % i)
+            core, mask = np.asarray(m["core_pos"], dtype=np.float32), np.asarray(m["core_mask"])
+            if core.shape != (n, 3) or mask.shape != (n,):
+                raise ValueError("core_pos / core_mask of molecule %d have shapes %s / %s, expected (%d, 3) / (%d,)"
+                                 % (i, core.shape, mask.shape, n, n))
+            out["core_pos_%d" % i] = core
+            out["core_mask_%d" % i] = (mask != 0).astype(np.uint8)
     np.savez_compressed(path, **out)
 
 
@@ -72,6 +85,8 @@ def load_testset(path):
             mols[-1]["stereo"] = z["stereo_%d" % i]
         if "pos_target_%d" % i in z.files:
             mols[-1]["pos_target"] = z["pos_target_%d" % i]
+        if "core_pos_%d" % i in z.files and "core_mask_%d" % i in z.files:
+            mols[-1]["core_pos"], mols[-1]["core_mask"] = z["core_pos_%d" % i], z["core_mask_%d" % i]
     return mols
 
 
@@ -144,9 +159,11 @@ def pack_batch(mols, confs_of):
     """repeat_data (utils/misc.py:88-90) for every molecule of the batch, concatenated.  When every molecule carries its `index`
     (load_testset), `stream_ids` [num_graphs] names each graph's random stream (stream_id, attempt 0): the ids travel with the
     graphs through subset_batch and dist.shard_of.  When every molecule carries a `pos_target` [n, 3], `pos_target` [N, 3] holds it
-    once per conformer (float32): what the sampler tracks every graph's RMSD to (--track-rmsd)."""
+    once per conformer (float32): what the sampler tracks every graph's RMSD to (--track-rmsd).  When ANY molecule carries a core
+    (`core_pos` [n, 3] + `core_mask` [n]), `core_pos` [N, 3] float32 and `core_select` [N] uint8 hold them once per conformer, zeros
+    for the molecules without one: what the sampler holds (--hold-core)."""
     from .synth import repeat_molecule
-    ats, rs, cs, ts, bs, spans, ids, targets = [], [], [], [], [], [], [], []
+    ats, rs, cs, ts, bs, spans, ids, targets, cores, masks = [], [], [], [], [], [], [], [], [], []
     node_off, g_off = 0, 0
     for m in mols:
         g = confs_of(m["num_refs"])
@@ -159,6 +176,12 @@ def pack_batch(mols, confs_of):
             ids.append(stream_id(int(m["index"]), np.arange(g, dtype=np.int64)))
         if isinstance(m, dict) and m.get("pos_target") is not None:
             targets.append(np.tile(np.asarray(m["pos_target"], dtype=np.float32).reshape(n, 3), (g, 1)))
+        if isinstance(m, dict) and m.get("core_pos") is not None and m.get("core_mask") is not None:
+            cores.append(np.tile(np.asarray(m["core_pos"], dtype=np.float32).reshape(n, 3), (g, 1)))
+            masks.append(np.tile((np.asarray(m["core_mask"]).reshape(n) != 0).astype(np.uint8), g))
+        else:
+            cores.append(None)
+            masks.append(np.zeros(n * g, dtype=np.uint8))
         node_off += n * g
         g_off += g
     out = dict(atom_type=np.concatenate(ats), bond_index=np.stack([np.concatenate(rs), np.concatenate(cs)]),
@@ -167,6 +190,9 @@ def pack_batch(mols, confs_of):
         out["stream_ids"] = np.concatenate(ids) if ids else np.zeros(0, dtype=np.int64)
     if mols and len(targets) == len(mols):
         out["pos_target"] = np.concatenate(targets)
+    if any(c is not None for c in cores):
+        out["core_pos"] = np.concatenate([np.zeros((k.shape[0], 3), dtype=np.float32) if c is None else c for c, k in zip(cores, masks)])
+        out["core_select"] = np.concatenate(masks)
     return out
 
 
@@ -220,7 +246,7 @@ def _prepare_in_worker(bmols, confs, rank, world, topo_opts):
 
 
 def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_retry=2, log=print, pos_init=None,
-                 noise=None, topology=None, counter_seed=None, *, curves=None):
+                 noise=None, topology=None, counter_seed=None, *, curves=None, core=None):
     """test.py:143-181 for every molecule of a packed batch: a molecule in which a NaN appeared is sampled again
     (fresh pos_init) with clip_local=20, at most `max_retry` attempts in all, and dropped after that; the molecules
     packed with it keep their first result -- graphs are independent on the whole path, and the update kernel flags
@@ -234,7 +260,11 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
     (the same draws in wider arithmetic).
     `curves`: a dict to fill with the tracked RMSD curves (epsnet.LangevinRun: rmsd_target = the batch's `pos_target`, heavy atoms):
     curves["rmsd"] float32 [steps, num_graphs] and, when it came in with curves["mirror"] true, curves["rmsd_mirror"].  A molecule's
-    columns come from the pass that succeeded; columns of dropped molecules are NaN."""
+    columns come from the pass that succeeded; columns of dropped molecules are NaN.
+    `core`: a dict {"weight": w, "start_sigma": s}: the batch's `core_pos` / `core_select` are held while sampling
+    (epsnet.LangevinRun: core_pos, core_select, core_weight, core_start_sigma; agdiff_amd/core.py) in every pass whose molecules
+    include one with a core; it comes back with core["dev"] float32 [num_graphs], the run's `core_dev` of the pass that succeeded
+    (NaN for graphs without a core and for dropped molecules)."""
     import torch
     T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
     spans = packed["spans"]
@@ -245,6 +275,12 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
             raise ValueError("tracking the RMSD needs `pos_target` in the packed batch (every molecule with its pos_target)")
         if not hasattr(model, "begin_sampling"):
             raise ValueError("tracking the RMSD needs a model with begin_sampling")
+    if core is not None:
+        if packed.get("core_pos") is None or packed.get("core_select") is None:
+            raise ValueError("holding a core needs `core_pos` and `core_select` in the packed batch (a molecule with its core_pos / core_mask)")
+        if not hasattr(model, "begin_sampling"):
+            raise ValueError("holding a core needs a model with begin_sampling")
+        core["dev"] = torch.full((int(packed["num_graphs"]),), float("nan"))
     if not hasattr(model, "begin_sampling"):
         at, bi, bt, ba = T(packed["atom_type"]), T(packed["bond_index"]), T(packed["bond_type"]), T(packed["batch"])
         clip_local = None
@@ -287,6 +323,10 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
             extra = {"topology": topology} if (topology is not None and sub is packed) else {}
             if curves is not None:
                 extra.update(rmsd_target=sub["pos_target"], rmsd_mirror=bool(curves.get("mirror")))
+            held = core is not None and bool(np.asarray(sub["core_select"]).any())      # (a retry of molecules without a core: as ever)
+            if held:
+                extra.update(core_pos=sub["core_pos"], core_select=sub["core_select"], core_weight=core.get("weight", 1.0),
+                             core_start_sigma=core.get("start_sigma", float("inf")))
             run = model.begin_sampling(at, p0, bi, bt, ba, sub["num_graphs"], False, clip_local=clip_local,
                                        save_traj=save_traj, raise_on_nan=False,
                                        noise=(noise if first else None), **extra, **counter, **sampler_kwargs)
@@ -305,6 +345,8 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
                                                  traj_out if save_traj else None, traj if save_traj else None)
         if curves is not None:
             _sort_curves(curves, run, todo, sub["spans"], spans, set(nan_failed) | set(range_failed))
+        if held:
+            _sort_per_graph(core["dev"], run.core_dev, todo, sub["spans"], spans, set(nan_failed) | set(range_failed))
         if out_of_range:
             SAMPLE_STATS["range_trips"] += len(out_of_range)
         if range_failed:
@@ -362,6 +404,22 @@ def _sort_curves(curves, run, todo, sub_spans, spans, failed):
             g_off += g
 
 
+def _sort_per_graph(out, got, todo, sub_spans, spans, failed):
+    """One pass's per-graph values `got` [graphs of the pass] (run.core_dev): the entries of the molecules that succeeded go into
+    `out` [graphs of `packed`]."""
+    gfirst = np.concatenate([[0], np.cumsum([g for (_, _, g) in spans])])
+    g_off = 0
+    for slot, (_, _, g) in zip(todo, sub_spans):
+        if slot not in failed:
+            out[gfirst[slot]:gfirst[slot] + g] = got[g_off:g_off + g]
+        g_off += g
+
+
+def _has_core(m):
+    """The molecule carries a template and a mask that selects an atom."""
+    return m.get("core_pos") is not None and m.get("core_mask") is not None and bool(np.asarray(m["core_mask"]).any())
+
+
 def _check_counter(model, packed, counter_seed):
     """--noise counter needs the batch's stream ids (pack_batch: every molecule with its `index`) and a model that draws from
     the counter-based generator."""
@@ -416,6 +474,8 @@ def subset_batch(packed, slots):
         sub["stream_ids"] = np.asarray(packed["stream_ids"])[np.concatenate(keep_graphs).astype(np.int64)]
     if packed.get("pos_target") is not None:
         sub["pos_target"] = np.asarray(packed["pos_target"])[keep]
+    if packed.get("core_pos") is not None:
+        sub["core_pos"], sub["core_select"] = np.asarray(packed["core_pos"])[keep], np.asarray(packed["core_select"])[keep]
     return sub
 
 
@@ -459,7 +519,8 @@ def merge_outputs(out_dir):
 def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, save_traj=False, resume=False,
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
             fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, repair_geometry=False,
-            check_planarity=False, repair_planarity=False, check_geometry=False):
+            check_planarity=False, repair_planarity=False, hold_core=False, core_weight=1.0, core_start_sigma=float("inf"),
+            check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -503,7 +564,30 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     molecule's `pos_target` (load_testset: `pos_target_<i>`; a molecule without one is an error) after every denoising step,
     computed while the run samples (agdiff_amd.trajectory), with or without save_traj; track_rmsd_mirror=True adds
     `rmsd_mirror_traj_<i>`, the RMSD of the mirror image.  Not with graph-sharded sampling (shard=True, what --dist-mode shard is over
-    several ranks: each rank updates only its own graphs); whole batches per rank (shard=False) work."""
+    several ranks: each rank updates only its own graphs); whole batches per rank (shard=False) work.
+    hold_core=True: conformers around a fixed core (agdiff_amd.core).  A molecule with `core_pos` / `core_mask`
+    (load_testset: `core_pos_<i>`, `core_mask_<i>`; no molecule with one is an error) is sampled with those atoms held to the
+    template's internal geometry: its batch runs with epsnet.LangevinRun's core_pos / core_select, core_weight (in (0, 1]) and
+    core_start_sigma (hold only below this noise level; the last step is always held exactly); batches without such a molecule are
+    sampled as ever.  Before anything else is done to them its conformers are superposed on `core_pos_<i>` over the core atoms
+    (agdiff_align_conformers), so `pos_gen_<i>` is in the template's frame with the core atoms on the template, and
+    `core_rmsd_<i>` float32 [G] says how far the last denoising step had pulled each conformer's core out of shape before the
+    closing hold.  Not with graph-sharded sampling (shard=True); whole batches per rank (shard=False) work."""
+    if hold_core:
+        from .core import core_arguments
+        if not any(_has_core(m) for m in mols):
+            raise ValueError("hold_core needs `core_pos_<i>` and `core_mask_<i>` in the test set; none of the %d molecules has them"
+                             % len(mols))
+        if shard:
+            raise ValueError("hold_core does not work with graph-sharded sampling (shard=True, %d ranks: each rank updates only its "
+                             "own graphs); use --dist-mode batches" % world)
+        for m in mols:
+            if _has_core(m):
+                try:
+                    core_arguments(m["atom_type"].shape[0], m["core_pos"], m["core_mask"], core_weight, core_start_sigma)
+                except ValueError as e:
+                    raise ValueError("hold_core, molecule %s: %s" % (m["name"], e))
+    hold = dict(weight=float(core_weight), start_sigma=float(core_start_sigma)) if hold_core else None
     track_rmsd = bool(track_rmsd or track_rmsd_mirror)
     if track_rmsd:
         missing = [m["name"] for m in mols if m.get("pos_target") is None]
@@ -585,7 +669,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
                                 world, counter_seed, prune_rms, fix_handedness, prune_tfd,
                                 ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_planarity,
-                                repair_planarity, check_geometry)
+                                repair_planarity, hold, check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -595,7 +679,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
                      counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, repair_geometry=False,
-                     check_planarity=False, repair_planarity=False, check_geometry=False):
+                     check_planarity=False, repair_planarity=False, hold=None, check_geometry=False):
     import torch.distributed as dist
     mirrored = undecided = checked = invalid = repaired = stuck = seen = judged = bent = 0
     for pos_in_mine, bidx in enumerate(mine):
@@ -623,8 +707,10 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 continue
         else:
             curves = dict(track) if track is not None else None
+            core = dict(hold) if (hold is not None and packed.get("core_pos") is not None) else None
             pos, traj, ok = sample_batch(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log, topology=topology,
-                                         counter_seed=counter_seed, **({"curves": curves} if curves is not None else {}))
+                                         counter_seed=counter_seed, **({"curves": curves} if curves is not None else {}),
+                                         **({"core": core} if core is not None else {}))
         if not ok.any():
             log("batch %d: every molecule failed twice (NaN); skipped: %s" % (bidx, [m["name"] for m in bmols]))
             continue
@@ -641,6 +727,11 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                         out[name % m["index"]] = curves[key][:, g_first - g:g_first].numpy().copy()
             out["pos_gen_%d" % m["index"]] = pos[off:off + n * g].numpy().reshape(g, n, 3)
             out["name_%d" % m["index"]] = np.str_(m["name"])
+            if hold is not None and _has_core(m):
+                from .core import to_template_frame          # (first: what follows then sees the conformers in the template's frame)
+                out["pos_gen_%d" % m["index"]] = to_template_frame(out["pos_gen_%d" % m["index"]], m["core_pos"], m["core_mask"],
+                                                                   device=device).cpu().numpy()
+                out["core_rmsd_%d" % m["index"]] = core["dev"][g_first - g:g_first].numpy().astype(np.float32)
             if fix_handedness:
                 import torch
                 from .stereo import fix_handedness as fix
@@ -783,6 +874,17 @@ def main(argv=None):
                          "--dist-mode shard over several ranks")
     ap.add_argument("--track-rmsd-mirror", action="store_true",
                     help="--track-rmsd plus rmsd_mirror_traj_<i>: the RMSD of each conformer's mirror image to the target")
+    ap.add_argument("--hold-core", action="store_true",
+                    help="sample the molecules that carry core_pos_<i> / core_mask_<i> in the test set around that core: its atoms keep "
+                         "the template's internal geometry through the run (agdiff_amd.core; the core floats rigidly with the rest), "
+                         "pos_gen_<i> is superposed on the template over the core atoms and core_rmsd_<i> [num_samples] says how hard the "
+                         "last step pulled against the hold; the other molecules are sampled as ever; not with --dist-mode shard over "
+                         "several ranks")
+    ap.add_argument("--core-weight", type=float, default=1.0,
+                    help="with --hold-core: the fraction of the way the core atoms are moved to the fitted template after every step, in "
+                         "(0, 1]; the last step is always held exactly")
+    ap.add_argument("--core-start-sigma", type=float, default=float("inf"),
+                    help="with --hold-core: hold only after steps whose noise level sigma is below this (default: from the first step)")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
     ap.add_argument("--dist-mode", default="shard", choices=["shard", "batches"],
                     help="with several ranks: 'shard' = every packed batch (max-atoms x world atoms) is split into "
@@ -827,7 +929,8 @@ def main(argv=None):
             resume=args.resume, rank=rank, world=world, shard=(world > 1 and args.dist_mode == "shard"), noise=args.noise,
             seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
             check_geometry=args.check_geometry, check_planarity=args.check_planarity, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror,
-            repair_planarity=args.repair_planarity)
+            repair_planarity=args.repair_planarity, hold_core=args.hold_core, core_weight=args.core_weight,
+            core_start_sigma=args.core_start_sigma)
     if own_pg:
         dist.destroy_process_group()
 

@@ -646,6 +646,15 @@ class DualEncoderEpsNetwork(nn.Module):
                            with rmsd_mirror=True `rmsd_curve_mirror`, the RMSD to the mirror image.  rmsd_select [N]: the atoms
                            that enter (default: the heavy atoms, atom_type != 1).  Works without save_traj (a ring of
                            2 x nan_check_every frames); no step graphs in such a run.  What the call returns does not change.
+          core_pos         [N, 3] with core_select [N] bool: sample around a fixed core (agdiff_amd/core.py).  After the
+                           update of every step with sigma < core_start_sigma (default inf: every step) the selected atoms of each
+                           graph are moved the fraction core_weight (in (0, 1], default 1) of the way to the template's selected
+                           atoms superposed on where they are now (agdiff_hold_core): the core keeps its internal geometry and
+                           floats rigidly with the rest.  The hold after the last step always runs, with weight 1; the run
+                           (begin_sampling) then has `core_dev`, after finish() a float32 host tensor [G]: the RMSD by which that
+                           last step had pulled each core out of shape.  A graph without a selected atom is sampled freely.  Such
+                           a run goes launch by launch (no fused front, no step graphs).  Nothing is put into the template's frame:
+                           superpose the result on core_pos afterwards (driver.run_job(hold_core=True) does)
           traj_overlap_min_bytes  the trajectory goes to the host while the run samples when a poll interval's chunk
                            (nan_check_every x N x 12 B) is at least this large (default 16 MiB); else one copy at the end
         """
@@ -659,6 +668,10 @@ class DualEncoderEpsNetwork(nn.Module):
                        extend_radius=True, n_steps=5000, step_lr=0.0000010, clip=1000, clip_local=None,
                        clip_pos=None, global_start_sigma=float("inf"), w_global=0.2, **kwargs):
         """Set up one sampling job (dualenc.py:468-476) and return a LangevinRun that enqueues steps."""
+        if kwargs.get("core_pos") is not None or kwargs.get("core_select") is not None:      # (a ValueError needs no GPU)
+            from .core import core_arguments
+            core_arguments(atom_type.shape[0], kwargs.get("core_pos"), kwargs.get("core_select"), kwargs.get("core_weight", 1.0),
+                           kwargs.get("core_start_sigma", float("inf")))
         self._require_gpu()
         return LangevinRun(self, atom_type, pos_init, bond_index, bond_type, batch, num_graphs, extend_order,
                            n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global,
@@ -698,11 +711,14 @@ class LangevinRun:
                  n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global, noise=None,
                  save_traj=True, skip_discarded_global=True, nan_check_every=64, step_indices=None, on_step=None,
                  extend_radius=True, raise_on_nan=True, noise_mode="chunked", traj_overlap_min_bytes=16 << 20, topology=None,
-                 noise_seed=None, stream_ids=None, *, rmsd_target=None, rmsd_select=None, rmsd_mirror=False, **_ignored):
+                 noise_seed=None, stream_ids=None, *, rmsd_target=None, rmsd_select=None, rmsd_mirror=False, core_pos=None,
+                 core_select=None, core_weight=1.0, core_start_sigma=float("inf"), **_ignored):
         if noise_mode not in ("chunked", "per_step", "counter"):
             raise ValueError("noise_mode must be 'chunked', 'per_step' or 'counter'")
         if noise_mode == "counter" and (noise_seed is None or stream_ids is None):
             raise ValueError("noise_mode='counter' needs noise_seed (int) and stream_ids (int64 [num_graphs])")
+        from .core import core_arguments
+        core = core_arguments(atom_type.shape[0], core_pos, core_select, core_weight, core_start_sigma)
         self.model, self.lib = model, _lib.load()
         dev = model._device()
         self.sigmas = ((1.0 - model.alphas).sqrt() / model.alphas.sqrt()).detach().cpu()
@@ -742,6 +758,17 @@ class LangevinRun:
             if self.traj is None:
                 rows = max(1, min(2 * max(int(nan_check_every), 1), len(self.steps)))
                 self._rmsd_ring = torch.empty((rows, N, 3), dtype=torch.float32, device=dev)
+        # core_pos [N, 3] + core_select [N]: the rigid core hold (agdiff_amd/core.py).  After the update of every
+        # step with sigma < core_start_sigma one agdiff_hold_core launch puts the template's selected atoms where each graph's core
+        # is now (blended by core_weight), in self.pos and in the frame the update has just written; the hold after the run's last
+        # step always runs, with weight 1, and leaves `core_dev` [G]: how far that step had pulled each core out of shape (on the
+        # host after finish(); NaN for a graph without a core and for a quarantined one).  Nothing may run between a step's update
+        # and the next step's radius graph in agdiff_sampler_front, so such a run goes launch by launch (_fused_front).
+        self._core, self.core_dev = None, None
+        if core is not None:
+            tpl, sel, self._core_weight, self._core_start = core
+            self._core = (torch.from_numpy(tpl).to(dev), torch.from_numpy(sel).to(dev))
+            self._core_dev = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
         self.noise, self.on_step = noise, on_step
         self.step_lr, self.global_start_sigma = step_lr, global_start_sigma
         self.skip_discarded, self.nan_every = bool(skip_discarded_global), int(nan_check_every)
@@ -779,7 +806,8 @@ class LangevinRun:
         sg = getattr(model, "step_graphs", "auto")
         self._use_graphs = bool((sg is True or (sg == "auto" and N <= model.STEP_GRAPH_MAX_NODES)) and on_step is None and
                                 noise_mode == "chunked" and self.pk.poly_kt > 0 and getattr(model, "fused_front", True) and
-                                not getattr(model, "front_split_graph", False) and not self.topo.large and self._rmsd is None)
+                                not getattr(model, "front_split_graph", False) and not self.topo.large and self._rmsd is None and
+                                self._core is None)
         self._graphs, self._step_table, self._step_index, self._dev_index = {}, None, None, None
         # (a capture needs a stream of its own: the legacy default stream, which torch hands out as the current one, cannot be captured)
         self._gstream = torch.cuda.Stream(device=dev) if self._use_graphs else None
@@ -845,8 +873,9 @@ class LangevinRun:
         radius graph of step t + 1): whenever the radius edges have their polynomials and the graph is built here.  Not for a
         batch with a molecule of more than AGDIFF_MAX_ATOMS_PER_GRAPH atoms (topo.large): agdiff_sampler_front keeps a
         molecule's masks in LDS; such a batch runs update, graph build (agdiff_graph_build_large) and forward launch by launch,
-        and with them no step graphs (they replay the fused front)."""
-        return self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large
+        and with them no step graphs (they replay the fused front).  Nor for a run that holds a core: agdiff_hold_core has to run
+        between a step's update and the next step's radius graph, which agdiff_sampler_front does in one launch."""
+        return self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large and self._core is None
 
     def _fill_args(self, a, k, dev, N):
         sig, step_size, noise_scale, use_global = self._sched[k]
@@ -1022,12 +1051,29 @@ class LangevinRun:
                 self._stage0_done = self._stage0_done or bool(run_global)
                 _lib.check(lib.agdiff_langevin_update(ctypes.byref(topo.struct), ctypes.byref(ws.struct),
                                                       ctypes.byref(a), stream), "agdiff_langevin_update")
+                if self._core is not None:
+                    self._hold_core(k, sig)
                 self.k += 1
                 self._traj_ready = self.k
                 if self.on_step is not None:
                     self.on_step(k, i, self.pos)
                 if self.k % self.nan_every == 0 or self.k == len(self.steps):
                     self.check_nan()
+
+    def _hold_core(self, k, sigma):
+        """The hold after the update of step k (launch-by-launch path only): one agdiff_hold_core launch on the current stream for
+        a step with sigma < core_start_sigma, over self.pos and the frame the update has just written (_traj_row(k)), skipping
+        the graphs the update kernels have quarantined (ws.nan_flag[1:]: they carry a placeholder).  After the LAST step of the
+        schedule it runs whatever sigma and core_weight say, with weight 1: what the run returns holds the core exactly."""
+        last = k == len(self.steps) - 1
+        if not (last or sigma < self._core_start):
+            return
+        tpl, sel = self._core
+        G = self.topo.G
+        skip = ctypes.c_void_p(self.ws.nan_flag.data_ptr() + 4)          # (element 0 is the "any graph" flag)
+        _lib.check(self.lib.agdiff_hold_core(self.pos_p, _lib.ptr(tpl), _lib.ptr(sel), _lib.ptr(self.topo.graph_ptr), skip, G, self.topo.N,
+                                             1.0 if last else self._core_weight, self._traj_row(k), _lib.ptr(self._core_dev),
+                                             _lib.stream_ptr()), "agdiff_hold_core")
 
     def check_nan(self):
         """dualenc.py:539-541.  ws.nan_flag[0] is set by the update kernel as soon as any position is NaN.  Polled every
@@ -1122,6 +1168,8 @@ class LangevinRun:
                     rows[:, bad] = float("nan")
                 curves.append(rows)
             self.rmsd_curve, self.rmsd_curve_mirror = curves
+        if self._core is not None:
+            self.core_dev = self._core_dev.cpu()
         if self.traj is not None and self._traj_overlap:
             self._traj_send(self.k)
             self._traj_land()

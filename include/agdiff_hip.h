@@ -1021,6 +1021,38 @@ int agdiff_traj_rmsd(const float* frames, int64_t frame_stride /* floats between
                      int32_t S, int32_t G, int32_t N, float* out /* [S][G] */, float* out_mirror /* [S][G] or null */,
                      void* stream);
 
+/* ---- rigid core hold ------------------------------------------------------------------------------------------------------
+ * Conformers around a fixed core (what rdkit's coordMap / ConstrainedEmbed are used for): epsnet.LangevinRun calls this after a
+ * step's update, so that the selected atoms of every graph keep the INTERNAL geometry of a template while the core floats rigidly
+ * with the rest of the molecule (the score network sees distances only).
+ *
+ * agdiff_hold_core: for graph g with selected atoms A (m = |A|), in place:
+ *   fit_a  = R (t_a - c_t) + c_x     c_x, c_t the centroids of pos[A] and core_pos[A]; R the proper rotation (Horn's quaternion of
+ *                                    lambda_max of the cross-covariance, cyclic Jacobi) that takes the centred template onto the
+ *                                    centred current core; all of it in fp64 from the stored fp32 coordinates
+ *   pos[a] = pos[a] + weight (fit_a - pos[a]) for a in A, rounded to fp32 once; weight == 1 stores fit_a itself.  Atoms outside
+ *            A are not written: they keep their bits.
+ *   pos [N][3]             a packed batch, read and written
+ *   core_pos [N][3]        the template, packed like pos; need not be centred; only the selected rows are read
+ *   select [N] uint8       1 = the atom belongs to the core
+ *   graph_ptr [G + 1]      first atom of every graph (agdiff_topo_t.graph_ptr); entries are clamped to [0, N]
+ *   skip [G] int32 or null != 0: the graph is left alone (agdiff_ws_t.nan_flag + 1: a quarantined graph holds a placeholder)
+ *   weight                 in (0, 1], else AGDIFF_ERR_ARG
+ *   copy_out [N][3] or null  the values written to pos[a], a in A, go to copy_out[a] too (the trajectory row the update kernel has
+ *                          just written); no other entry is touched.  Not pos, not core_pos.
+ *   dev [G] or null        sqrt(max((sum |x - c_x|^2 + sum |t - c_t|^2 - 2 lambda_max) / m, 0)): the RMSD over A between the core
+ *                          BEFORE this call and the fit -- how far the step before pulled the core out of shape
+ * A graph is left untouched, with dev[g] = NaN, when it has no selected atom, when skip[g] != 0, or when a selected coordinate of
+ * pos or of core_pos is not finite.  Any m >= 1: m = 1 leaves the atom where it is; where the rotation is not unique (m = 2,
+ * collinear atoms) one maximiser is taken, as by agdiff_align_conformers.  Proper rotations only: a template is held in ITS
+ * handedness.  Identity atom mapping.  One 64-lane wave per graph, lanes striding over the graph's atoms: any number of atoms
+ * per graph.  Every read that feeds the sums is reduced across the wave before the first store.  No atomics, deterministic bit
+ * for bit. */
+int agdiff_hold_core(float* pos /* [N][3], in place */, const float* core_pos /* [N][3] */, const uint8_t* select /* [N] */,
+                     const int32_t* graph_ptr /* [G + 1] */, const int32_t* skip /* [G] or null: != 0 leaves the graph alone */,
+                     int32_t G, int32_t N, float weight /* (0, 1] */, float* copy_out /* [N][3] or null */,
+                     float* dev /* [G] or null */, void* stream);
+
 /* ---- distance-distribution MMD -----------------------------------------------------------------------------------------
  * The maximum mean discrepancy between the interatomic-distance distributions of the generated and the reference conformers of
  * one molecule, as the ConfGF / CGCF / GraphDG line reports it ("all", and "single" per atom pair; their "pair" mode, over all
