@@ -124,6 +124,52 @@ __device__ __forceinline__ void ag_store_row(const f32x4 (&y)[NY], float* __rest
 #pragma unroll
   for (int t = 0; t < NT; ++t) ag_st4(row + 16 * t + 4 * q, y[T0 + t]);
 }
+// Coalesced row moves.  In the layout above adjacent lanes hold different rows, so a row load or store is 64 separate 16-byte
+// L1 accesses per wave instruction: the four lanes on 64 contiguous bytes of one row sit 16 lanes apart.  In the PIECE layout
+//     lane 4p + c  <->  tile row p, 16-byte piece c of a 64-byte run
+// four adjacent lanes cover the 64 bytes, a quarter of the accesses for the same bytes.  One fixed lane permutation
+// (ds_bpermute_b32: the LDS crossbar, no LDS memory) moves a dword between the two layouts:
+//     operand lane 16q + p  <->  piece lane 4p + q
+// Only fp32 dwords move, before ag_cvt and after the last layer, so the three arithmetic modes share the helpers and every
+// operation sees the operands it saw in the operand layout.  Call them with all 64 lanes active.
+__device__ __forceinline__ int ag_to_operand_addr(int lane) { return (4 * (lane & 15) + (lane >> 4)) << 2; }   // lane 16q + p reads lane 4p + q
+__device__ __forceinline__ int ag_to_piece_addr(int lane) { return (16 * (lane & 3) + (lane >> 2)) << 2; }     // lane 4p + c reads lane 16c + p
+__device__ __forceinline__ f32x4 ag_permute4(const f32x4& v, int addr) {
+  f32x4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v[r])));
+  return o;
+}
+// What the operand layout holds per tile row (a row index, a flag: the same in all four quarters), for the row lane >> 2 that
+// the lane serves in the piece layout.
+__device__ __forceinline__ int ag_piece_row_value(int v, int lane) { return __builtin_amdgcn_ds_bpermute(lane & ~3, v); }
+// k-tile k (32 features) of a row in the piece layout: v0 = the lane's piece of features 32k .. 32k+15, v1 of 32k+16 .. 32k+31;
+// `row` belongs to tile row lane >> 2.  ag_permute4(v, ag_to_operand_addr(lane)) of the two are ag_cvt's arguments.
+__device__ __forceinline__ void ag_load_slice_pieces(f32x4& v0, f32x4& v1, const float* __restrict__ row, int k, int lane) {
+  const float* p = row + 32 * k + 4 * (lane & 3);
+  v0 = ag_ld4(p);
+  v1 = ag_ld4(p + 16);
+}
+// ag_load_row through the piece layout: `row` belongs to tile row lane >> 2; the tiles arrive in the operand layout.
+template <int NT, int T0, int NY>
+__device__ __forceinline__ void ag_load_row_pieces(f32x4 (&y)[NY], const float* __restrict__ row, int lane) {
+  const int addr = ag_to_operand_addr(lane);
+  f32x4 v[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) v[t] = ag_ld4(row + 16 * t + 4 * (lane & 3));
+#pragma unroll
+  for (int t = 0; t < NT; ++t) y[T0 + t] = ag_permute4(v[t], addr);
+}
+// ag_store_row through the piece layout: `row` and `ok` belong to tile row lane >> 2 (ag_piece_row_value of the operand layout's).
+template <int NT, int T0, int NY>
+__device__ __forceinline__ void ag_store_row_pieces(const f32x4 (&y)[NY], float* __restrict__ row, bool ok, int lane) {
+  const int addr = ag_to_piece_addr(lane);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const f32x4 v = ag_permute4(y[T0 + t], addr);
+    if (ok) ag_st4(row + 16 * t + 4 * (lane & 3), v);
+  }
+}
 // sum_f w[f] * y[f] over the first NT tiles for the lane's edge (all four quarters hold the total)
 template <int NT, int NY>
 __device__ __forceinline__ float ag_dot_vec(const f32x4 (&y)[NY], const float* __restrict__ w, int q) {

@@ -651,39 +651,50 @@ __global__ void __launch_bounds__(64 * AG_PERSIST_WAVES, 4) k_pair_head(HeadArgs
     const int64_t e = tile * AG_TW + (lane & 15);
     const bool valid = e < E;
     const int s = valid ? a.src[e] : 0, t = valid ? a.dst[e] : 0;
-    const int64_t pe = a.pos_index ? (valid ? (int64_t)a.pos_index[e] : 0) : e;     // where the edge's attrs / result live
-    const int64_t pm = (a.pos_index && valid) ? (int64_t)a.mir_index[e] : -1;
+    const int pp = (a.pos_index && valid) ? a.pos_index[e] : 0;     // with pos_index: where the edge's attrs / result live
 
     // first layer over eight 32-feature k-tiles of [h_src * h_dst || edge_attr] (pkk weights)
     f32x4 y1[8];
     ag_init_vec<8>(y1, a.hp.b1, q);
     {
-      const float* hs = a.node_h + (size_t)s * 128;
-      const float* ht = a.node_h + (size_t)t * 128;
+      // h and edge_attr rows in the piece layout (common.hpp: coalesced row moves): the lane reads the rows of tile row
+      // lane >> 2; h_src * h_dst is formed there and only the product is permuted into the operand layout
+      const float* hs = a.node_h + (size_t)ag_piece_row_value(s, lane) * 128;
+      const float* ht = a.node_h + (size_t)ag_piece_row_value(t, lane) * 128;
+      const int64_t er = tile * AG_TW + (lane >> 2);
+      const float* ar = a.attr_rows + (size_t)(er < E ? er : 0) * 128;       // (used with attr_rows only)
+      const int to_op = ag_to_operand_addr(lane);
       AgIn<MODE> sl[2];
-      auto load_slice = [&](AgIn<MODE>& dst, int k) {
+      f32x4 raw[4];
+      // slice k: `fetch` issues its loads (edge_attr in operand form goes straight to its place), `finish` turns fetched rows
+      // into the operand
+      auto fetch = [&](f32x4 (&r)[4], AgIn<MODE>& dst, int k) {
         if (k < 4) {
-          const f32x4 p0 = ag_ld4(hs + 32 * k + 4 * q) * ag_ld4(ht + 32 * k + 4 * q);
-          const f32x4 p1 = ag_ld4(hs + 32 * k + 16 + 4 * q) * ag_ld4(ht + 32 * k + 16 + 4 * q);
-          ag_cvt(p0, p1, dst);
+          ag_load_slice_pieces(r[0], r[1], hs, k, lane);
+          ag_load_slice_pieces(r[2], r[3], ht, k, lane);
         } else if (a.attr_frag && a.pos_index) {
-          ag_load_attr(dst, a.attr_frag, pe >> 4, k - 4, q * 16 + (int)(pe & 15));
+          ag_load_attr(dst, a.attr_frag, (int64_t)(pp >> 4), k - 4, q * 16 + (pp & 15));
         } else if (a.attr_frag) {
           ag_load_attr(dst, a.attr_frag, tile, k - 4, lane);
         } else {
-          const float* ar = a.attr_rows + (size_t)(valid ? e : 0) * 128 + 32 * (k - 4) + 4 * q;
-          ag_cvt(ag_ld4(ar), ag_ld4(ar + 16), dst);
+          ag_load_slice_pieces(r[0], r[1], ar, k - 4, lane);
         }
       };
-      load_slice(sl[0], 0);
+      auto finish = [&](AgIn<MODE>& dst, const f32x4 (&r)[4], int k) {
+        if (k < 4) ag_cvt(ag_permute4(r[0] * r[2], to_op), ag_permute4(r[1] * r[3], to_op), dst);
+        else if (!a.attr_frag) ag_cvt(ag_permute4(r[0], to_op), ag_permute4(r[1], to_op), dst);
+      };
+      fetch(raw, sl[0], 0);
+      finish(sl[0], raw, 0);
       const lds_u32x4* lw1_lo = ag_lds_base(lw1, lane);
       const lds_u32x4* lw1_hi = ag_lds_base(lw1 + 32 * 128, lane);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        if (k + 1 < 8) load_slice(sl[(k + 1) & 1], k + 1);
+        if (k + 1 < 8) fetch(raw, sl[(k + 1) & 1], k + 1);       // one slice ahead: the loads fly during slice k's MFMAs
         const lds_u32x4* wk = (k < 4) ? lw1_lo + (k * 8) * 128 : lw1_hi + ((k - 4) * 8) * 128;
         if (k & 1) ag_dense_lds<MODE, false, true, 1, 8, 1, 0>(sl, y1, wk, 0);
         else ag_dense_lds<MODE, false, true, 1, 8, 0, 0>(sl, y1, wk, 0);
+        if (k + 1 < 8) finish(sl[(k + 1) & 1], raw, k + 1);
       }
     }
     ag_head_act<8>(y1, a.hp.act);
@@ -698,7 +709,12 @@ __global__ void __launch_bounds__(64 * AG_PERSIST_WAVES, 4) k_pair_head(HeadArgs
     ag_head_act<4>(y2, a.hp.act);
     const float o = ag_dot_vec<4>(y2, a.hp.w3, q) + a.hp.b3;
     if (valid && q == 0) {
-      a.out[pe] = o;
+      // (the list position and the mirror are formed here, not held in registers across the chain)
+      int l2 = lane0;
+      asm volatile("" : "+v"(l2));
+      const int64_t e2 = tile * AG_TW + (l2 & 15);
+      a.out[a.pos_index ? (int64_t)pp : e2] = o;
+      const int pm = a.pos_index ? a.mir_index[e2] : -1;
       if (pm >= 0) a.out[pm] = o;
     }
   }
@@ -765,7 +781,8 @@ struct AttrPolyArgs {
 // here (features once, one masked MFMA round per coefficient set present in the tile); the other rows are flagged for the
 // encoder MLP (agdiff_local_edge_rows).
 // One 16-wave workgroup per CU: the kernel is bound by its row stores (0.055 ms without them, 0.135 with, at 8 waves; twice the
-// tiles in flight drain them 6 % faster: 0.127 ms for 417 MB on the 196 k-atom batch).
+// tiles in flight drain them 6 % faster: 0.127 ms for 417 MB on the 196 k-atom batch; written in 64-byte runs through the piece
+// layout instead of 16-byte pieces a further 22 % faster, profiles/row_moves_timing.txt).
 #define AG_ATTRP_WAVES 16
 #define AG_ATTRP_MAX_SLOTS 9         // 9 x 16 KiB of coefficients in LDS
 template <int MODE>
@@ -836,7 +853,9 @@ __global__ void __launch_bounds__(64 * AG_ATTRP_WAVES, AG_ATTRP_WAVES / 4) k_edg
         for (int ot = 0; ot < 8; ++ot) ag_block_mma_part<MODE, false>(y[ot], ph[0], w[ot], part);
       }
     }
-    if (valid && !hard) ag_store_row<8, 0>(y, a.out_rows + (size_t)e * 128, q);
+    // rows go out through the piece layout (common.hpp: coalesced row moves): four adjacent lanes write 64 contiguous bytes
+    const bool ok = ag_piece_row_value(valid && !hard, lane) != 0;
+    ag_store_row_pieces<8, 0>(y, a.out_rows + (size_t)(tile * AG_TW + (lane >> 2)) * 128, ok, lane);
   }
   // flagged tiles of the launch: one atomic per workgroup (a count of integers: the order does not matter)
   if (lane0 == 0 && my_flagged) atomicAdd(&wg_flagged, my_flagged);
@@ -907,21 +926,29 @@ __global__ void __launch_bounds__(64 * AG_PERSIST_WAVES, 4) k_pair_head_poly(Hea
     f32x4 y1[8];
     ag_init_vec<8>(y1, a.hp.b1, q);
     {
-      const float* hs = a.node_h + (size_t)s * 128;
-      const float* ht = a.node_h + (size_t)t * 128;
+      // h rows in the piece layout (common.hpp: coalesced row moves): the lane reads the rows of tile row lane >> 2, the
+      // product is formed there and only the product is permuted into the operand layout
+      const float* hs = a.node_h + (size_t)ag_piece_row_value(s, lane) * 128;
+      const float* ht = a.node_h + (size_t)ag_piece_row_value(t, lane) * 128;
+      const int to_op = ag_to_operand_addr(lane);
       AgIn<MODE> sl[2];
-      auto load_slice = [&](AgIn<MODE>& dst, int k) {
-        const f32x4 p0 = ag_ld4(hs + 32 * k + 4 * q) * ag_ld4(ht + 32 * k + 4 * q);
-        const f32x4 p1 = ag_ld4(hs + 32 * k + 16 + 4 * q) * ag_ld4(ht + 32 * k + 16 + 4 * q);
-        ag_cvt(p0, p1, dst);
+      f32x4 raw[4];
+      auto fetch = [&](f32x4 (&r)[4], int k) {
+        ag_load_slice_pieces(r[0], r[1], hs, k, lane);
+        ag_load_slice_pieces(r[2], r[3], ht, k, lane);
       };
-      load_slice(sl[0], 0);
+      auto finish = [&](AgIn<MODE>& dst, const f32x4 (&r)[4]) {
+        ag_cvt(ag_permute4(r[0] * r[2], to_op), ag_permute4(r[1] * r[3], to_op), dst);
+      };
+      fetch(raw, 0);
+      finish(sl[0], raw);
       const lds_u32x4* lw1_l = ag_lds_base(lw1, lane);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        if (k + 1 < 4) load_slice(sl[(k + 1) & 1], k + 1);
+        if (k + 1 < 4) fetch(raw, k + 1);       // one slice ahead: the loads fly during slice k's MFMAs
         if (k & 1) ag_dense_lds<MODE, false, true, 1, 8, 1, 0>(sl, y1, lw1_l + (k * 8) * 128, 0);
         else ag_dense_lds<MODE, false, true, 1, 8, 0, 0>(sl, y1, lw1_l + (k * 8) * 128, 0);
+        if (k + 1 < 4) finish(sl[(k + 1) & 1], raw);
       }
       AgIn<MODE> ph[NKT];
       ag_poly_features<MODE, NKT>(d, a.two_over_rc, q, ph);

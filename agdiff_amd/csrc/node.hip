@@ -110,6 +110,13 @@ __global__ void __launch_bounds__(LDSW ? 1024 : 256, LDSW ? 1 : 2) k_schnet_node
   const int64_t node = tile * AG_TW + (lane & 15);
   const bool valid = active && node < a.n;
   const int64_t nd = valid ? node : 0;
+  // LDSW, split fp16: h and xs rows move through the piece layout (common.hpp: coalesced row moves), the lane on tile row
+  // lane >> 2.  (Measured on 196 k atoms, profiles/row_moves_timing.txt: -4 % in split fp16; nothing in split bf16, +3 % in exact
+  // fp32, where the kernel spills: those two keep the operand-layout rows.)
+  constexpr bool PIECES = LDSW && MODE == AG_H3;
+  const int64_t nr = tile * AG_TW + (lane >> 2);
+  const bool okr = active && nr < a.n;
+  const int64_t ndr = okr ? nr : 0;
 
   f32x4 hv[8];
   if (!a.finish) {
@@ -206,7 +213,8 @@ __global__ void __launch_bounds__(LDSW ? 1024 : 256, LDSW ? 1 : 2) k_schnet_node
         ag_cvt_tiles<MODE, 1, 0>(s1, sb);
         AG_NODE_DENSE(false, 1, 8, 0, 0, sb, s2, a.prev.scale2_pk, 4);
       }
-      ag_load_row<8, 0>(hv, a.h_in + (size_t)nd * 128, q);
+      if constexpr (PIECES) ag_load_row_pieces<8, 0>(hv, a.h_in + (size_t)ndr * 128, lane);
+      else ag_load_row<8, 0>(hv, a.h_in + (size_t)nd * 128, q);
 #pragma unroll
       for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -215,7 +223,8 @@ __global__ void __launch_bounds__(LDSW ? 1024 : 256, LDSW ? 1 : 2) k_schnet_node
   }
   if (!active) return;                     // no barrier below this point
   ag_report_range<MODE>(ag_absmax<MODE, 8>(hv, 0.0f), a.range_rows, nd, valid, 255.0f);       // (the node state: the heads multiply two of them)
-  if (valid) ag_store_row<8, 0>(hv, a.h + (size_t)node * 128, q);
+  if constexpr (PIECES) ag_store_row_pieces<8, 0>(hv, a.h + (size_t)nr * 128, okr, lane);
+  else if (valid) ag_store_row<8, 0>(hv, a.h + (size_t)node * 128, q);
   if (a.prep) {
     f32x4 xo[12];
     ag_init_vec<12>(xo, a.next.lin1_b, q);
@@ -226,7 +235,8 @@ __global__ void __launch_bounds__(LDSW ? 1024 : 256, LDSW ? 1 : 2) k_schnet_node
     }
     AG_FOR_TILE(xo, 12, ag_lrelu(v));
     ag_report_range<MODE>(ag_absmax<MODE, 12>(xo, 0.0f), a.range_rows, nd, valid, 60000.0f);
-    if (valid) ag_store_row<12, 0>(xo, a.xs + (size_t)node * 192, q);
+    if constexpr (PIECES) ag_store_row_pieces<12, 0>(xo, a.xs + (size_t)nr * 192, okr, lane);
+    else if (valid) ag_store_row<12, 0>(xo, a.xs + (size_t)node * 192, q);
   }
 }
 
@@ -583,10 +593,13 @@ __global__ void __launch_bounds__(1024, 1) k_gin_layer_persistent(GinArgs a) {
     const int64_t node = tile * AG_TW + (lane & 15);
     const bool valid = node < a.n;
     const int64_t nd = valid ? node : 0;
-    const float* hin_self = a.emb ? a.emb + (size_t)a.atom_type[nd] * 128 : a.h_in + (size_t)nd * 128;
+    // rows move through the piece layout (common.hpp: coalesced row moves): the lane reads and writes tile row lane >> 2
+    const int64_t nr = tile * AG_TW + (lane >> 2);
+    const bool okr = nr < a.n;
+    const int64_t ndr = okr ? nr : 0;
     f32x4 m[8], hself[8];
-    ag_load_row<8, 0>(m, a.h_out + (size_t)nd * 128, q);
-    ag_load_row<8, 0>(hself, hin_self, q);
+    ag_load_row_pieces<8, 0>(m, a.h_out + (size_t)ndr * 128, lane);
+    ag_load_row_pieces<8, 0>(hself, a.emb ? a.emb + (size_t)a.atom_type[ndr] * 128 : a.h_in + (size_t)ndr * 128, lane);
     f32x4 y1[8];
     ag_init_vec<8>(y1, a.gp.b1, q);
     {
@@ -606,7 +619,7 @@ __global__ void __launch_bounds__(1024, 1) k_gin_layer_persistent(GinArgs a) {
 #pragma unroll
     for (int t = 0; t < 8; ++t) m[t] += hself[t];
     ag_report_range<MODE>(ag_absmax<MODE, 8>(m, 0.0f), a.range_rows, nd, valid, 255.0f);
-    if (valid) ag_store_row<8, 0>(m, a.h_out + (size_t)node * 128, q);
+    ag_store_row_pieces<8, 0>(m, a.h_out + (size_t)nr * 128, okr, lane);
   }
 }
 
