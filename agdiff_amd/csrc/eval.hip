@@ -608,6 +608,68 @@ __global__ void __launch_bounds__(64) k_mirror_conformers(float* __restrict__ po
   }
 }
 
+// E/Z of double bonds: one wave per conformer, which walks the D tagged bonds in row order.  Every lane computes
+// n1 . n2 of the quad (a, i, j, e) with k_torsion_angles' arithmetic (fp64 from the fp32 positions: the same loads in every lane, so
+// the decision is wave-uniform): parity + 1 (trans) when n1 . n2 < 0, - 1 (cis) when > 0, 0 when a normal is zero or a coordinate
+// is not finite; state = parity against the target's sign, 0 for target 0, written from the positions as they are when the bond's
+// turn comes.  A wrong bond with a side row is flipped: the lanes stride over the row and turn each listed atom by 180 degrees
+// about the axis through p_i along u = (p_j - p_i) / |p_j - p_i|, p' = 2 (p_i + u (u . (p - p_i))) - p in fp64, rounded to fp32
+// once.  Atoms i and j lie on the axis and are skipped, so they stay bit for bit; so does a listed atom with a coordinate that is
+// not finite or an index outside [0, n).  pos is read AND written through one pointer (neither const nor __restrict__): within
+// one bond every coordinate is read and written by the same lane, the loads of the quad come before the stores in the wave's
+// program order, and a workgroup barrier after a rotation (wave-uniform: state is) makes it visible to the next bond's loads.
+// The workgroup is ONE wave: with more, a second barrier between a bond's quad loads and its stores would be needed.
+// A conformer without a wrong bond that has a side row is not written at all.
+__global__ void __launch_bounds__(64) k_flip_double_bonds(float* pos, const int32_t* __restrict__ quads, const int8_t* __restrict__ target,
+                                                          const int32_t* __restrict__ side_ptr, const int32_t* __restrict__ side_idx,
+                                                          int n, int D, int8_t* __restrict__ state, int32_t* __restrict__ flipped) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  float* p = pos + (size_t)g * n * 3;
+  int count = 0;
+  for (int c = 0; c < D; ++c) {
+    const int a = quads[4 * c], u = quads[4 * c + 1], v = quads[4 * c + 2], b = quads[4 * c + 3];
+    int parity = 0;
+    double ux = 0.0, uy = 0.0, uz = 0.0, b2x = 0.0, b2y = 0.0, b2z = 0.0;
+    if (ag_atoms_in_range(n, a, u, v, b)) {
+      const double ax = p[3 * a], ay = p[3 * a + 1], az = p[3 * a + 2];
+      ux = p[3 * u]; uy = p[3 * u + 1]; uz = p[3 * u + 2];
+      const double vx = p[3 * v], vy = p[3 * v + 1], vz = p[3 * v + 2];
+      const double bx = p[3 * b], by = p[3 * b + 1], bz = p[3 * b + 2];
+      const double b1x = ux - ax, b1y = uy - ay, b1z = uz - az;
+      b2x = vx - ux; b2y = vy - uy; b2z = vz - uz;
+      const double b3x = bx - vx, b3y = by - vy, b3z = bz - vz;
+      const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
+      const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
+      const double n1sq = n1x * n1x + n1y * n1y + n1z * n1z, n2sq = n2x * n2x + n2y * n2y + n2z * n2z;
+      const double x = n1x * n2x + n1y * n2y + n1z * n2z;                    // |n1| |n2| cos(phi): phi = 0 cis, pi trans
+      const bool finite = ag_finite(ax) && ag_finite(ay) && ag_finite(az) && ag_finite(ux) && ag_finite(uy) && ag_finite(uz) &&
+                          ag_finite(vx) && ag_finite(vy) && ag_finite(vz) && ag_finite(bx) && ag_finite(by) && ag_finite(bz);
+      if (finite && n1sq > 0.0 && n2sq > 0.0) parity = x < 0.0 ? 1 : (x > 0.0 ? -1 : 0);
+    }
+    const int want = target[c];
+    const int st = (want == 0 || parity == 0) ? 0 : (parity == (want > 0 ? 1 : -1) ? 1 : -1);
+    if (lane == 0) state[(size_t)g * D + c] = (int8_t)st;
+    const int s0 = side_ptr[c], s1 = side_ptr[c + 1];
+    if (st < 0 && s0 >= 0 && s1 > s0 && side_idx) {                                    // (wave-uniform; n1sq > 0 here, so |b2| > 0)
+      const double inv = 1.0 / sqrt(b2x * b2x + b2y * b2y + b2z * b2z);
+      const double ex = b2x * inv, ey = b2y * inv, ez = b2z * inv;
+      for (int k = s0 + lane; k < s1; k += 64) {
+        const int m = side_idx[k];
+        if (m == u || m == v || !ag_atoms_in_range(n, m)) continue;
+        const double px = p[3 * m], py = p[3 * m + 1], pz = p[3 * m + 2];
+        if (!(ag_finite(px) && ag_finite(py) && ag_finite(pz))) continue;
+        const double t = ex * (px - ux) + ey * (py - uy) + ez * (pz - uz);
+        p[3 * m] = (float)(2.0 * (ux + ex * t) - px);
+        p[3 * m + 1] = (float)(2.0 * (uy + ey * t) - py);
+        p[3 * m + 2] = (float)(2.0 * (uz + ez * t) - pz);
+      }
+      ++count;
+      __syncthreads();
+    }
+  }
+  if (flipped && lane == 0) flipped[g] = count;
+}
+
 // ---- torsion fingerprint deviation: RMSD grows with the molecule and mixes ring breathing with rotamer changes; the dihedrals of
 // the rotatable bonds are what defines a conformer, so the matrix, the threshold bits and the mirror value exist over them too ----
 
@@ -1556,6 +1618,17 @@ extern "C" int agdiff_mirror_conformers(float* pos, const int32_t* flags, int32_
   if (!pos || !flags || G < 0 || n <= 0) return AGDIFF_ERR_ARG;
   if (G == 0) return AGDIFF_OK;
   k_mirror_conformers<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, flags, n);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_flip_double_bonds(float* pos, const int32_t* quads, const int8_t* target, const int32_t* side_ptr,
+                                        const int32_t* side_idx, int32_t G, int32_t n, int32_t D, int8_t* state, int32_t* flipped,
+                                        void* stream) {
+  if (G < 0 || n <= 0 || D < 0) return AGDIFF_ERR_ARG;
+  if (G == 0 || D == 0) return AGDIFF_OK;
+  if (!pos || !quads || !target || !side_ptr || !state) return AGDIFF_ERR_ARG;
+  k_flip_double_bonds<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, quads, target, side_ptr, side_idx, n, D, state, flipped);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

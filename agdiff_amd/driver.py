@@ -12,7 +12,7 @@ Input .npz (see `save_testset`): for molecule i: `atom_type_i` [n], `edge_index_
 `num_refs_i` scalar, `name_i` string.  Output: `samples_<first>_<last>.npz` per batch (named by the molecule
 indices it holds) with `pos_gen_<i>` [num_samples, n, 3] (+ `traj_<i>` [steps, num_samples, n, 3] with
 --save-traj; + `kept_<i>` [K] and `cluster_<i>` [num_samples] with --prune-rms T: the conformers that differ by more than T; + `hand_<i>` [num_samples] with --fix-handedness, which needs
-`stereo_<i>` in the test set; + `valid_<i>`, `bond_dev_<i>` and `clash_<i>` [num_samples] with --check-geometry; + `rmsd_traj_<i>` [steps, num_samples] with --track-rmsd, which needs `pos_target_<i>` in the test set: every
+`stereo_<i>` in the test set; + `ez_state_<i>` [num_samples, D] with --fix-double-bonds, which needs `ez_quads_<i>` and `ez_<i>` in the test set; + `valid_<i>`, `bond_dev_<i>` and `clash_<i>` [num_samples] with --check-geometry; + `rmsd_traj_<i>` [steps, num_samples] with --track-rmsd, which needs `pos_target_<i>` in the test set: every
 conformer's heavy-atom RMSD to that target after every step, + `rmsd_mirror_traj_<i>` with --track-rmsd-mirror; + `core_rmsd_<i>`
 [num_samples] with --hold-core for the molecules with `core_pos_<i>` / `core_mask_<i>` in the test set) and the merged
 `samples_all.npz`, written by rank 0 after a barrier.
@@ -42,7 +42,8 @@ def num_confs(spec):
 
 def save_testset(path, molecules):
     """molecules: list of dicts with atom_type, edge_index, edge_type, num_refs, name; optionally stereo (int8 [n]: the target
-    parity at the stereocentres, 0 elsewhere -- agdiff_amd.stereo), saved as `stereo_<i>` when present, and pos_target (float32
+    parity at the stereocentres, 0 elsewhere -- agdiff_amd.stereo), saved as `stereo_<i>` when present, ez_quads (int32 [D, 4]) with ez
+    (int8 [D]: the stereogenic double bonds and their target parity -- agdiff_amd.ezbonds), saved as `ez_quads_<i>` and `ez_<i>`, and pos_target (float32
     [n, 3]: the structure --track-rmsd follows every conformer's RMSD to -- agdiff_amd.trajectory), saved as `pos_target_<i>`, and
     core_pos (float32 [n, 3]) with core_mask ([n], non-zero = the atom belongs to the core: the template --hold-core keeps those
     atoms on -- agdiff_amd.core; rows of core_pos outside the mask are not read), saved as `core_pos_<i>` and `core_mask_<i>` (uint8)."""
@@ -55,6 +56,9 @@ def save_testset(path, molecules):
         out["name_%d" % i] = np.str_(m.get("name", "mol%d" % i))
         if m.get("stereo") is not None:
             out["stereo_%d" % i] = np.asarray(m["stereo"], dtype=np.int8)
+        if m.get("ez_quads") is not None and m.get("ez") is not None:
+            out["ez_quads_%d" % i] = np.asarray(m["ez_quads"], dtype=np.int32).reshape(-1, 4)
+            out["ez_%d" % i] = np.asarray(m["ez"], dtype=np.int8).reshape(-1)
         if m.get("pos_target") is not None:
             n = np.asarray(m["atom_type"]).reshape(-1).shape[0]
             target = np.asarray(m["pos_target"], dtype=np.float32)
@@ -83,6 +87,8 @@ def load_testset(path):
                          name=str(z["name_%d" % i]), index=i))
         if "stereo_%d" % i in z.files:
             mols[-1]["stereo"] = z["stereo_%d" % i]
+        if "ez_quads_%d" % i in z.files and "ez_%d" % i in z.files:
+            mols[-1]["ez_quads"], mols[-1]["ez"] = z["ez_quads_%d" % i], z["ez_%d" % i]
         if "pos_target_%d" % i in z.files:
             mols[-1]["pos_target"] = z["pos_target_%d" % i]
         if "core_pos_%d" % i in z.files and "core_mask_%d" % i in z.files:
@@ -520,7 +526,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
             rank=0, world=1, shard=False, log=print, noise="default", seed=2021, prune_rms=None,
             fix_handedness=False, prune_tfd=None, track_rmsd=False, track_rmsd_mirror=False, repair_geometry=False,
             check_planarity=False, repair_planarity=False, hold_core=False, core_weight=1.0, core_start_sigma=float("inf"),
-            check_geometry=False):
+            fix_double_bonds=False, check_geometry=False):
     """Plan, sample and save (the loop of scripts/test.py:128-181 over packed batches).  Returns the merged result
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
@@ -537,6 +543,14 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     are inverted through their centroid (agdiff_amd.stereo.fix_handedness on the GPU) -- before the prune, which then compares
     like with like.  `pos_gen_<i>` holds the mirrored conformers, `hand_<i>` int8 [G] the verdict before the fix: -1 was mirrored,
     0 (a diastereomer or a flat centre) is left as sampled, +1 was right.
+    fix_double_bonds=True: the bond types say "double", not E or Z, so every conformer's tagged double bonds are read against the
+    molecule's `ez_quads` / `ez` tags (load_testset: `ez_quads_<i>`, `ez_<i>`; a molecule without them is an error) and the wrong
+    ones are turned over, one side of the bond by 180 degrees about it (agdiff_amd.ezbonds.fix_double_bonds on the GPU; DESIGN.md
+    4.17) -- after the core frame and the handedness fix, and BEFORE the repairs, the checks and the prune: the rotation keeps
+    every distance within each side but can bring the two sides into contact, which the repair then sees.  With hold_core the core
+    atoms never move: the other side turns, and a bond with core atoms on both sides is left as sampled.  `pos_gen_<i>` holds the
+    flipped conformers, `ez_state_<i>` int8 [G, D] each bond's state before the fix: +1 right, -1 wrong (flipped, unless it is a
+    ring bond or held on both sides), 0 undecided or untagged.
     check_geometry=True: every saved molecule also gets `valid_<i>` int8 [G], `bond_dev_<i>` float32 [G] (the worst violation of a
     bond-length bound in Angstrom) and `clash_<i>` float32 [G] (the smallest distance between atoms more than three bonds apart as
     a fraction of their van der Waals sum) -- agdiff_amd.validity.check_geometry with the table bounds, after the handedness fix
@@ -557,7 +571,8 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     repair_planarity=True: repair_geometry's step with planes -- one launch of agdiff_amd.planarity.repair_planarity with the table
     bounds and its defaults at the same place: the conformers check_planarity calls bent are flattened (every atom of an aromatic
     ring or of a double bond and its neighbours to within 0.10 Angstrom of the group's best plane) while the bond lengths and
-    contacts are held or repaired as repair_geometry does; still NOT MMFF, and E or Z is not chosen.  A superset of repair_geometry:
+    contacts are held or repaired as repair_geometry does; still NOT MMFF, and E or Z is not chosen (unless fix_double_bonds ran
+    first).  A superset of repair_geometry:
     giving both switches equals giving this one.  The same keys, `repair_status_<i>` (0: valid AND flat as sampled) and
     `repair_moved_<i>`; both checks and the prune then describe the repaired conformers.
     track_rmsd=True: every saved molecule also gets `rmsd_traj_<i>` float32 [steps, G]: each conformer's heavy-atom RMSD to the
@@ -610,6 +625,17 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
         if missing:
             raise ValueError("fix_handedness needs `stereo_<i>` in the test set (python -m agdiff_amd.stereo adds it); missing for "
                              "%d molecules: %s" % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
+    if fix_double_bonds:
+        missing = [m["name"] for m in mols if m.get("ez_quads") is None or m.get("ez") is None]
+        if missing:
+            raise ValueError("fix_double_bonds needs `ez_quads_<i>` and `ez_<i>` in the test set (python -m agdiff_amd.ezbonds adds them); "
+                             "missing for %d molecules: %s" % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
+        from .ezbonds import ez_table
+        for m in mols:
+            try:
+                ez_table(m)
+            except ValueError as e:
+                raise ValueError("fix_double_bonds, molecule %s: %s" % (m["name"], e))
     counter_seed = int(seed) if noise == "counter" else None
     import torch.distributed as dist
     os.makedirs(out_dir, exist_ok=True)
@@ -669,7 +695,7 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
         return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
                                 world, counter_seed, prune_rms, fix_handedness, prune_tfd,
                                 ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_planarity,
-                                repair_planarity, hold, check_geometry)
+                                repair_planarity, hold, fix_double_bonds, check_geometry)
     finally:
         if worker is not None:
             worker.close()
@@ -679,9 +705,10 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
 
 def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
                      counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, repair_geometry=False,
-                     check_planarity=False, repair_planarity=False, hold=None, check_geometry=False):
+                     check_planarity=False, repair_planarity=False, hold=None, fix_double_bonds=False, check_geometry=False):
     import torch.distributed as dist
     mirrored = undecided = checked = invalid = repaired = stuck = seen = judged = bent = 0
+    ez_flipped = ez_left = ez_open = ez_seen = 0
     for pos_in_mine, bidx in enumerate(mine):
         bmols = batches[bidx]
         # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until here,
@@ -742,6 +769,20 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
                 out["hand_%d" % m["index"]] = hand
                 mirrored += int((hand < 0).sum())
                 undecided += int((hand == 0).sum())
+            if fix_double_bonds:
+                import torch
+                from .ezbonds import double_bond_verdict, ez_table, fix_double_bonds as flip
+                item = dict(atom_type=m["atom_type"], edge_index=m["edge_index"], edge_type=m["edge_type"], ez_quads=m["ez_quads"], ez=m["ez"])
+                on_gpu = torch.from_numpy(np.ascontiguousarray(out["pos_gen_%d" % m["index"]], dtype=np.float32)).to(device)
+                frozen = (np.asarray(m["core_mask"]).reshape(-1) != 0) if (hold is not None and _has_core(m)) else None
+                state = flip(item, on_gpu, frozen=frozen).cpu().numpy().astype(np.int8)
+                after = double_bond_verdict(on_gpu, *ez_table(item)).cpu().numpy()
+                out["pos_gen_%d" % m["index"]] = on_gpu.cpu().numpy()
+                out["ez_state_%d" % m["index"]] = state
+                ez_seen += int(state.shape[0])
+                ez_flipped += int(((state < 0) & (after > 0)).any(axis=1).sum())
+                ez_left += int((after < 0).sum())
+                ez_open += int(((state == 0) & (np.asarray(m["ez"]).reshape(1, -1) != 0)).sum())
             if repair_geometry or repair_planarity:
                 if repair_planarity:                   # (holds the bonds too: the distance repair is part of it)
                     from .planarity import repair_planarity as repair
@@ -791,6 +832,9 @@ def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, dev
     if fix_handedness and (rank == 0 or mirrored or undecided):       # (the ranks that wrote files)
         log("rank %d: %d conformers were mirror images and were inverted; %d match neither hand (verdict 0) and stay as sampled"
             % (rank, mirrored, undecided))
+    if fix_double_bonds and (rank == 0 or ez_seen):
+        log("rank %d: %d of %d conformers had a double bond of the wrong E/Z parity flipped; %d bonds stay wrong (in a ring, or held on "
+            "both sides) and %d tagged bonds are undecided (ez_state_<i> = 0)" % (rank, ez_flipped, ez_seen, ez_left, ez_open))
     if (repair_geometry or repair_planarity) and (rank == 0 or seen):
         log("rank %d: %d of %d conformers were repaired (%s); %d more were not within the iteration limit (repair_status_<i> = 2)"
             % (rank, repaired, seen, "flattened and moved into their distance bounds" if repair_planarity else
@@ -846,6 +890,12 @@ def main(argv=None):
                     help="invert the conformers that came out as the mirror image (the sampler cannot tell the hands apart): needs "
                          "stereo_<i> in the test set (python -m agdiff_amd.stereo); pos_gen_<i> then holds the mirrored conformers and "
                          "hand_<i> the verdict before the fix (-1 mirrored, 0 neither hand: left as sampled, +1 right)")
+    ap.add_argument("--fix-double-bonds", action="store_true",
+                    help="turn over the double bonds that came out as the wrong E/Z isomer (the bond types do not say which one): needs "
+                         "ez_quads_<i> and ez_<i> in the test set (python -m agdiff_amd.ezbonds); one side of each wrong bond is rotated by "
+                         "180 degrees about it, after --fix-handedness and before the repairs and checks; pos_gen_<i> then holds the "
+                         "flipped conformers and ez_state_<i> [num_samples, D] each bond's state before the fix (+1 right, -1 wrong, 0 "
+                         "undecided or untagged); ring bonds are judged, never flipped; with --hold-core the core atoms stay")
     ap.add_argument("--check-geometry", action="store_true",
                     help="also save, per molecule, valid_<i>, bond_dev_<i> and clash_<i>: which conformers pass the bond-length bounds "
                          "and the steric clash scan of agdiff_amd.validity (pos_gen_<i> still holds them all); with --prune-rms / "
@@ -866,7 +916,7 @@ def main(argv=None):
                          "contacts are held, so a conformer that is bent but otherwise fine comes back usable instead of being dropped "
                          "by --check-planarity; includes --repair-geometry (giving both equals giving this one); the same keys "
                          "repair_status_<i> and repair_moved_<i>; E or Z is not chosen: a double bond twisted past 90 degrees flattens "
-                         "into the other isomer")
+                         "into the other isomer, unless --fix-double-bonds ran first")
     ap.add_argument("--track-rmsd", action="store_true",
                     help="also save, per molecule, rmsd_traj_<i> [steps, num_samples]: every conformer's heavy-atom RMSD to the "
                          "molecule's pos_target_<i> of the test set after every denoising step, computed while the run samples "
@@ -930,7 +980,7 @@ def main(argv=None):
             seed=args.seed, prune_rms=args.prune_rms, fix_handedness=args.fix_handedness, prune_tfd=args.prune_tfd,
             check_geometry=args.check_geometry, check_planarity=args.check_planarity, repair_geometry=args.repair_geometry, track_rmsd=args.track_rmsd, track_rmsd_mirror=args.track_rmsd_mirror,
             repair_planarity=args.repair_planarity, hold_core=args.hold_core, core_weight=args.core_weight,
-            core_start_sigma=args.core_start_sigma)
+            core_start_sigma=args.core_start_sigma, fix_double_bonds=args.fix_double_bonds)
     if own_pg:
         dist.destroy_process_group()
 

@@ -22,6 +22,7 @@ from . import _lib
 from .evaluation import selection_of, selection_on_device
 from .molecule import as_host, check_threshold, heavy_atoms, num_atoms, sampled_items
 from .planarity import check_planarity
+from .ezbonds import fix_double_bonds as _fix_double_bonds
 from .stereo import fix_handedness as _fix_handedness
 from .validity import check_geometry
 
@@ -114,7 +115,8 @@ def _valid_mask(valid, G):
     return v
 
 
-def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False, metric="rmsd", valid=None):
+def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False, metric="rmsd", fix_double_bonds=False,
+                     valid=None):
     """RDKit's pruneRmsThresh rule over the item's generated conformers, in their order: a conformer is kept iff its best RMSD
     to every conformer kept before it is above `threshold`; a dropped one belongs to the first kept conformer within the
     threshold.  metric="tfd": the same leader walk with the torsion fingerprint deviation (agdiff_amd.torsions; in [0, 1], the item
@@ -130,6 +132,11 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     families that can never superpose; the dict also gets
         hand   int32 [G]  the verdict before the fix: -1 was mirrored, 0 matches neither hand and is left as it is, +1 was right
     and `pos` holds the mirrored coordinates.
+    fix_double_bonds=True (the item carries `ez_quads`, `ez` and its bonds): after the handedness fix, the tagged double bonds of the
+    wrong E/Z parity are turned over (agdiff_amd.ezbonds.fix_double_bonds), so that the kept set is not spent on the wrong isomer;
+    the dict also gets
+        ez_state int8 [G, D]  each bond's state before the fix: +1 right, -1 wrong, 0 undecided or untagged
+    and `pos` holds the flipped coordinates.
     valid (bool [G], e.g. agdiff_amd.validity.check_geometry(item)["valid"]): the walk runs over the valid conformers only, in their
     order -- a broken conformer is far from everything, so without the mask the rule keeps every one of them.  `kept` still indexes
     the item's conformers, `leader` is -1 for an invalid one, and with no valid conformer `kept` is empty and nothing is aligned.
@@ -149,6 +156,12 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     if fix_handedness:
         gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
         hand = _fix_handedness(item, gen)
+    ez_state = None
+    if fix_double_bonds:
+        gen = gen.to(device).contiguous()
+        if not fix_handedness:
+            gen = gen.clone()                            # (the caller's tensor is never written)
+        ez_state = _fix_double_bonds(item, gen)
     sel = None
     if mask is not None:                                 # compacted on the device; the kernels below see the valid ones only
         gen = gen.to(device).contiguous()
@@ -160,6 +173,8 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
                    "count": torch.empty(0, dtype=torch.int32, device=gen.device), "pos": gen[:0]}
             if hand is not None:
                 res["hand"] = hand
+            if ez_state is not None:
+                res["ez_state"] = ez_state
             return res
         gen = gen[sel].contiguous()
     if metric == "tfd":
@@ -182,6 +197,8 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
         res["kept"], res["leader"] = sel[kept].to(torch.int32), full
     if hand is not None:
         res["hand"] = hand
+    if ez_state is not None:
+        res["ez_state"] = ez_state
     return res
 
 
@@ -190,7 +207,9 @@ def main(argv=None):
     Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
     symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
     (+ `name_<i>`).  Exactly one of --prune-rms / --prune-tfd T (the torsion fingerprint deviation, in [0, 1]).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
-    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix.  --drop-invalid: the conformers that fail
+    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix.  --fix-double-bonds: then the double bonds of
+    the wrong E/Z parity are turned over (the test set must carry `ez_quads_<i>` / `ez_<i>`: python -m agdiff_amd.ezbonds); also
+    writes `ez_state_<i>` [G, D], each bond's state before the fix.  --drop-invalid: the conformers that fail
     agdiff_amd.validity.check_geometry (table bounds, default clash ratio) take no part in the walk: `cluster_<i>` is -1 for them;
     also writes `valid_<i>` int8 [G].  --drop-bent: the same for the conformers that fail agdiff_amd.planarity.check_planarity (an
     aromatic ring or a double bond out of plane, default threshold); also writes `flat_<i>` int8 [G]."""
@@ -204,6 +223,11 @@ def main(argv=None):
                      help="torsion fingerprint deviation threshold in [0, 1] (agdiff_amd.torsions) instead of an RMSD")
     ap.add_argument("--align", action="store_true", help="superpose the kept conformers on the first of them")
     ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
+    ap.add_argument("--fix-double-bonds", action="store_true",
+                    help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
+                         "in --testset: python -m agdiff_amd.ezbonds); also writes ez_state_<i> [G, D].  --drop-invalid and --drop-bent "
+                         "judge the conformers as sampled, before the flip, which can bring the two sides of a bond into contact: the "
+                         "driver's order (flip, repair, check) is the one to use when that matters")
     ap.add_argument("--drop-invalid", action="store_true",
                     help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the walk")
     ap.add_argument("--drop-bent", action="store_true",
@@ -220,6 +244,11 @@ def main(argv=None):
             if mol.get("stereo") is None:
                 raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
             item["stereo"] = mol["stereo"]
+        if args.fix_double_bonds:
+            if mol.get("ez_quads") is None or mol.get("ez") is None:
+                raise ValueError("--fix-double-bonds: %s has no ez_quads_%d / ez_%d (python -m agdiff_amd.ezbonds adds them)"
+                                 % (args.testset, i, i))
+            item["ez_quads"], item["ez"] = mol["ez_quads"], mol["ez"]
         valid = None
         if args.drop_invalid:
             valid = check_geometry(item, device=args.device)["valid"]       # (mirroring keeps every distance: before or after the fix)
@@ -229,7 +258,7 @@ def main(argv=None):
             out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
             valid = flat if valid is None else valid & flat
         res = prune_conformers(item, threshold, align=args.align, device=args.device, fix_handedness=args.fix_handedness,
-                               metric=metric, valid=valid)
+                               metric=metric, valid=valid, fix_double_bonds=args.fix_double_bonds)
         out["pos_%d" % i] = res["pos"].cpu().numpy()
         out["kept_%d" % i] = res["kept"].cpu().numpy()
         out["cluster_%d" % i] = res["leader"].cpu().numpy()
@@ -237,6 +266,8 @@ def main(argv=None):
         out["name_%d" % i] = np.str_(mol["name"])
         if "hand" in res:
             out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
+        if "ez_state" in res:
+            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
         total += int(res["leader"].shape[0])
         left += int(res["kept"].shape[0])
     np.savez_compressed(args.out, **out)

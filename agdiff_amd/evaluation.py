@@ -304,6 +304,30 @@ class CovMatEvaluator(object):
         pass
 
 
+def ez_report(samples_path, tags_path, device="cuda", print_fn=print):
+    """{i: share}: for every molecule i with `pos_gen_<i>` in the samples file and `ez_quads_<i>` + `ez_<i>` (and atom_type_<i>, its
+    bonds) in the tags file -- a test set or a references file -- the share of generated conformers with at least one tagged double
+    bond of the wrong E/Z parity (agdiff_amd.ezbonds.wrong_share: the check only), one printed line each."""
+    from .ezbonds import wrong_share
+    zs, zt = np.load(samples_path), np.load(tags_path)
+    shares = {}
+    for key in sorted((k for k in zt.files if k.startswith("ez_quads_")), key=lambda k: int(k[len("ez_quads_"):])):
+        i = key[len("ez_quads_"):]
+        if "ez_" + i not in zt.files or "pos_gen_" + i not in zs.files:
+            continue
+        item = {"atom_type": zt["atom_type_" + i], "ez_quads": zt[key], "ez": zt["ez_" + i], "pos_gen": zs["pos_gen_" + i]}
+        for k in ("bond_index", "bond_type", "edge_index", "edge_type"):
+            if "%s_%s" % (k, i) in zt.files:
+                item[k] = zt["%s_%s" % (k, i)]
+        if not np.asarray(item["ez"]).any():
+            continue
+        shares[int(i)] = wrong_share(item, device=device)
+        name = str(zt["name_" + i]) if "name_" + i in zt.files else "mol" + i
+        print_fn("%s: %d tagged double bonds, %.4f of %d generated conformers have one with the wrong E/Z parity"
+                 % (name, int((np.asarray(item["ez"]) != 0).sum()), shares[int(i)], np.asarray(item["pos_gen"]).reshape(-1, item["atom_type"].shape[0], 3).shape[0]))
+    return shares
+
+
 def main(argv=None):
     """python -m agdiff_amd.evaluation --samples samples_all.npz --refs refs.npz
     samples: `pos_gen_<i>` [G, n, 3] (agdiff_amd.driver output); refs: `pos_ref_<i>` [R, n, 3], `atom_type_<i>` [n],
@@ -322,10 +346,17 @@ def main(argv=None):
                     help="also print the table computed from min(proper, mirror): what the run would score were handedness free")
     ap.add_argument("--metric", default="rmsd", choices=["rmsd", "tfd"],
                     help="'tfd': COV / MAT over the torsion fingerprint deviation (thresholds 0.01 .. 0.60) instead of the RMSD")
+    ap.add_argument("--ez-report", action="store_true",
+                    help="also print, per molecule with E/Z tags (ez_quads_<i> + ez_<i>: agdiff_amd.ezbonds), the share of generated "
+                         "conformers with a double bond of the wrong parity; the tags and bonds are read from --testset, or from --refs "
+                         "without one; the check only, the COV / MAT numbers do not change")
+    ap.add_argument("--testset", default=None, help="with --ez-report: the test set that carries the tags (default: --refs)")
     args = ap.parse_args(argv)
     items = [item for _, item in reference_items(args.refs, args.samples)]
     res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand, metric=args.metric)(items)
     print_covmat_results(res)
+    if args.ez_report:
+        res.ez_wrong = ez_report(args.samples, args.testset or args.refs)
     if args.either_hand:
         print("\neither hand (every generated conformer scored as the better of itself and its mirror image):")
         print_covmat_results(res.either_hand)

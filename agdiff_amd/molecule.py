@@ -1,5 +1,5 @@
-"""What the modules that run after the sampler (evaluation, ensemble, stereo, torsions, validity, planarity, trajectory, distances) share on
-the host: how an item's fields, atoms and bonds are read, the bonded-neighbour graph, colour refinement, and the item loops of
+"""What the modules that run after the sampler (evaluation, ensemble, stereo, ezbonds, torsions, validity, planarity, trajectory, distances) share on
+the host: how an item's fields, atoms and bonds are read, the bonded-neighbour graph, colour refinement, the bridge search, and the item loops of
 their command lines.  numpy only; the device-side counterparts (`call`, `conformers`, ...) are in _lib.py.
 
 An item is a plain dict (or any object with the same attributes): atom_type [n] atomic numbers, its bonds as bond_index [2, e] +
@@ -71,6 +71,37 @@ def refine_colours(colour, adj):
         if stable:
             break
     return colour
+
+
+def bridges(nbrs):
+    """The bridges (u, v), u < v, of an undirected graph given as sorted neighbour lists: depth-first search with low-links,
+    iterative (a molecule may have thousands of atoms)."""
+    n = len(nbrs)
+    order, low, out, clock = [-1] * n, [0] * n, set(), 0
+    for root in range(n):
+        if order[root] >= 0:
+            continue
+        order[root] = low[root] = clock
+        clock += 1
+        stack = [(root, -1, 0)]
+        while stack:
+            i, parent, k = stack.pop()
+            if k < len(nbrs[i]):
+                stack.append((i, parent, k + 1))
+                j = nbrs[i][k]
+                if j == parent:
+                    continue
+                if order[j] < 0:
+                    order[j] = low[j] = clock
+                    clock += 1
+                    stack.append((j, i, 0))
+                else:
+                    low[i] = min(low[i], order[j])
+            elif parent >= 0:
+                low[parent] = min(low[parent], low[i])
+                if low[i] > order[parent]:
+                    out.add((min(i, parent), max(i, parent)))
+    return out
 
 
 def as_host(x, dtype=None):

@@ -28,7 +28,8 @@ flat_to = 0.10 Angstrom from its group's best plane is moved towards it while th
 onto a plane shortens bonds, so the flattening includes the distance repair), and a conformer that is valid and flat comes back
 bit for bit.  Like the distance repair it is a projection from the topology alone, NOT MMFF: no energies, no torsion terms, no
 electrostatics.  It does not choose E or Z: a double bond twisted past 90 degrees flattens into the other isomer, because nothing
-here knows which one the molecule is.
+here knows which one the molecule is -- unless --fix-double-bonds (agdiff_amd.ezbonds) ran first, which puts every tagged bridge
+double bond on the right side of 90 degrees.
 
     python -m agdiff_amd.planarity --samples out/samples_all.npz --testset test.npz --out planarity.npz [--thresh 0.25] [--per-group]
                                    [--repair flattened.npz [--flat-to 0.10] [--pad 0.02] [--omega 1.0] [--max-iter 200]]
@@ -217,7 +218,8 @@ def relax_planar(pos, grp_ptr, grp_idx, pairs, lo, hi, radius, ex_ptr, ex_idx, t
     planar_deviation at `thresh` has its atoms moved by small steps until every bounded distance and every contact is inside
     relax_bounds' targets and every member of every group is within flat_to of its group's best plane (to within half a pad), or
     max_iter updates are spent.  Not MMFF: no energies, no torsions, no electrostatics; E or Z is not chosen -- a double bond
-    twisted past 90 degrees flattens into the other isomer (include/agdiff_hip.h has the rule).  Returns what
+    twisted past 90 degrees flattens into the other isomer, unless ezbonds.fix_double_bonds (--fix-double-bonds) ran first
+    (include/agdiff_hip.h has the rule).  Returns what
     relax_bounds returns: (pos_out, status int32 [G]: 0 valid and flat as it came and unchanged bit for bit, 1 repaired, 2 not within
     max_iter updates, 3 not finite and unchanged; iters; resid; moved).  All tables are checked here, on the host (check_groups,
     validity.relax_tables; flat_to + pad <= thresh): ValueError before any launch.  More than AGDIFF_RELAX_MAX_ATOMS atoms or

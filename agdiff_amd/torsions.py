@@ -30,7 +30,7 @@ import numpy as np
 from . import _lib
 from .ensemble import bits_pitch
 from .evaluation import selection_of
-from .molecule import as_host, bonded_neighbours, bonds_of, check_threshold, num_atoms, sampled_items
+from .molecule import as_host, bonded_neighbours, bonds_of, bridges, check_threshold, num_atoms, sampled_items
 
 MAX_COLUMNS = _lib.DEFINES["AGDIFF_TFD_MAX_COLUMNS"]
 
@@ -45,35 +45,7 @@ def _heavy_graph(atom_type, bond_index, bond_type):
     return heavy, adj, hadj
 
 
-def _bridges(hadj):
-    """The bridges (u, v), u < v, of an undirected graph given as sorted neighbour lists: depth-first search with low-links,
-    iterative (a molecule may have thousands of atoms)."""
-    n = len(hadj)
-    order, low, out, clock = [-1] * n, [0] * n, set(), 0
-    for root in range(n):
-        if order[root] >= 0:
-            continue
-        order[root] = low[root] = clock
-        clock += 1
-        stack = [(root, -1, 0)]
-        while stack:
-            i, parent, k = stack.pop()
-            if k < len(hadj[i]):
-                stack.append((i, parent, k + 1))
-                j = hadj[i][k]
-                if j == parent:
-                    continue
-                if order[j] < 0:
-                    order[j] = low[j] = clock
-                    clock += 1
-                    stack.append((j, i, 0))
-                else:
-                    low[i] = min(low[i], order[j])
-            elif parent >= 0:
-                low[parent] = min(low[parent], low[i])
-                if low[i] > order[parent]:
-                    out.add((min(i, parent), max(i, parent)))
-    return out
+_bridges = bridges            # (the search lives in molecule.py, which ezbonds.py shares; the name stays for its importers)
 
 
 def _columns(atom_type, bond_index, bond_type):

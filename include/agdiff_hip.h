@@ -821,6 +821,32 @@ int agdiff_chiral_verdict(const float* pos, const int32_t* quads, const int8_t* 
  * flags[g] == 0 are neither read nor written.  pos [G][n][3]. */
 int agdiff_mirror_conformers(float* pos, const int32_t* flags, int32_t G, int32_t n, void* stream);
 
+/* E/Z of double bonds, judged and repaired in place: the bond types the score network sees do not say which isomer a C=C, C=N or
+ * N=N is, and the sampler draws either.  The host finds the stereogenic double bonds and the atoms on one side of each
+ * (agdiff_amd/ezbonds.py).
+ *   pos [G][n][3]             read and written
+ *   quads [D][4] int32        (a, i, j, d): the double bond i - j, a neighbour a of i and a neighbour d of j
+ *   target [D] int8           +1: a and d on opposite sides (trans); -1: on the same side (cis); 0: do not judge
+ *   side_ptr [D + 1], side_idx   CSR: the atoms that turn with one end of bond c, entries in [0, n) (NOT checked against the graph
+ *                             here: the caller does); an empty row: judge, do not flip.  side_idx may be null when every row is empty
+ *   state [G][D] int8         +1 right, -1 wrong, 0 undecided or target 0 -- from the positions as they are when the bond's turn
+ *                             comes (the bonds are walked in row order), that is BEFORE this bond's own flip
+ *   flipped [G] int32 or null the number of flips applied to the conformer (not written when G = 0 or D = 0)
+ * The parity of a bond is read from n1 . n2 = |n1| |n2| cos(phi) of agdiff_torsion_angles' formula (fp64 from the fp32 positions):
+ * +1 when it is negative (|phi| > 90 degrees), -1 when positive, 0 when it or a normal is zero or a coordinate is not finite.  A
+ * quad naming an atom outside [0, n) reads nothing and gives state 0.
+ * A bond with state -1 and a side row is flipped: every listed atom p is turned by 180 degrees about the axis through p_i along
+ * u = (p_j - p_i) / |p_j - p_i|, p' = 2 (p_i + u (u . (p - p_i))) - p in fp64, stored as fp32.  Atoms i and j are skipped when
+ * listed and stay bit for bit, as does a listed atom with a coordinate that is not finite.  A 180 degree rotation of a rigid side
+ * keeps every bond length, every distance within each side and every tetrahedral parity (it is a proper rotation, not a
+ * reflection); it negates cos(phi) of that one bond and leaves the other tagged bonds' dihedrals alone when the bonds are
+ * bridges (the four atoms of any other quad lie on one side of the cut).  It CAN create contacts between the two sides: that is
+ * why the driver runs the flip before the repairs and the checks.  A conformer without a wrong bond that has a side row is not
+ * written at all.  No limit on n or D.  One wave per conformer, a workgroup barrier after each flip; deterministic. */
+int agdiff_flip_double_bonds(float* pos /* [G][n][3], in place */, const int32_t* quads /* [D][4] */, const int8_t* target /* [D] */,
+                             const int32_t* side_ptr /* [D + 1] */, const int32_t* side_idx, int32_t G, int32_t n, int32_t D,
+                             int8_t* state /* [G][D] */, int32_t* flipped /* [G] or NULL: flips applied */, void* stream);
+
 /* ---- torsion fingerprint deviation -----------------------------------------------------------------------------------
  * The second standard metric between conformers next to the RMSD: the mean circular difference of the rotatable bonds'
  * dihedrals, in [0, 1] and independent of the molecule's size (rdkit Chem.TorsionFingerprints.GetTFDBetweenConformers /
@@ -944,7 +970,8 @@ int agdiff_relax_bounds(const float* pos, const int32_t* bd_ptr, const int32_t* 
  * the same launch: a folded aromatic ring, a pyramidal sp2 centre and a twisted double bond are flattened while the bonds are
  * held -- a projection onto a plane shortens them, so this is a superset of agdiff_relax_bounds.  Still NOT MMFF: no energies, no
  * torsion terms, no electrostatics.  It does not choose E or Z either: a double bond twisted past 90 degrees flattens into the
- * other isomer, because nothing here knows which one the molecule is.
+ * other isomer, because nothing here knows which one the molecule is -- unless agdiff_flip_double_bonds (--fix-double-bonds) ran
+ * first: it puts every tagged bridge double bond on the right side of 90 degrees, and the flattening then ends in the tagged isomer.
  *   pos ... ex_idx, G, n, K, clash, pad, omega, max_iter, pos_out ... moved   as agdiff_relax_bounds, the same checks
  *   grp_ptr [P + 1], grp_idx   the planar groups as agdiff_planar_groups takes them, 3 .. AGDIFF_PLANAR_MAX_ATOMS members each, P <=
  *                          AGDIFF_FLATTEN_MAX_GROUPS (else AGDIFF_ERR_LIMIT).  NOT checked here: the caller does (members in [0, n))
