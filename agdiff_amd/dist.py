@@ -130,52 +130,31 @@ def sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=False,
     ranks, the trajectories [steps, N, 3] are gathered to rank 0 only (None elsewhere).  A rank that raises while the
     others sample keeps issuing its collectives, then every rank raises.
     `counter_seed`: as in driver.sample_batch -- every rank draws its share from the stream ids of its graph range, so the
-    sharded job draws what the one-GPU job draws."""
-    from .driver import SAMPLE_STATS, _arithmetic, _check_counter, _counter_kwargs, _sort_results, subset_batch
+    sharded job draws what the one-GPU job draws.  The retry schedule is driver.sample_passes'; every rank takes the same decisions.
+    No `curves` / `core`: a rank's run sees only its own graphs, so the steps that need them refuse shard=True (postprocess.Step.require)."""
+    from .driver import check_counter, run_part, sample_passes
     world, rank = dist.get_world_size(group), dist.get_rank(group)
-    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
-    spans = packed["spans"]
-    n_mol, N = len(spans), packed["atom_type"].shape[0]
-    _check_counter(model, packed, counter_seed)
-    pos_out = torch.full((N, 3), float("nan"))
-    traj_out = None
-    ok = np.zeros(n_mol, dtype=bool)
+    check_counter(model, packed, counter_seed)
     # collectives per pass = steps LangevinRun will take (epsnet.py: len(step_indices) if given, else n_steps): a rank
     # without graphs must issue exactly as many gathers as the ranks that sample
     si = sampler_kwargs.get("step_indices")
     n_steps = len(si) if si is not None else int(sampler_kwargs.get("n_steps", 5000))
-    # passes still to run, as in driver.sample_batch: (molecule slots, clip_local, split-bf16?, attempts counted); every rank
-    # takes the same decisions (the flags they rest on are gathered)
-    passes = [(list(range(n_mol)), None, False, 0)]
-    first = True
-    while passes:
-        todo, clip_local, wide, tries = passes.pop(0)
-        sub = packed if len(todo) == n_mol else subset_batch(packed, todo)
+
+    def run_pass(sub, todo, clip_local, wide, tries, first):
+        nonlocal topology
         mine, (g0, g1), (lo, hi) = shard_of(sub, rank, world)
         gather = StepAllGather(hi - lo, device, group)
         empty, zero = torch.zeros(0, 3, device=device), torch.zeros(1, dtype=torch.int32, device=device)
         err, traj, bad_local, range_local = None, None, np.zeros(0, dtype=bool), []
+        # (`topology`: this rank's range of the whole batch, prepared ahead by driver.prepare_batch: first attempt only)
+        extra = {"topology": topology} if (topology is not None and sub is packed) else {}
+        topology = None
         if mine is not None:
             try:
-                counter = _counter_kwargs(mine, counter_seed, tries)
-                if first and pos_init is not None:
-                    p0 = pos_init[lo:hi].to(device)
-                elif counter:
-                    p0 = model.counter_normals(mine["batch"], counter["stream_ids"], counter_seed, [-1])[0]
-                else:
-                    p0 = torch.randn(hi - lo, 3).to(device)
-                with _arithmetic(model, wide):
-                    # (`topology`: this rank's range of the whole batch, prepared ahead by driver.prepare_batch: first attempt only)
-                    extra = {"topology": topology} if (topology is not None and sub is packed) else {}
-                    topology = None
-                    run = model.begin_sampling(T(mine["atom_type"]), p0, T(mine["bond_index"]), T(mine["bond_type"]),
-                                               T(mine["batch"]), mine["num_graphs"], False, clip_local=clip_local,
-                                               save_traj=save_traj, raise_on_nan=False,
-                                               noise=(noise[:, lo:hi] if (first and noise is not None) else None),
-                                               **extra, **counter, **sampler_kwargs)
-                    run.on_step = lambda k, i, pos: gather(k, i, pos, run.ws.nan_flag)
-                    run.advance(run.remaining())
-                    _, traj = run.finish()
+                run, _, traj = run_part(model, mine, device, sampler_kwargs, counter_seed, tries, wide,
+                                        pos_init[lo:hi] if (first and pos_init is not None) else None,
+                                        hook=lambda run: lambda k, i, pos: gather(k, i, pos, run.ws.nan_flag), clip_local=clip_local,
+                                        save_traj=save_traj, noise=(noise[:, lo:hi] if (first and noise is not None) else None), **extra)
                 bad_local = run.nan_graphs().numpy()
                 range_local = [g0 + int(g) for g in getattr(run, "range_graphs", ())]      # graph ids of `sub`
             except Exception as e:            # (AgdiffLimitError, out of memory, ...): the other ranks are inside the
@@ -196,29 +175,12 @@ def sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=False,
         bad_all = [None] * world
         dist.all_gather_object(bad_all, (bad_local.tolist(), range_local), group=group)
         bad_graph = np.array([b for part, _ in bad_all for b in part], dtype=bool)
-        out_of_range = sorted(g for _, r in bad_all for g in r)   # conformers that left the split-fp16 range, on any rank
-        SAMPLE_STATS["range_trips"] += len(out_of_range)
-        first = False
+        out_of_range = [g for _, r in bad_all for g in r]         # conformers that left the split-fp16 range, on any rank
         if save_traj:                          # [steps, N_r, 3] per rank: to rank 0 only (it writes them)
             trajs = [None] * world if rank == 0 else None
             dist.gather_object(None if traj is None else torch.stack(traj).numpy(), trajs, dst=0, group=group)
-            if rank == 0:
-                traj = torch.from_numpy(np.concatenate([x for x in trajs if x is not None], axis=1))
-                if traj_out is None:
-                    traj_out = torch.full((traj.shape[0], N, 3), float("nan"))
-        nan_failed, range_failed = _sort_results(todo, sub["spans"], spans, bad_graph, out_of_range, wide, ok, pos_out, pos,
-                                                 traj_out if (save_traj and rank == 0) else None, traj if (save_traj and rank == 0) else None)
-        if range_failed:
-            SAMPLE_STATS["bf16x3_retries"] += 1
-            if rank == 0:
-                log("%d conformers left the split-fp16 range: sampling their molecules (%d of %d) again in split-bf16."
-                    % (len(out_of_range), len(range_failed), len(sub["spans"])))
-            passes.append((range_failed, clip_local, True, tries))
-        if nan_failed:
-            if tries + 1 < max_retry:
-                if rank == 0:
-                    log("NaN in %d of %d molecules: retrying those with local clipping." % (len(nan_failed), len(sub["spans"])))
-                passes.append((nan_failed, 20, wide, tries + 1))
-            else:
-                SAMPLE_STATS["dropped"] += len(nan_failed)
-    return pos_out, traj_out, ok
+            traj = torch.from_numpy(np.concatenate([x for x in trajs if x is not None], axis=1)) if rank == 0 else None
+        return pos, (traj if save_traj else None), bad_graph, out_of_range, {}
+
+    ok, got = sample_passes(packed, run_pass, max_retry, log if rank == 0 else (lambda s: None))
+    return got["pos"], got.get("traj"), ok

@@ -202,32 +202,25 @@ def pack_batch(mols, confs_of):
     return out
 
 
-def prepare_batch(model, bmols, confs_of, rank=0, world=1):
+def prepare_batch(model, bmols, confs_of, rank=0, world=1, build=None):
     """(packed batch, its BatchTopology on the host or None) -- for world > 1 the topology of THIS rank's graph range of the
     batch (dist.shard_of), as sample_batch_sharded samples it.  Host work only (no GPU call): run_job calls it for the next
-    batch from a background thread.  None for models without prepare_topology (test stubs) or a rank without graphs."""
+    batch from a background thread.  `build`: by default the model's prepare_topology; None without one (test stubs) or without graphs."""
     packed = pack_batch(bmols, confs_of)
-    if not hasattr(model, "prepare_topology"):
-        return packed, None
+    build = build or getattr(model, "prepare_topology", None)
     part = packed
-    if world > 1:
+    if world > 1 and build is not None:
         from .dist import shard_of
         part = shard_of(packed, rank, world)[0]
-        if part is None:
-            return packed, None
+    if build is None or part is None:
+        return packed, None
     try:
-        return packed, model.prepare_topology(part["atom_type"], part["bond_index"], part["bond_type"], part["batch"], part["num_graphs"],
-                                              extend_order=False, device="cpu")
+        return packed, build(part["atom_type"], part["bond_index"], part["bond_type"], part["batch"], num_graphs=part["num_graphs"],
+                             extend_order=False, device="cpu")
     except Exception:
         # (a batch the topology refuses -- e.g. a molecule beyond the atom limit: the sampler builds it again and raises THERE, where
         # sample_batch_sharded keeps a failing rank's collectives in step with the others)
         return packed, None
-
-
-def _topology_options(model):
-    """What model.prepare_topology needs of the model (plain values: they travel to the worker process)."""
-    return dict(order=int(model.config.edge_order), group_targets=getattr(model, "group_targets", None),
-                radius_column=bool(getattr(model, "tuning", {}).get("group_radius_column", 1)))
 
 
 def _prepare_in_worker(bmols, confs, rank, world, topo_opts):
@@ -235,20 +228,10 @@ def _prepare_in_worker(bmols, confs, rank, world, topo_opts):
     process's interpreter lock -- a background THREAD hid 0.3 s of a batch's 1-4 s of numpy, because every Python-level step of
     the build waits for the launch loop's lock and vice versa.  Host work only: nothing here touches a GPU.  `confs`: conformers
     per molecule of the batch (the callable of scripts/test.py:15-24 does not pickle)."""
+    import functools
     from .topology import BatchTopology
     it = iter(confs)
-    packed = pack_batch(bmols, lambda _num_refs: next(it))
-    part = packed
-    if world > 1:
-        from .dist import shard_of
-        part = shard_of(packed, rank, world)[0]
-        if part is None:
-            return packed, None
-    try:
-        return packed, BatchTopology(part["atom_type"], part["bond_index"], part["bond_type"], part["batch"], num_graphs=part["num_graphs"],
-                                     extend_order=False, device="cpu", **topo_opts)
-    except Exception:
-        return packed, None               # (the sampler builds it again and raises there: prepare_batch)
+    return prepare_batch(None, bmols, lambda _num_refs: next(it), rank, world, build=functools.partial(BatchTopology, **topo_opts))
 
 
 def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_retry=2, log=print, pos_init=None,
@@ -265,17 +248,14 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
     conformer, attempt) alone.  A NaN retry draws with attempt + 1; a split-bf16 re-run of a range-only fault keeps its attempt
     (the same draws in wider arithmetic).
     `curves`: a dict to fill with the tracked RMSD curves (epsnet.LangevinRun: rmsd_target = the batch's `pos_target`, heavy atoms):
-    curves["rmsd"] float32 [steps, num_graphs] and, when it came in with curves["mirror"] true, curves["rmsd_mirror"].  A molecule's
-    columns come from the pass that succeeded; columns of dropped molecules are NaN.
-    `core`: a dict {"weight": w, "start_sigma": s}: the batch's `core_pos` / `core_select` are held while sampling
-    (epsnet.LangevinRun: core_pos, core_select, core_weight, core_start_sigma; agdiff_amd/core.py) in every pass whose molecules
-    include one with a core; it comes back with core["dev"] float32 [num_graphs], the run's `core_dev` of the pass that succeeded
-    (NaN for graphs without a core and for dropped molecules)."""
+    curves["rmsd"] float32 [steps, num_graphs] and, when it came in with curves["mirror"] true, curves["rmsd_mirror"].
+    `core`: a dict {"weight": w, "start_sigma": s}: the batch's `core_pos` / `core_select` are held while sampling (epsnet.LangevinRun;
+    agdiff_amd/core.py) in every pass whose molecules include one with a core; it comes back with core["dev"] float32 [num_graphs],
+    the runs' `core_dev`.  Both hold a molecule's values from the pass that succeeded, NaN for dropped molecules (and graphs without a core)."""
     import torch
     T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
-    spans = packed["spans"]
-    n_mol = len(spans)
-    _check_counter(model, packed, counter_seed)
+    n_mol = len(packed["spans"])
+    check_counter(model, packed, counter_seed)
     if curves is not None:
         if packed.get("pos_target") is None:
             raise ValueError("tracking the RMSD needs `pos_target` in the packed batch (every molecule with its pos_target)")
@@ -303,62 +283,83 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
                 log("Retrying with local clipping.")
         return None, None, np.zeros(n_mol, dtype=bool)
 
-    N = packed["atom_type"].shape[0]
-    pos_out = torch.full((N, 3), float("nan"))
-    traj_out = None
-    ok = np.zeros(n_mol, dtype=bool)
-    # Passes still to run: (molecule slots of `packed`, clip_local, split-bf16?, attempts counted so far).  A molecule in which a
-    # NaN appeared is sampled again with clip_local=20 and that pass counts against max_retry (test.py:143-181).  A molecule
-    # whose ONLY fault was leaving the split-fp16 range (epsnet.check_nan) has not failed by the reference's lights: in fp32 it
-    # would have been sampled once, without local clipping -- it is sampled again in split-bf16 (fp32's exponent range) with
-    # the sampler settings unchanged, and that pass is not counted.
+    def run_pass(sub, todo, clip_local, wide, tries, first):
+        nonlocal topology
+        extra = {"topology": topology} if (topology is not None and sub is packed) else {}
+        topology = None                        # (moved to the device and owned by the run now)
+        if curves is not None:
+            extra.update(rmsd_target=sub["pos_target"], rmsd_mirror=bool(curves.get("mirror")))
+        held = core is not None and bool(np.asarray(sub["core_select"]).any())      # (a retry of molecules without a core: as ever)
+        if held:
+            extra.update(core_pos=sub["core_pos"], core_select=sub["core_select"], core_weight=core.get("weight", 1.0),
+                         core_start_sigma=core.get("start_sigma", float("inf")))
+        run, pos, traj = run_part(model, sub, device, sampler_kwargs, counter_seed, tries, wide, pos_init if first else None,
+                                  clip_local=clip_local, save_traj=save_traj, noise=(noise if first else None), **extra)
+        per_graph = dict(rmsd=run.rmsd_curve, rmsd_mirror=run.rmsd_curve_mirror) if curves is not None else {}
+        if held:
+            per_graph["core_dev"] = run.core_dev
+        return pos.cpu(), (torch.stack(traj) if save_traj else None), run.nan_graphs().numpy(), getattr(run, "range_graphs", ()), per_graph
+
+    ok, got = sample_passes(packed, run_pass, max_retry, log)
+    if curves is not None:
+        curves.update({k: got[k] for k in ("rmsd", "rmsd_mirror") if k in got})
+    if "core_dev" in got:
+        core["dev"] = got["core_dev"]
+    return got["pos"], got.get("traj"), ok
+
+
+# what sample_batch / sample_batch_sharded met since the process started (run_job logs it with the job's summary)
+SAMPLE_STATS = {"range_trips": 0, "bf16x3_retries": 0, "dropped": 0}
+
+
+def sample_passes(packed, run_pass, max_retry, log):
+    """The retry schedule of sample_batch and dist.sample_batch_sharded: (ok [num molecules] bool, results).  The queue holds the
+    passes still to run: (molecule slots of `packed`, clip_local, split-bf16?, attempts counted so far).  A molecule in which a NaN
+    appeared is sampled again with clip_local=20 and that pass counts against max_retry (test.py:143-181).  One whose ONLY fault was
+    leaving the split-fp16 range (epsnet.check_nan) has not failed by the reference's lights: it is sampled again in split-bf16
+    (fp32's exponent range; no range watch there, so nothing is range-only in a `wide` pass), settings unchanged, and not counted.
+    run_pass(sub, todo, clip_local, wide, tries, first) samples `sub` (`packed` or its subset of the slots `todo`) and returns, on the host,
+    (pos [rows, 3], traj [steps, rows, 3] or None, bad_graph bool [graphs], the graphs that left the range, {name: tensor [..., graphs] or
+    None}).  results: "pos", "traj" and those names over the rows / graphs of `packed`, NaN where no pass succeeded."""
+    import torch
+    spans = packed["spans"]
+    n_mol = len(spans)
+    gfirst = np.concatenate([[0], np.cumsum([g for (_, _, g) in spans])])
+    size = {-2: packed["atom_type"].shape[0], -1: int(gfirst[-1])}       # (rows [..., N, 3] are counted by dimension -2, graphs [..., G] by -1)
+    ok, results = np.zeros(n_mol, dtype=bool), {}
     passes = [(list(range(n_mol)), None, False, 0)]
     first = True
     while passes:
         todo, clip_local, wide, tries = passes.pop(0)
         sub = packed if len(todo) == n_mol else subset_batch(packed, todo)
-        at, bi, bt, ba = T(sub["atom_type"]), T(sub["bond_index"]), T(sub["bond_type"]), T(sub["batch"])
-        counter = _counter_kwargs(sub, counter_seed, tries)
-        if first and pos_init is not None:
-            p0 = pos_init.to(device)
-        elif counter:
-            p0 = model.counter_normals(sub["batch"], counter["stream_ids"], counter_seed, [-1])[0]
-        else:
-            p0 = torch.randn(at.shape[0], 3).to(device)
-        with _arithmetic(model, wide):
-            extra = {"topology": topology} if (topology is not None and sub is packed) else {}
-            if curves is not None:
-                extra.update(rmsd_target=sub["pos_target"], rmsd_mirror=bool(curves.get("mirror")))
-            held = core is not None and bool(np.asarray(sub["core_select"]).any())      # (a retry of molecules without a core: as ever)
-            if held:
-                extra.update(core_pos=sub["core_pos"], core_select=sub["core_select"], core_weight=core.get("weight", 1.0),
-                             core_start_sigma=core.get("start_sigma", float("inf")))
-            run = model.begin_sampling(at, p0, bi, bt, ba, sub["num_graphs"], False, clip_local=clip_local,
-                                       save_traj=save_traj, raise_on_nan=False,
-                                       noise=(noise if first else None), **extra, **counter, **sampler_kwargs)
-            topology = None                    # (moved to the device and owned by the run now)
-            run.advance(run.remaining())
-            pos, traj = run.finish()
+        pos, traj, bad_graph, out_of_range, per_graph = run_pass(sub, todo, clip_local, wide, tries, first)
         first = False
-        pos = pos.cpu()
-        bad_graph = run.nan_graphs().numpy()
-        out_of_range = sorted(getattr(run, "range_graphs", ()))
-        if save_traj:
-            traj = torch.stack(traj)
-            if traj_out is None:
-                traj_out = torch.full((traj.shape[0], N, 3), float("nan"))
-        nan_failed, range_failed = _sort_results(todo, sub["spans"], spans, bad_graph, out_of_range, wide, ok, pos_out, pos,
-                                                 traj_out if save_traj else None, traj if save_traj else None)
-        if curves is not None:
-            _sort_curves(curves, run, todo, sub["spans"], spans, set(nan_failed) | set(range_failed))
-        if held:
-            _sort_per_graph(core["dev"], run.core_dev, todo, sub["spans"], spans, set(nan_failed) | set(range_failed))
-        if out_of_range:
-            SAMPLE_STATS["range_trips"] += len(out_of_range)
+        parts = [(k, t, -2) for k, t in (("pos", pos), ("traj", traj)) if t is not None] + [(k, t, -1) for k, t in per_graph.items() if t is not None]
+        for name, t, dim in parts:
+            if name not in results:
+                shape = list(t.shape)
+                shape[dim] = size[dim]
+                results[name] = torch.full(shape, float("nan"))
+        in_range_set = set(int(g) for g in out_of_range)
+        nan_failed, range_failed, g_off = [], [], 0
+        for slot, (off_s, n, g) in zip(todo, sub["spans"]):
+            bad = [k for k in range(g_off, g_off + g) if bad_graph[k]]
+            if bad:
+                (range_failed if (not wide and all(k in in_range_set for k in bad)) else nan_failed).append(slot)
+            else:
+                ok[slot] = True
+                off = spans[slot][0]
+                for name, t, dim in parts:           # one scatter by molecule slot
+                    if dim == -2:
+                        results[name][..., off:off + n * g, :] = t[..., off_s:off_s + n * g, :]
+                    else:
+                        results[name][..., gfirst[slot]:gfirst[slot] + g] = t[..., g_off:g_off + g]
+            g_off += g
+        SAMPLE_STATS["range_trips"] += len(in_range_set)
         if range_failed:
             SAMPLE_STATS["bf16x3_retries"] += 1
             log("%d conformers left the split-fp16 range: sampling their molecules (%d of %d) again in split-bf16."
-                % (len(out_of_range), len(range_failed), len(sub["spans"])))
+                % (len(in_range_set), len(range_failed), len(sub["spans"])))
             passes.append((range_failed, clip_local, True, tries))
         if nan_failed:
             if tries + 1 < max_retry:
@@ -366,67 +367,10 @@ def sample_batch(model, packed, device, sampler_kwargs, save_traj=False, max_ret
                 passes.append((nan_failed, 20, wide, tries + 1))
             else:
                 SAMPLE_STATS["dropped"] += len(nan_failed)
-    return pos_out, traj_out, ok
+    return ok, results
 
 
-# what sample_batch / sample_batch_sharded met since the process started (run_job logs it with the job's summary)
-SAMPLE_STATS = {"range_trips": 0, "bf16x3_retries": 0, "dropped": 0}
-
-
-def _sort_results(todo, sub_spans, spans, bad_graph, out_of_range, wide, ok, pos_out, pos, traj_out, traj):
-    """One pass's molecules: the good ones' rows go into pos_out / traj_out (rows of `packed`), the others are returned as
-    (molecules with a NaN graph, molecules whose bad graphs all merely left the split-fp16 range).  In split-bf16 (`wide`)
-    the range watch does not run, so nothing is range-only there."""
-    in_range_set = set(int(g) for g in out_of_range)
-    nan_failed, range_failed, g_off = [], [], 0
-    for slot, (off_s, n, g) in zip(todo, sub_spans):
-        off, _, _ = spans[slot]
-        bad = [k for k in range(g_off, g_off + g) if bad_graph[k]]
-        if bad:
-            (range_failed if (not wide and all(k in in_range_set for k in bad)) else nan_failed).append(slot)
-        else:
-            ok[slot] = True
-            pos_out[off:off + n * g] = pos[off_s:off_s + n * g]
-            if traj_out is not None:
-                traj_out[:, off:off + n * g] = traj[:, off_s:off_s + n * g]
-        g_off += g
-    return nan_failed, range_failed
-
-
-def _sort_curves(curves, run, todo, sub_spans, spans, failed):
-    """One pass's tracked curves (run.rmsd_curve [steps, graphs of the pass]): the columns of the molecules that succeeded go into
-    curves["rmsd"] / curves["rmsd_mirror"] [steps, graphs of `packed`], which start out as NaN."""
-    import torch
-    gfirst = np.concatenate([[0], np.cumsum([g for (_, _, g) in spans])])
-    for key, got in (("rmsd", run.rmsd_curve), ("rmsd_mirror", run.rmsd_curve_mirror)):
-        if got is None:
-            continue
-        if curves.get(key) is None:
-            curves[key] = torch.full((got.shape[0], int(gfirst[-1])), float("nan"))
-        g_off = 0
-        for slot, (_, _, g) in zip(todo, sub_spans):
-            if slot not in failed:
-                curves[key][:, gfirst[slot]:gfirst[slot] + g] = got[:, g_off:g_off + g]
-            g_off += g
-
-
-def _sort_per_graph(out, got, todo, sub_spans, spans, failed):
-    """One pass's per-graph values `got` [graphs of the pass] (run.core_dev): the entries of the molecules that succeeded go into
-    `out` [graphs of `packed`]."""
-    gfirst = np.concatenate([[0], np.cumsum([g for (_, _, g) in spans])])
-    g_off = 0
-    for slot, (_, _, g) in zip(todo, sub_spans):
-        if slot not in failed:
-            out[gfirst[slot]:gfirst[slot] + g] = got[g_off:g_off + g]
-        g_off += g
-
-
-def _has_core(m):
-    """The molecule carries a template and a mask that selects an atom."""
-    return m.get("core_pos") is not None and m.get("core_mask") is not None and bool(np.asarray(m["core_mask"]).any())
-
-
-def _check_counter(model, packed, counter_seed):
+def check_counter(model, packed, counter_seed):
     """--noise counter needs the batch's stream ids (pack_batch: every molecule with its `index`) and a model that draws from
     the counter-based generator."""
     if counter_seed is None:
@@ -437,20 +381,30 @@ def _check_counter(model, packed, counter_seed):
         raise ValueError("counter noise: the model has no counter-based generator (begin_sampling / counter_normals)")
 
 
-def _counter_kwargs(part, counter_seed, attempt):
-    """begin_sampling's keyword arguments for counter noise on `part` (a packed batch, a subset or a rank's range of one) in
-    sampling pass `attempt` ({} in the default mode)."""
-    if counter_seed is None:
-        return {}
-    return dict(noise_mode="counter", noise_seed=int(counter_seed), stream_ids=with_attempt(part["stream_ids"], attempt))
-
-
-def _arithmetic(model, wide):
-    """`wide`: the model in split-bf16 for both branches (fp32's exponent range) for the duration of one attempt."""
+def run_part(model, part, device, sampler_kwargs, counter_seed, attempt, wide, pos_init=None, hook=None, **kw):
+    """One sampling run over `part` (a packed batch, a subset or a rank's range of one) in sampling pass `attempt`: (run, pos, traj).
+    pos_init as given; else, with a `counter_seed`, from the counter-based generator and the part's stream ids with that attempt, like
+    the steps' noise; else from torch's generator.  `wide`: the model in split-bf16 for both branches (fp32's exponent range) for
+    the duration of the run.  hook(run): the run's on_step.  `kw` goes to begin_sampling."""
     import contextlib
-    if wide and hasattr(model, "arithmetic"):
-        return model.arithmetic("bf16x3", "bf16x3")
-    return contextlib.nullcontext(model)
+    import torch
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    counter = {}
+    if counter_seed is not None:
+        counter = dict(noise_mode="counter", noise_seed=int(counter_seed), stream_ids=with_attempt(part["stream_ids"], attempt))
+    with model.arithmetic("bf16x3", "bf16x3") if (wide and hasattr(model, "arithmetic")) else contextlib.nullcontext():
+        if pos_init is not None:
+            p0 = pos_init.to(device)
+        elif counter:
+            p0 = model.counter_normals(part["batch"], counter["stream_ids"], counter_seed, [-1])[0]
+        else:
+            p0 = torch.randn(part["atom_type"].shape[0], 3).to(device)
+        run = model.begin_sampling(T(part["atom_type"]), p0, T(part["bond_index"]), T(part["bond_type"]), T(part["batch"]), part["num_graphs"],
+                                   False, raise_on_nan=False, **kw, **counter, **sampler_kwargs)
+        if hook is not None:
+            run.on_step = hook(run)
+        run.advance(run.remaining())
+        return (run,) + tuple(run.finish())
 
 
 def subset_batch(packed, slots):
@@ -531,111 +485,17 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     dict on rank 0 (None elsewhere).  noise="counter": every conformer's pos_init and noise are drawn from the counter-based
     generator under the key `seed` and the conformer's stream id (stream_id: molecule index, conformer, attempt) -- the same
     draws whatever `max_atoms`, the plan, a resume or the number of ranks put beside it; "default": torch's generator.
-    prune_rms=T (Angstrom, >= 0): every saved molecule also gets `kept_<i>` int32 [K] -- the conformers RDKit's pruneRmsThresh rule
-    keeps at T, indices into `pos_gen_<i>` -- and `cluster_<i>` int32 [G], the kept conformer each one belongs to
-    (agdiff_amd.ensemble.prune_conformers on the GPU, symmetry-aware through the molecule's bonds; at most
-    AGDIFF_PRUNE_MAX_CONFS conformers per molecule).  `pos_gen_<i>` holds all conformers either way.  One molecule at a time, after
-    the batch's retries have settled, by the rank that writes the batch's file: a few launches next to seconds of sampling.
-    prune_tfd=T (in [0, 1]) instead of prune_rms: the same keys from the same walk over the torsion fingerprint deviation
-    (agdiff_amd.torsions); giving both is a ValueError.
-    fix_handedness=True: the sampler cannot tell a molecule from its mirror image, so every conformer's stereocentres are read
-    against the molecule's `stereo` tags (load_testset: `stereo_<i>`; a molecule without them is an error) and the mirror images
-    are inverted through their centroid (agdiff_amd.stereo.fix_handedness on the GPU) -- before the prune, which then compares
-    like with like.  `pos_gen_<i>` holds the mirrored conformers, `hand_<i>` int8 [G] the verdict before the fix: -1 was mirrored,
-    0 (a diastereomer or a flat centre) is left as sampled, +1 was right.
-    fix_double_bonds=True: the bond types say "double", not E or Z, so every conformer's tagged double bonds are read against the
-    molecule's `ez_quads` / `ez` tags (load_testset: `ez_quads_<i>`, `ez_<i>`; a molecule without them is an error) and the wrong
-    ones are turned over, one side of the bond by 180 degrees about it (agdiff_amd.ezbonds.fix_double_bonds on the GPU; DESIGN.md
-    4.17) -- after the core frame and the handedness fix, and BEFORE the repairs, the checks and the prune: the rotation keeps
-    every distance within each side but can bring the two sides into contact, which the repair then sees.  With hold_core the core
-    atoms never move: the other side turns, and a bond with core atoms on both sides is left as sampled.  `pos_gen_<i>` holds the
-    flipped conformers, `ez_state_<i>` int8 [G, D] each bond's state before the fix: +1 right, -1 wrong (flipped, unless it is a
-    ring bond or held on both sides), 0 undecided or untagged.
-    check_geometry=True: every saved molecule also gets `valid_<i>` int8 [G], `bond_dev_<i>` float32 [G] (the worst violation of a
-    bond-length bound in Angstrom) and `clash_<i>` float32 [G] (the smallest distance between atoms more than three bonds apart as
-    a fraction of their van der Waals sum) -- agdiff_amd.validity.check_geometry with the table bounds, after the handedness fix
-    and before the prune.  `pos_gen_<i>` is left as it is; with a prune switch the invalid conformers take no part in the walk
-    (`cluster_<i>` is -1 for them).
-    check_planarity=True: every saved molecule also gets `flat_<i>` int8 [G] and `flat_dev_<i>` float32 [G] (the largest distance of
-    an atom from the best plane of its aromatic ring or of its double bond and that bond's neighbours, in Angstrom) --
-    agdiff_amd.planarity.check_planarity with its defaults, after the handedness fix and the repair, next to check_geometry, whose
-    `valid_<i>` does not change.  With a prune switch the bent conformers take no part in the walk either (`cluster_<i>` is -1 for
-    them): the mask handed to the prune is `flat`, and `flat & valid` with check_geometry.
-    repair_geometry=True: the conformers those two checks call invalid are not only marked: their atoms are moved by small steps
-    until every bond length and every contact is back inside the limits (agdiff_amd.validity.repair_geometry with the table bounds
-    and its defaults; a projection onto distance bounds, NOT MMFF: no energies, torsions or electrostatics) -- after the handedness
-    fix (a mirror image has the same distances) and before the check and the prune, which then describe the repaired conformers.
-    `pos_gen_<i>` holds the repaired conformers (a valid one is unchanged bit for bit), `repair_status_<i>` int8 [G] is 0 valid as
-    sampled, 1 repaired, 2 not repaired within the iteration limit, 3 not finite, and `repair_moved_<i>` float32 [G] the root mean
-    square displacement of the atoms in Angstrom.
-    repair_planarity=True: repair_geometry's step with planes -- one launch of agdiff_amd.planarity.repair_planarity with the table
-    bounds and its defaults at the same place: the conformers check_planarity calls bent are flattened (every atom of an aromatic
-    ring or of a double bond and its neighbours to within 0.10 Angstrom of the group's best plane) while the bond lengths and
-    contacts are held or repaired as repair_geometry does; still NOT MMFF, and E or Z is not chosen (unless fix_double_bonds ran
-    first).  A superset of repair_geometry:
-    giving both switches equals giving this one.  The same keys, `repair_status_<i>` (0: valid AND flat as sampled) and
-    `repair_moved_<i>`; both checks and the prune then describe the repaired conformers.
-    track_rmsd=True: every saved molecule also gets `rmsd_traj_<i>` float32 [steps, G]: each conformer's heavy-atom RMSD to the
-    molecule's `pos_target` (load_testset: `pos_target_<i>`; a molecule without one is an error) after every denoising step,
-    computed while the run samples (agdiff_amd.trajectory), with or without save_traj; track_rmsd_mirror=True adds
-    `rmsd_mirror_traj_<i>`, the RMSD of the mirror image.  Not with graph-sharded sampling (shard=True, what --dist-mode shard is over
-    several ranks: each rank updates only its own graphs); whole batches per rank (shard=False) work.
-    hold_core=True: conformers around a fixed core (agdiff_amd.core).  A molecule with `core_pos` / `core_mask`
-    (load_testset: `core_pos_<i>`, `core_mask_<i>`; no molecule with one is an error) is sampled with those atoms held to the
-    template's internal geometry: its batch runs with epsnet.LangevinRun's core_pos / core_select, core_weight (in (0, 1]) and
-    core_start_sigma (hold only below this noise level; the last step is always held exactly); batches without such a molecule are
-    sampled as ever.  Before anything else is done to them its conformers are superposed on `core_pos_<i>` over the core atoms
-    (agdiff_align_conformers), so `pos_gen_<i>` is in the template's frame with the core atoms on the template, and
-    `core_rmsd_<i>` float32 [G] says how far the last denoising step had pulled each conformer's core out of shape before the
-    closing hold.  Not with graph-sharded sampling (shard=True); whole batches per rank (shard=False) work."""
-    if hold_core:
-        from .core import core_arguments
-        if not any(_has_core(m) for m in mols):
-            raise ValueError("hold_core needs `core_pos_<i>` and `core_mask_<i>` in the test set; none of the %d molecules has them"
-                             % len(mols))
-        if shard:
-            raise ValueError("hold_core does not work with graph-sharded sampling (shard=True, %d ranks: each rank updates only its "
-                             "own graphs); use --dist-mode batches" % world)
-        for m in mols:
-            if _has_core(m):
-                try:
-                    core_arguments(m["atom_type"].shape[0], m["core_pos"], m["core_mask"], core_weight, core_start_sigma)
-                except ValueError as e:
-                    raise ValueError("hold_core, molecule %s: %s" % (m["name"], e))
-    hold = dict(weight=float(core_weight), start_sigma=float(core_start_sigma)) if hold_core else None
-    track_rmsd = bool(track_rmsd or track_rmsd_mirror)
-    if track_rmsd:
-        missing = [m["name"] for m in mols if m.get("pos_target") is None]
-        if missing:
-            raise ValueError("track_rmsd needs `pos_target_<i>` in the test set; missing for %d molecules: %s"
-                             % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
-        if shard:
-            raise ValueError("track_rmsd does not work with graph-sharded sampling (shard=True, %d ranks: each rank updates only its "
-                             "own graphs); use --dist-mode batches" % world)
+    Every other switch but save_traj (`traj_<i>`) turns on one step of agdiff_amd.postprocess.STEPS, the order in which they run over
+    each saved molecule: CoreFrame (hold_core, core_weight, core_start_sigma), Handedness, DoubleBonds, Repair, CheckGeometry,
+    CheckPlanarity, Prune, TrackedRmsd; each class names its switches, what it needs of the test set and the keys it saves."""
+    keywords = dict(locals())                  # (first: the arguments and nothing else; each step reads its own switches)
+    import contextlib
+    from . import postprocess
     if noise not in ("default", "counter"):
         raise ValueError("noise must be 'default' or 'counter'")
-    if prune_rms is not None and not float(prune_rms) >= 0.0:
-        raise ValueError("prune_rms must be >= 0 (an RMSD threshold in Angstrom) or None")
-    if prune_tfd is not None and prune_rms is not None:
-        raise ValueError("prune_rms and prune_tfd are two rules for one pair of keys (kept_<i>, cluster_<i>): give one of them")
-    if prune_tfd is not None and not float(prune_tfd) >= 0.0:
-        raise ValueError("prune_tfd must be >= 0 (a torsion fingerprint deviation, in [0, 1]) or None")
-    if fix_handedness:
-        missing = [m["name"] for m in mols if m.get("stereo") is None]
-        if missing:
-            raise ValueError("fix_handedness needs `stereo_<i>` in the test set (python -m agdiff_amd.stereo adds it); missing for "
-                             "%d molecules: %s" % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
-    if fix_double_bonds:
-        missing = [m["name"] for m in mols if m.get("ez_quads") is None or m.get("ez") is None]
-        if missing:
-            raise ValueError("fix_double_bonds needs `ez_quads_<i>` and `ez_<i>` in the test set (python -m agdiff_amd.ezbonds adds them); "
-                             "missing for %d molecules: %s" % (len(missing), ", ".join(map(str, missing[:5])) + (" ..." if len(missing) > 5 else "")))
-        from .ezbonds import ez_table
-        for m in mols:
-            try:
-                ez_table(m)
-            except ValueError as e:
-                raise ValueError("fix_double_bonds, molecule %s: %s" % (m["name"], e))
+    steps = postprocess.enabled_steps(keywords)
+    for step in steps:
+        step.require(mols, shard, world)
     counter_seed = int(seed) if noise == "counter" else None
     import torch.distributed as dist
     os.makedirs(out_dir, exist_ok=True)
@@ -649,18 +509,63 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
     mols = [m for m in mols if m["index"] not in done]
     batches = plan_batches(mols, confs_of, sharded_capacity(max_atoms, world) if shard else max_atoms)
     mine = [bidx for bidx in range(len(batches)) if shard or bidx % world == rank]
-    # The next batch is packed -- and its topology built -- while the GPU samples the current one, in a background thread (the
-    # sampling loop spends its time inside library calls, which release the interpreter lock).  Measured on the MI355X box, four
-    # 196 k-atom batches x 600 steps (tools/job_wall.py, profiles/r06_job_wall.json): sampling + saving alone 10.13 s, preparation
-    # inline 11.3 s (0.29 s per batch), thread 10.8 s, worker process 11.8 s.
-    # AGDIFF_PREPARE=process: a worker PROCESS (agdiff_amd/prep_worker.py, a fresh interpreter started as a child; host work only)
-    # -- it shares nothing with the launch loop, but its reply (~100 MB of index arrays per batch) comes back through a pipe and a
-    # pickle, which costs the main thread more than the thread's lock contention on a host with fast cores; for hosts where the
-    # numpy build takes seconds per batch.  =inline: on the main thread, when the batch's turn comes (measurements, debugging).
-    from concurrent.futures import Future, ThreadPoolExecutor
-    prep = lambda bidx: prepare_batch(model, batches[bidx], confs_of, rank if shard else 0, world if shard else 1)
+    with contextlib.closing(_prepared_batches(model, batches, mine, confs_of, rank if shard else 0, world if shard else 1, log)) as prepared:
+        for bidx, bmols, packed, topology in prepared:
+            extras = {}                        # (what the steps ask of the sampler; it comes back filled in, for their apply)
+            if shard:
+                from .dist import sample_batch_sharded
+                pos, traj, ok = sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log,
+                                                     topology=topology, counter_seed=counter_seed)
+                if rank != 0:
+                    continue
+            else:
+                for step in steps:
+                    extras.update(step.sampler_keywords(packed))
+                pos, traj, ok = sample_batch(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log, topology=topology,
+                                             counter_seed=counter_seed, **extras)
+            if not ok.any():
+                log("batch %d: every molecule failed twice (NaN); skipped: %s" % (bidx, [m["name"] for m in bmols]))
+                continue
+            out = {}
+            g_first = 0
+            for m, (off, n, g), good in zip(bmols, packed["spans"], ok):
+                g_first += g
+                if not good:
+                    log("molecule %s failed twice (NaN); skipped" % m["name"])
+                    continue
+                out["pos_gen_%d" % m["index"]] = pos[off:off + n * g].numpy().reshape(g, n, 3)
+                out["name_%d" % m["index"]] = np.str_(m["name"])
+                ctx = postprocess.MolContext(dict(atom_type=m["atom_type"], edge_index=m["edge_index"], edge_type=m["edge_type"]), device,
+                                             slice(g_first - g, g_first), extras)
+                postprocess.run_chain(steps, m, out, ctx)
+                if traj is not None:
+                    out["traj_%d" % m["index"]] = traj[:, off:off + n * g].numpy().reshape(traj.shape[0], g, n, 3)
+            _save_npz_atomic(_batch_path(out_dir, bmols), out)
+            log("rank %d: batch %d/%d (%d of %d molecules, %d conformers) saved" % (rank, bidx + 1, len(batches),
+                                                                                   int(ok.sum()), len(bmols), packed["num_graphs"]))
+    for line in filter(None, (step.summary(rank) for step in steps)):       # (None on a rank that wrote no file)
+        log(line)
+    if world > 1:
+        dist.barrier()                       # every rank's batch files are on disk
+    if SAMPLE_STATS["range_trips"]:
+        log("rank %d: %d conformers left the split-fp16 range; their molecules were sampled again in split-bf16 (%d extra passes)"
+            % (rank, SAMPLE_STATS["range_trips"], SAMPLE_STATS["bf16x3_retries"]))
+    if SAMPLE_STATS["dropped"]:
+        log("rank %d: %d molecules were dropped (a NaN in every attempt)" % (rank, SAMPLE_STATS["dropped"]))
+    return merge_outputs(out_dir) if rank == 0 else None
+
+
+def _prepared_batches(model, batches, mine, confs_of, rank, world, log):
+    """Yields (bidx, bmols, packed, topology) for the batches `mine`, each prepared (prepare_batch for `rank` of `world`) while the
+    GPU samples the one before it: in a background thread (the sampling loop spends its time inside library calls, which release
+    the interpreter lock).  Four 196 k-atom batches x 600 steps on an MI355X (tools/job_wall.py, profiles/r06_job_wall.json):
+    sampling + saving alone 10.13 s, preparation inline 11.3 s, thread 10.8 s, worker process 11.8 s.
+    AGDIFF_PREPARE=process: a worker PROCESS (agdiff_amd/prep_worker.py; host work only) -- it shares nothing with the launch loop,
+    but its reply (~100 MB of index arrays per batch) comes back through a pipe and a pickle; for hosts where the numpy build takes
+    seconds per batch.  =inline: on the main thread, when the batch's turn comes (measurements, debugging)."""
+    from concurrent.futures import ThreadPoolExecutor
+    prep = lambda bidx: prepare_batch(model, batches[bidx], confs_of, rank, world)
     how = os.environ.get("AGDIFF_PREPARE", "inline" if os.environ.get("AGDIFF_PREPARE_INLINE", "0") not in ("", "0") else "thread")
-    inline = how == "inline"
     worker, pool = None, None
     if how == "process" and hasattr(model, "prepare_topology") and hasattr(model, "config") and len(mine) > 1:
         try:
@@ -670,189 +575,39 @@ def run_job(model, mols, out_dir, confs_of, max_atoms, sampler_kwargs, device, s
             log("run_job: no worker process for the batch preparation (%s: %s); using a thread" % (type(e).__name__, e))
     if worker is None:
         pool = ThreadPoolExecutor(max_workers=1)
-    opts = _topology_options(model) if worker is not None else None
+    if worker is not None:      # (what model.prepare_topology needs of the model, as plain values: they travel to the worker process)
+        opts = dict(order=int(model.config.edge_order), group_targets=getattr(model, "group_targets", None),
+                    radius_column=bool(getattr(model, "tuning", {}).get("group_radius_column", 1)))
 
-    class _FromWorker:
-        on_main = False
-
-        def result(self):
-            return worker.result()
-
-    def submit(bidx, first=False):
-        if inline or (first and worker is not None):
-            f = Future()
-            f.set_result(bidx)                 # (resolved on the main thread, when the batch's turn comes)
-            f.on_main = True
-            return f
+    def request(bidx, first=False):
+        """Starts the batch's preparation; returns the call that waits for it."""
+        if how == "inline" or (first and worker is not None):
+            return lambda: prep(bidx)          # (on the main thread, when the batch's turn comes)
         if worker is not None:
-            worker.submit(batches[bidx], [confs_of(m["num_refs"]) for m in batches[bidx]], rank if shard else 0, world if shard else 1, opts)
-            return _FromWorker()
-        f = pool.submit(prep, bidx)
-        f.on_main = False
-        return f
-    fut = submit(mine[0], first=True) if mine else None
+            worker.submit(batches[bidx], [confs_of(m["num_refs"]) for m in batches[bidx]], rank, world, opts)
+            return worker.result
+        return pool.submit(prep, bidx).result
     try:
-        return _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank,
-                                world, counter_seed, prune_rms, fix_handedness, prune_tfd,
-                                ({"mirror": bool(track_rmsd_mirror)} if track_rmsd else None), repair_geometry, check_planarity,
-                                repair_planarity, hold, fix_double_bonds, check_geometry)
+        arrived = request(mine[0], first=True) if mine else None
+        for k, bidx in enumerate(mine):
+            # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until
+            # here, and a request larger than the pipe's buffer sent before that would wait for a reader that is itself waiting)
+            try:
+                packed, topology = arrived()
+            except Exception as e:                   # (a worker that died: this batch on the main thread)
+                log("run_job: the prepared batch did not arrive (%s: %s); preparing it here" % (type(e).__name__, e))
+                packed, topology = prep(bidx)
+            try:
+                arrived = request(mine[k + 1]) if k + 1 < len(mine) else None
+            except Exception as e:                   # (the worker's pipe is gone: the next batch on the main thread, when its turn comes)
+                log("run_job: the next batch could not be handed to the worker (%s: %s)" % (type(e).__name__, e))
+                arrived = lambda b=mine[k + 1]: prep(b)
+            yield bidx, batches[bidx], packed, topology
     finally:
         if worker is not None:
             worker.close()
         if pool is not None:
             pool.shutdown(wait=True)
-
-
-def _run_job_batches(model, batches, mine, fut, submit, prep, inline, shard, device, sampler_kwargs, save_traj, log, out_dir, rank, world,
-                     counter_seed=None, prune_rms=None, fix_handedness=False, prune_tfd=None, track=None, repair_geometry=False,
-                     check_planarity=False, repair_planarity=False, hold=None, fix_double_bonds=False, check_geometry=False):
-    import torch.distributed as dist
-    mirrored = undecided = checked = invalid = repaired = stuck = seen = judged = bent = 0
-    ez_flipped = ez_left = ez_open = ez_seen = 0
-    for pos_in_mine, bidx in enumerate(mine):
-        bmols = batches[bidx]
-        # (first this batch's reply, THEN the next request: the worker writes a reply of ~100 MB into a pipe nobody reads until here,
-        # and a request larger than the pipe's buffer sent before that would wait for a reader that is itself waiting)
-        try:
-            packed, topology = prep(fut.result()) if getattr(fut, "on_main", inline) else fut.result()
-        except Exception as e:                   # (a worker that died: this batch on the main thread)
-            log("run_job: the prepared batch did not arrive (%s: %s); preparing it here" % (type(e).__name__, e))
-            packed, topology = prep(bidx)
-        try:
-            fut = submit(mine[pos_in_mine + 1]) if pos_in_mine + 1 < len(mine) else None
-        except Exception as e:                   # (the worker's pipe is gone: the next batch on the main thread, when its turn comes)
-            log("run_job: the next batch could not be handed to the worker (%s: %s)" % (type(e).__name__, e))
-            from concurrent.futures import Future
-            fut = Future()
-            fut.set_result(mine[pos_in_mine + 1])
-            fut.on_main = True
-        if shard:
-            from .dist import sample_batch_sharded
-            pos, traj, ok = sample_batch_sharded(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log,
-                                                 topology=topology, counter_seed=counter_seed)
-            if rank != 0:
-                continue
-        else:
-            curves = dict(track) if track is not None else None
-            core = dict(hold) if (hold is not None and packed.get("core_pos") is not None) else None
-            pos, traj, ok = sample_batch(model, packed, device, sampler_kwargs, save_traj=save_traj, log=log, topology=topology,
-                                         counter_seed=counter_seed, **({"curves": curves} if curves is not None else {}),
-                                         **({"core": core} if core is not None else {}))
-        if not ok.any():
-            log("batch %d: every molecule failed twice (NaN); skipped: %s" % (bidx, [m["name"] for m in bmols]))
-            continue
-        out = {}
-        g_first = 0
-        for m, (off, n, g), good in zip(bmols, packed["spans"], ok):
-            g_first += g
-            if not good:
-                log("molecule %s failed twice (NaN); skipped" % m["name"])
-                continue
-            if track is not None:
-                for key, name in (("rmsd", "rmsd_traj_%d"), ("rmsd_mirror", "rmsd_mirror_traj_%d")):
-                    if curves.get(key) is not None:
-                        out[name % m["index"]] = curves[key][:, g_first - g:g_first].numpy().copy()
-            out["pos_gen_%d" % m["index"]] = pos[off:off + n * g].numpy().reshape(g, n, 3)
-            out["name_%d" % m["index"]] = np.str_(m["name"])
-            if hold is not None and _has_core(m):
-                from .core import to_template_frame          # (first: what follows then sees the conformers in the template's frame)
-                out["pos_gen_%d" % m["index"]] = to_template_frame(out["pos_gen_%d" % m["index"]], m["core_pos"], m["core_mask"],
-                                                                   device=device).cpu().numpy()
-                out["core_rmsd_%d" % m["index"]] = core["dev"][g_first - g:g_first].numpy().astype(np.float32)
-            if fix_handedness:
-                import torch
-                from .stereo import fix_handedness as fix
-                on_gpu = torch.from_numpy(np.ascontiguousarray(out["pos_gen_%d" % m["index"]], dtype=np.float32)).to(device)
-                hand = fix(dict(atom_type=m["atom_type"], edge_index=m["edge_index"], edge_type=m["edge_type"], stereo=m["stereo"]),
-                           on_gpu).cpu().numpy().astype(np.int8)
-                out["pos_gen_%d" % m["index"]] = on_gpu.cpu().numpy()
-                out["hand_%d" % m["index"]] = hand
-                mirrored += int((hand < 0).sum())
-                undecided += int((hand == 0).sum())
-            if fix_double_bonds:
-                import torch
-                from .ezbonds import double_bond_verdict, ez_table, fix_double_bonds as flip
-                item = dict(atom_type=m["atom_type"], edge_index=m["edge_index"], edge_type=m["edge_type"], ez_quads=m["ez_quads"], ez=m["ez"])
-                on_gpu = torch.from_numpy(np.ascontiguousarray(out["pos_gen_%d" % m["index"]], dtype=np.float32)).to(device)
-                frozen = (np.asarray(m["core_mask"]).reshape(-1) != 0) if (hold is not None and _has_core(m)) else None
-                state = flip(item, on_gpu, frozen=frozen).cpu().numpy().astype(np.int8)
-                after = double_bond_verdict(on_gpu, *ez_table(item)).cpu().numpy()
-                out["pos_gen_%d" % m["index"]] = on_gpu.cpu().numpy()
-                out["ez_state_%d" % m["index"]] = state
-                ez_seen += int(state.shape[0])
-                ez_flipped += int(((state < 0) & (after > 0)).any(axis=1).sum())
-                ez_left += int((after < 0).sum())
-                ez_open += int(((state == 0) & (np.asarray(m["ez"]).reshape(1, -1) != 0)).sum())
-            if repair_geometry or repair_planarity:
-                if repair_planarity:                   # (holds the bonds too: the distance repair is part of it)
-                    from .planarity import repair_planarity as repair
-                else:
-                    from .validity import repair_geometry as repair
-                res = repair(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
-                                  edge_type=m["edge_type"]), device=device)
-                status = res["status"].cpu().numpy()
-                out["pos_gen_%d" % m["index"]] = res["pos"].cpu().numpy()
-                out["repair_status_%d" % m["index"]] = status.astype(np.int8)
-                out["repair_moved_%d" % m["index"]] = res["moved"].cpu().numpy()
-                seen += int(status.shape[0])
-                repaired += int((status == 1).sum())
-                stuck += int((status == 2).sum())
-            valid = None
-            if check_geometry:
-                from .validity import check_geometry as check
-                res = check(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
-                                 edge_type=m["edge_type"]), device=device)
-                valid = res["valid"]
-                out["valid_%d" % m["index"]] = valid.cpu().numpy().astype(np.int8)
-                out["bond_dev_%d" % m["index"]] = res["bond_dev"].cpu().numpy()
-                out["clash_%d" % m["index"]] = res["clash"].cpu().numpy()
-                checked += int(valid.shape[0])
-                invalid += int((~valid).sum())
-            if check_planarity:
-                from .planarity import check_planarity as planar
-                res = planar(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
-                                  edge_type=m["edge_type"]), device=device)
-                out["flat_%d" % m["index"]] = res["flat"].cpu().numpy().astype(np.int8)
-                out["flat_dev_%d" % m["index"]] = res["flat_dev"].cpu().numpy()
-                judged += int(res["flat"].shape[0])
-                bent += int((~res["flat"]).sum())
-                valid = res["flat"] if valid is None else valid & res["flat"]      # (the prune's mask; valid_<i> is already saved)
-            if prune_rms is not None or prune_tfd is not None:
-                from .ensemble import prune_conformers
-                res = prune_conformers(dict(atom_type=m["atom_type"], pos_gen=out["pos_gen_%d" % m["index"]], edge_index=m["edge_index"],
-                                            edge_type=m["edge_type"]), float(prune_rms if prune_tfd is None else prune_tfd), align=False,
-                                       device=device, metric="rmsd" if prune_tfd is None else "tfd", valid=valid)
-                out["kept_%d" % m["index"]] = res["kept"].cpu().numpy()
-                out["cluster_%d" % m["index"]] = res["leader"].cpu().numpy()
-            if traj is not None:
-                out["traj_%d" % m["index"]] = traj[:, off:off + n * g].numpy().reshape(traj.shape[0], g, n, 3)
-        _save_npz_atomic(_batch_path(out_dir, bmols), out)
-        log("rank %d: batch %d/%d (%d of %d molecules, %d conformers) saved" % (rank, bidx + 1, len(batches),
-                                                                               int(ok.sum()), len(bmols), packed["num_graphs"]))
-    if fix_handedness and (rank == 0 or mirrored or undecided):       # (the ranks that wrote files)
-        log("rank %d: %d conformers were mirror images and were inverted; %d match neither hand (verdict 0) and stay as sampled"
-            % (rank, mirrored, undecided))
-    if fix_double_bonds and (rank == 0 or ez_seen):
-        log("rank %d: %d of %d conformers had a double bond of the wrong E/Z parity flipped; %d bonds stay wrong (in a ring, or held on "
-            "both sides) and %d tagged bonds are undecided (ez_state_<i> = 0)" % (rank, ez_flipped, ez_seen, ez_left, ez_open))
-    if (repair_geometry or repair_planarity) and (rank == 0 or seen):
-        log("rank %d: %d of %d conformers were repaired (%s); %d more were not within the iteration limit (repair_status_<i> = 2)"
-            % (rank, repaired, seen, "flattened and moved into their distance bounds" if repair_planarity else
-               "moved into their distance bounds", stuck))
-    if check_geometry and (rank == 0 or checked):
-        log("rank %d: %d of %d conformers are invalid (a bond length out of bounds or a steric clash) and are marked in valid_<i>"
-            % (rank, invalid, checked))
-    if check_planarity and (rank == 0 or judged):
-        log("rank %d: %d of %d conformers are bent (an aromatic ring or a double bond out of plane) and are marked in flat_<i>"
-            % (rank, bent, judged))
-    if world > 1:
-        dist.barrier()                       # every rank's batch files are on disk
-    if SAMPLE_STATS["range_trips"]:
-        log("rank %d: %d conformers left the split-fp16 range; their molecules were sampled again in split-bf16 (%d extra passes)"
-            % (rank, SAMPLE_STATS["range_trips"], SAMPLE_STATS["bf16x3_retries"]))
-    if SAMPLE_STATS["dropped"]:
-        log("rank %d: %d molecules were dropped (a NaN in every attempt)" % (rank, SAMPLE_STATS["dropped"]))
-    return merge_outputs(out_dir) if rank == 0 else None
 
 
 def main(argv=None):

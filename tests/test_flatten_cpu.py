@@ -116,10 +116,10 @@ def test_the_new_functions_refuse_bad_input_before_any_launch():
 
 def test_signatures_and_command_line_switches(tmp_path):
     import argparse
-    from agdiff_amd import driver, planarity
-    for fn in (driver.run_job, driver._run_job_batches):
-        assert inspect.signature(fn).parameters["repair_planarity"].default is False
-        assert inspect.signature(fn).parameters["repair_geometry"].default is False
+    from agdiff_amd import driver, planarity, postprocess
+    for name in ("repair_planarity", "repair_geometry"):
+        assert inspect.signature(driver.run_job).parameters[name].default is False
+        assert any(name in step.switches for step in postprocess.STEPS)
     sig = inspect.signature(planarity.relax_planar).parameters
     assert list(sig) == ["pos", "grp_ptr", "grp_idx", "pairs", "lo", "hi", "radius", "ex_ptr", "ex_idx", "thresh", "flat_to", "clash", "pad",
                          "omega", "max_iter"]

@@ -260,8 +260,9 @@ def test_command_lines_and_signatures(tmp_path):
             assert seen["args"].check_planarity is want and seen["args"].check_geometry is False
     finally:
         argparse.ArgumentParser.parse_args = real
-    for fn in (driver.run_job, driver._run_job_batches):
-        assert inspect.signature(fn).parameters["check_planarity"].default is False
+    from agdiff_amd import postprocess
+    assert inspect.signature(driver.run_job).parameters["check_planarity"].default is False
+    assert any("check_planarity" in step.switches for step in postprocess.STEPS)
     sig = inspect.signature(planarity.check_planarity).parameters
     assert list(sig) == ["item", "thresh", "groups", "device", "want_dev"]
     assert [sig[k].default for k in ("thresh", "groups", "device", "want_dev")] == [0.25, None, "cuda", False]

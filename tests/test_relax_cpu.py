@@ -111,9 +111,9 @@ def test_relax_tables_refuse_bad_input_before_any_launch():
 
 def test_signatures_and_command_line_switches(tmp_path):
     import argparse
-    from agdiff_amd import driver, validity
-    for fn in (driver.run_job, driver._run_job_batches):
-        assert inspect.signature(fn).parameters["repair_geometry"].default is False
+    from agdiff_amd import driver, postprocess, validity
+    assert inspect.signature(driver.run_job).parameters["repair_geometry"].default is False
+    assert any("repair_geometry" in step.switches for step in postprocess.STEPS)
     sig = inspect.signature(validity.relax_bounds).parameters
     assert list(sig) == ["pos", "pairs", "lo", "hi", "radius", "ex_ptr", "ex_idx", "clash", "pad", "omega", "max_iter"]
     assert [sig[k].default for k in ("clash", "pad", "omega", "max_iter")] == [0.60, 0.02, 1.0, 200]

@@ -210,10 +210,11 @@ def test_command_lines_accept_the_new_switches(tmp_path):
 
 def test_run_job_and_prune_signatures_keep_their_positional_order():
     import inspect
-    from agdiff_amd import driver, ensemble
-    for fn, name in ((driver.run_job, "check_geometry"), (driver._run_job_batches, "check_geometry"), (ensemble.prune_conformers, "valid")):
+    from agdiff_amd import driver, ensemble, postprocess
+    for fn, name in ((driver.run_job, "check_geometry"), (ensemble.prune_conformers, "valid")):
         params = list(inspect.signature(fn).parameters.values())
         assert params[-1].name == name and params[-1].default in (False, None)
+    assert any("check_geometry" in step.switches for step in postprocess.STEPS)
 
 
 def test_reference_on_pinned_cases():

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Wall clock of agdiff_amd.driver.run_job (plan, pack, topology, sample, save) on the first batches of the default job against
-the time its GPU sampling alone takes, with the next batch prepared in a worker process (default), a background thread
-(AGDIFF_PREPARE=thread) or inline (AGDIFF_PREPARE=inline).   python tools/job_wall.py [--batches 3] [--n-steps 600]"""
+the time its GPU sampling alone takes, with the next batch prepared in a background thread (the default), a worker process
+(AGDIFF_PREPARE=process) or inline (AGDIFF_PREPARE=inline).   python tools/job_wall.py [--batches 3] [--n-steps 600]"""
 import argparse, json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
