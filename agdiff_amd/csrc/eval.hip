@@ -36,6 +36,13 @@ __device__ __forceinline__ bool ag_atoms_in_range(int n, I... a) {
   return (((unsigned)a < (unsigned)n) && ...);
 }
 
+// the atoms [a0, a1) of graph g of a packed batch of N atoms: the walk of the one-wave-per-graph kernels is
+// for (a = a0 + lane; a < a1; a += 64).  Clamped to [0, N]: a graph_ptr that is not one touches nothing outside.
+__device__ __forceinline__ void ag_graph_span(const int32_t* __restrict__ graph_ptr, int g, int N, int& a0, int& a1) {
+  a0 = max(graph_ptr[g], 0);
+  a1 = min(graph_ptr[g + 1], N);
+}
+
 // neither Inf nor NaN
 __device__ __forceinline__ bool ag_finite(double x) { return fabs(x) <= 1.79769313486231570e308; }
 
@@ -212,7 +219,8 @@ __global__ void __launch_bounds__(64) k_traj_rmsd(const float* __restrict__ fram
                                                   float* __restrict__ out, float* __restrict__ out_mirror) {
   const int g = blockIdx.x, s = blockIdx.y, lane = threadIdx.x;
   const float* p = frames + (size_t)s * frame_stride;
-  const int a0 = max(graph_ptr[g], 0), a1 = min(graph_ptr[g + 1], N);       // (a graph_ptr that is not one reads nothing outside)
+  int a0, a1;
+  ag_graph_span(graph_ptr, g, N, a0, a1);
   double c[7] = {0, 0, 0, 0, 0, 0, 0};          // sums of the frame's and the target's selected atoms, and their number
   for (int a = a0 + lane; a < a1; a += 64) {
     if (!select[a]) continue;
@@ -496,7 +504,8 @@ __global__ void __launch_bounds__(64) k_hold_core(float* pos, const float* __res
     if (dev && lane == 0) dev[g] = nan;
     return;
   }
-  const int a0 = max(graph_ptr[g], 0), a1 = min(graph_ptr[g + 1], N);       // (a graph_ptr that is not one touches nothing outside)
+  int a0, a1;
+  ag_graph_span(graph_ptr, g, N, a0, a1);
   double c[7] = {0, 0, 0, 0, 0, 0, 0};            // sums of the core's and the template's selected atoms, and their number
   for (int a = a0 + lane; a < a1; a += 64) {
     if (!select[a]) continue;
@@ -554,6 +563,121 @@ __global__ void __launch_bounds__(64) k_hold_core(float* pos, const float* __res
     if (copy_out) { copy_out[o] = v0; copy_out[o + 1] = v1; copy_out[o + 2] = v2; }
   }
   if (dev && lane == 0) dev[g] = (float)sqrt(fmax((gsum - 2.0 * lam) / m, 0.0));
+}
+
+// Distance restraints of the sampler: flat-bottomed windows [lo, hi] on interatomic distances, k_hold_core's walk
+// over a packed batch with a gather over the by-atom table of validity.bounds_csr.  One row of that table, for atom a at x (fp64
+// from the stored fp32): worst = the largest |e| of the row, sum = sum s (-e) (x_a - x_b) / d over its entries, moved = some entry
+// contributed, bad = a coordinate or a distance that is not finite.  A partner outside the graph's atoms [a0, a1) is not read.
+__device__ __forceinline__ void ag_restrain_row(const float* pos, const double (&x)[3], bool a_fixed, int a0, int a1, int r0, int r1,
+                                                const int32_t* __restrict__ rs_idx, const float* __restrict__ rs_lo,
+                                                const float* __restrict__ rs_hi, const uint8_t* __restrict__ fixed, double (&sum)[3],
+                                                double& worst, bool& moved, bool& bad) {
+  bad = bad || !(ag_finite(x[0]) && ag_finite(x[1]) && ag_finite(x[2]));
+  for (int r = r0; r < r1; ++r) {
+    const int b = rs_idx[r];
+    if ((unsigned)(b - a0) >= (unsigned)(a1 - a0)) continue;
+    const size_t p = (size_t)3 * b;
+    const double dx = x[0] - pos[p], dy = x[1] - pos[p + 1], dz = x[2] - pos[p + 2];
+    const double d = sqrt(dx * dx + dy * dy + dz * dz);
+    if (!ag_finite(d)) { bad = true; continue; }
+    const double lo = rs_lo[r], hi = rs_hi[r];
+    const double e = d > hi ? d - hi : (d < lo ? d - lo : 0.0);
+    worst = fmax(worst, fabs(e));
+    if (e == 0.0 || d < 1e-12 || a_fixed) continue;
+    const double f = -((fixed && fixed[b]) ? 1.0 : 0.5) * e / d;
+    sum[0] += f * dx; sum[1] += f * dy; sum[2] += f * dz;
+    moved = true;
+  }
+}
+
+// One wave per graph, lanes striding over the graph's atoms in rounds of 64 (every lane makes every round: the ballots below are
+// wave-wide), each lane gathering the row of its own atom.  pos is read AND written in place, and a lane that strides to a later
+// atom must still read pre-sweep values (Jacobi): a sweep's new values wait in LDS, at the atom's ordinal among the graph's
+// restrained atoms, until every read of the sweep is done, and go out after the barrier.  A graph with skip[g] != 0, with a
+// restrained coordinate that is not finite or with more than AGDIFF_RESTRAIN_MAX_ATOMS restrained atoms is not written at all and
+// gets viol = NaN.  An atom whose row moved nothing keeps its bits.
+__global__ void __launch_bounds__(64) k_restrain_pairs(float* pos, const int32_t* __restrict__ graph_ptr, const int32_t* __restrict__ rs_ptr,
+                                                       const int32_t* __restrict__ rs_idx, const float* __restrict__ rs_lo,
+                                                       const float* __restrict__ rs_hi, const uint8_t* __restrict__ fixed,
+                                                       const int32_t* __restrict__ skip, int N, int R2, float weight, int sweeps,
+                                                       float* copy_out, float* __restrict__ viol) {
+  __shared__ float stage[3 * AGDIFF_RESTRAIN_MAX_ATOMS];
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float nan = __int_as_float(0x7fc00000);
+  if (skip && skip[g] != 0) {                     // (wave-uniform)
+    if (viol && lane == 0) viol[g] = nan;
+    return;
+  }
+  int a0, a1;
+  ag_graph_span(graph_ptr, g, N, a0, a1);
+  const uint64_t below = (1ull << lane) - 1ull;
+  double worst = 0.0;
+  bool bad = false;
+  int count = 0;
+  for (int base = a0; base < a1; base += 64) {    // the measure: nothing is written before it is complete
+    const int a = base + lane;
+    int r0 = 0, r1 = 0;
+    if (a < a1) { r0 = max(rs_ptr[a], 0); r1 = min(rs_ptr[a + 1], R2); }
+    const bool has = r1 > r0;
+    if (has) {
+      const size_t o = (size_t)3 * a;
+      const double x[3] = {pos[o], pos[o + 1], pos[o + 2]};
+      double sum[3] = {0, 0, 0};
+      bool moved = false;
+      ag_restrain_row(pos, x, true, a0, a1, r0, r1, rs_idx, rs_lo, rs_hi, fixed, sum, worst, moved, bad);
+    }
+    count += __popcll(__ballot(has));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
+  if (__ballot(bad) != 0 || count > AGDIFF_RESTRAIN_MAX_ATOMS) {            // (wave-uniform)
+    if (viol && lane == 0) viol[g] = nan;
+    return;
+  }
+  if (viol && lane == 0) viol[g] = (float)worst;
+  const double w = weight;
+  for (int s = 0; s < sweeps; ++s) {
+    int first = 0;                                // ordinal of the round's first restrained atom
+    for (int base = a0; base < a1; base += 64) {
+      const int a = base + lane;
+      int r0 = 0, r1 = 0;
+      if (a < a1) { r0 = max(rs_ptr[a], 0); r1 = min(rs_ptr[a + 1], R2); }
+      const bool has = r1 > r0;
+      const uint64_t m = __ballot(has);
+      if (has) {
+        const size_t o = (size_t)3 * a;
+        const float p0 = pos[o], p1 = pos[o + 1], p2 = pos[o + 2];
+        const double x[3] = {p0, p1, p2};
+        double sum[3] = {0, 0, 0}, unused = 0.0;
+        bool moved = false, ignored = false;
+        ag_restrain_row(pos, x, fixed && fixed[a], a0, a1, r0, r1, rs_idx, rs_lo, rs_hi, fixed, sum, unused, moved, ignored);
+        const double wc = w / (double)(r1 - r0);
+        const int k = 3 * (first + __popcll(m & below));
+        stage[k] = moved ? (float)(x[0] + wc * sum[0]) : p0;
+        stage[k + 1] = moved ? (float)(x[1] + wc * sum[1]) : p1;
+        stage[k + 2] = moved ? (float)(x[2] + wc * sum[2]) : p2;
+      }
+      first += __popcll(m);
+    }
+    __syncthreads();                              // every read of the sweep is done
+    const bool last = s == sweeps - 1;
+    first = 0;
+    for (int base = a0; base < a1; base += 64) {
+      const int a = base + lane;
+      const bool has = a < a1 && min(rs_ptr[a + 1], R2) > max(rs_ptr[a], 0);
+      const uint64_t m = __ballot(has);
+      if (has) {
+        const size_t o = (size_t)3 * a;
+        const int k = 3 * (first + __popcll(m & below));
+        const float v0 = stage[k], v1 = stage[k + 1], v2 = stage[k + 2];
+        pos[o] = v0; pos[o + 1] = v1; pos[o + 2] = v2;
+        if (last && copy_out) { copy_out[o] = v0; copy_out[o + 1] = v1; copy_out[o + 2] = v2; }
+      }
+      first += __popcll(m);
+    }
+    __syncthreads();                              // the next sweep reads what this one wrote
+  }
 }
 
 // ---- handedness: the sampler cannot tell a molecule from its mirror image (the score network sees distances only), so the RMSD
@@ -1783,6 +1907,22 @@ extern "C" int agdiff_hold_core(float* pos, const float* core_pos, const uint8_t
   if (copy_out == pos || core_pos == pos || (copy_out && copy_out == core_pos)) return AGDIFF_ERR_ARG;
   if (G == 0) return AGDIFF_OK;
   k_hold_core<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, core_pos, select, graph_ptr, skip, N, weight, copy_out, dev);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_restrain_pairs(float* pos, const int32_t* graph_ptr, const int32_t* rs_ptr, const int32_t* rs_idx, const float* rs_lo,
+                                     const float* rs_hi, const uint8_t* fixed, const int32_t* skip, int32_t G, int32_t N, int32_t R2,
+                                     int32_t max_restrained, float weight, int32_t sweeps, float* copy_out, float* viol, void* stream) {
+  if (!pos || !graph_ptr || !rs_ptr || G < 0 || N <= 0 || R2 < 0 || max_restrained < 0 || !(weight > 0.0f && weight <= 1.0f) ||
+      sweeps < 0 || sweeps > 16)
+    return AGDIFF_ERR_ARG;
+  if (R2 > 0 && (!rs_idx || !rs_lo || !rs_hi)) return AGDIFF_ERR_ARG;
+  if (copy_out == pos) return AGDIFF_ERR_ARG;
+  if (max_restrained > AGDIFF_RESTRAIN_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) return AGDIFF_OK;
+  k_restrain_pairs<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, graph_ptr, rs_ptr, rs_idx, rs_lo, rs_hi, fixed, skip, N, R2,
+                                                                           weight, sweeps, copy_out, viol);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

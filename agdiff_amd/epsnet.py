@@ -655,6 +655,16 @@ class DualEncoderEpsNetwork(nn.Module):
                            last step had pulled each core out of shape.  A graph without a selected atom is sampled freely.  Such
                            a run goes launch by launch (no fused front, no step graphs).  Nothing is put into the template's frame:
                            superpose the result on core_pos afterwards (driver.run_job(hold_core=True) does)
+          restraint_pairs  [R, 2] batch-level atom indices with restraint_lo / restraint_hi [R] (hi = inf: a lower bound only): sample
+                           under distance restraints (agdiff_amd/restraints.py).  After the update of every step with
+                           sigma < restraint_start_sigma (default inf: every step) restraint_sweeps (1 .. 16, default 1) Jacobi sweeps
+                           of agdiff_restrain_pairs pull every violated pair the fraction restraint_weight (in (0, 1], default 1) of
+                           the way onto its violated bound, before the core hold when a core is held too (its atoms stay; their
+                           partners take the whole step).  The launch after the last step always runs, at the given weight: a
+                           restraint is soft.  The run (begin_sampling) then has `restraint_viol`, after finish() a float32 host
+                           tensor [G]: each graph's largest violation in the returned positions (NaN for a quarantined graph).  Such
+                           a run goes launch by launch (no fused front, no step graphs); no pairs or an empty list: the run is what
+                           it is without the keywords
           traj_overlap_min_bytes  the trajectory goes to the host while the run samples when a poll interval's chunk
                            (nan_check_every x N x 12 B) is at least this large (default 16 MiB); else one copy at the end
         """
@@ -672,6 +682,9 @@ class DualEncoderEpsNetwork(nn.Module):
             from .core import core_arguments
             core_arguments(atom_type.shape[0], kwargs.get("core_pos"), kwargs.get("core_select"), kwargs.get("core_weight", 1.0),
                            kwargs.get("core_start_sigma", float("inf")))
+        from .restraints import SAMPLER_KEYWORDS, sampler_arguments
+        if any(k in kwargs for k in SAMPLER_KEYWORDS):                                       # (likewise)
+            sampler_arguments(atom_type.shape[0], batch, **{k: kwargs[k] for k in SAMPLER_KEYWORDS if k in kwargs})
         self._require_gpu()
         return LangevinRun(self, atom_type, pos_init, bond_index, bond_type, batch, num_graphs, extend_order,
                            n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global,
@@ -712,13 +725,17 @@ class LangevinRun:
                  save_traj=True, skip_discarded_global=True, nan_check_every=64, step_indices=None, on_step=None,
                  extend_radius=True, raise_on_nan=True, noise_mode="chunked", traj_overlap_min_bytes=16 << 20, topology=None,
                  noise_seed=None, stream_ids=None, *, rmsd_target=None, rmsd_select=None, rmsd_mirror=False, core_pos=None,
-                 core_select=None, core_weight=1.0, core_start_sigma=float("inf"), **_ignored):
+                 core_select=None, core_weight=1.0, core_start_sigma=float("inf"), restraint_pairs=None, restraint_lo=None,
+                 restraint_hi=None, restraint_weight=1.0, restraint_start_sigma=float("inf"), restraint_sweeps=1, **_ignored):
         if noise_mode not in ("chunked", "per_step", "counter"):
             raise ValueError("noise_mode must be 'chunked', 'per_step' or 'counter'")
         if noise_mode == "counter" and (noise_seed is None or stream_ids is None):
             raise ValueError("noise_mode='counter' needs noise_seed (int) and stream_ids (int64 [num_graphs])")
         from .core import core_arguments
+        from .restraints import sampler_arguments
         core = core_arguments(atom_type.shape[0], core_pos, core_select, core_weight, core_start_sigma)
+        restr = sampler_arguments(atom_type.shape[0], batch, restraint_pairs, restraint_lo, restraint_hi, restraint_weight,
+                                  restraint_start_sigma, restraint_sweeps)
         self.model, self.lib = model, _lib.load()
         dev = model._device()
         self.sigmas = ((1.0 - model.alphas).sqrt() / model.alphas.sqrt()).detach().cpu()
@@ -769,6 +786,18 @@ class LangevinRun:
             tpl, sel, self._core_weight, self._core_start = core
             self._core = (torch.from_numpy(tpl).to(dev), torch.from_numpy(sel).to(dev))
             self._core_dev = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
+        # restraint_pairs [R, 2] + restraint_lo / restraint_hi [R]: distance restraints (agdiff_amd/restraints.py).
+        # After the update of every step with sigma < restraint_start_sigma one agdiff_restrain_pairs launch of restraint_sweeps
+        # sweeps pulls the violated pairs towards their windows, in self.pos and in the frame the update has just written, BEFORE the
+        # core hold (whose atoms it leaves where they are: fixed = core_select); the launch after the run's last step always runs, at
+        # the given weight (a restraint is soft), and one measuring launch after the closing hold leaves `restraint_viol` [G]: each
+        # graph's largest violation in what the run returns (on the host after finish(); NaN for a quarantined graph).  Launch by
+        # launch, like a run that holds a core (_fused_front).  No pairs: nothing of this exists and the run is what it was.
+        self._restr, self.restraint_viol = None, None
+        if restr is not None:
+            rs_ptr, rs_idx, rs_lo, rs_hi, self._restr_most, self._restr_weight, self._restr_start, self._restr_sweeps = restr
+            self._restr = tuple(torch.from_numpy(x).to(dev) for x in (rs_ptr, rs_idx, rs_lo, rs_hi))
+            self._restr_viol = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
         self.noise, self.on_step = noise, on_step
         self.step_lr, self.global_start_sigma = step_lr, global_start_sigma
         self.skip_discarded, self.nan_every = bool(skip_discarded_global), int(nan_check_every)
@@ -807,7 +836,7 @@ class LangevinRun:
         self._use_graphs = bool((sg is True or (sg == "auto" and N <= model.STEP_GRAPH_MAX_NODES)) and on_step is None and
                                 noise_mode == "chunked" and self.pk.poly_kt > 0 and getattr(model, "fused_front", True) and
                                 not getattr(model, "front_split_graph", False) and not self.topo.large and self._rmsd is None and
-                                self._core is None)
+                                self._core is None and self._restr is None)
         self._graphs, self._step_table, self._step_index, self._dev_index = {}, None, None, None
         # (a capture needs a stream of its own: the legacy default stream, which torch hands out as the current one, cannot be captured)
         self._gstream = torch.cuda.Stream(device=dev) if self._use_graphs else None
@@ -873,9 +902,11 @@ class LangevinRun:
         radius graph of step t + 1): whenever the radius edges have their polynomials and the graph is built here.  Not for a
         batch with a molecule of more than AGDIFF_MAX_ATOMS_PER_GRAPH atoms (topo.large): agdiff_sampler_front keeps a
         molecule's masks in LDS; such a batch runs update, graph build (agdiff_graph_build_large) and forward launch by launch,
-        and with them no step graphs (they replay the fused front).  Nor for a run that holds a core: agdiff_hold_core has to run
-        between a step's update and the next step's radius graph, which agdiff_sampler_front does in one launch."""
-        return self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large and self._core is None
+        and with them no step graphs (they replay the fused front).  Nor for a run that holds a core or restrains distances:
+        agdiff_hold_core / agdiff_restrain_pairs have to run between a step's update and the next step's radius graph, which
+        agdiff_sampler_front does in one launch."""
+        return (self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large and self._core is None and
+                self._restr is None)
 
     def _fill_args(self, a, k, dev, N):
         sig, step_size, noise_scale, use_global = self._sched[k]
@@ -1051,8 +1082,12 @@ class LangevinRun:
                 self._stage0_done = self._stage0_done or bool(run_global)
                 _lib.check(lib.agdiff_langevin_update(ctypes.byref(topo.struct), ctypes.byref(ws.struct),
                                                       ctypes.byref(a), stream), "agdiff_langevin_update")
+                if self._restr is not None:
+                    self._restrain(k, sig)
                 if self._core is not None:
                     self._hold_core(k, sig)
+                if self._restr is not None and k == len(self.steps) - 1:
+                    self._restrain_launch(0, None)                   # what is left in what the run returns
                 self.k += 1
                 self._traj_ready = self.k
                 if self.on_step is not None:
@@ -1074,6 +1109,23 @@ class LangevinRun:
         _lib.check(self.lib.agdiff_hold_core(self.pos_p, _lib.ptr(tpl), _lib.ptr(sel), _lib.ptr(self.topo.graph_ptr), skip, G, self.topo.N,
                                              1.0 if last else self._core_weight, self._traj_row(k), _lib.ptr(self._core_dev),
                                              _lib.stream_ptr()), "agdiff_hold_core")
+
+    def _restrain(self, k, sigma):
+        """The restraint launch after the update of step k (launch-by-launch path only), before the core hold: for a step with
+        sigma < restraint_start_sigma, and after the LAST step of the schedule whatever sigma says, at the given weight."""
+        if k == len(self.steps) - 1 or sigma < self._restr_start:
+            self._restrain_launch(self._restr_sweeps, self._traj_row(k))
+
+    def _restrain_launch(self, sweeps, copy_out):
+        """One agdiff_restrain_pairs launch on the current stream over self.pos: `sweeps` sweeps (0: only measures), the atoms of a
+        held core fixed, the graphs the update kernels have quarantined skipped (ws.nan_flag[1:]), viol -> restraint_viol."""
+        rs_ptr, rs_idx, rs_lo, rs_hi = self._restr
+        fixed = _lib.ptr(self._core[1]) if self._core is not None else ctypes.c_void_p(0)
+        skip = ctypes.c_void_p(self.ws.nan_flag.data_ptr() + 4)          # (element 0 is the "any graph" flag)
+        _lib.check(self.lib.agdiff_restrain_pairs(self.pos_p, _lib.ptr(self.topo.graph_ptr), _lib.ptr(rs_ptr), _lib.ptr(rs_idx), _lib.ptr(rs_lo),
+                                                  _lib.ptr(rs_hi), fixed, skip, self.topo.G, self.topo.N, int(rs_idx.shape[0]),
+                                                  self._restr_most, self._restr_weight, int(sweeps), copy_out, _lib.ptr(self._restr_viol),
+                                                  _lib.stream_ptr()), "agdiff_restrain_pairs")
 
     def check_nan(self):
         """dualenc.py:539-541.  ws.nan_flag[0] is set by the update kernel as soon as any position is NaN.  Polled every
@@ -1170,6 +1222,9 @@ class LangevinRun:
             self.rmsd_curve, self.rmsd_curve_mirror = curves
         if self._core is not None:
             self.core_dev = self._core_dev.cpu()
+        if self._restr is not None:
+            self.restraint_viol = self._restr_viol.cpu()
+            self.restraint_viol[self.nan_graphs()] = float("nan")        # (also a graph that left the range at the very last poll)
         if self.traj is not None and self._traj_overlap:
             self._traj_send(self.k)
             self._traj_land()

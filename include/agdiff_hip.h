@@ -51,6 +51,8 @@ extern "C" {
 #define AGDIFF_FLATTEN_MAX_GROUPS 192 /* most planar groups of agdiff_relax_planar: one group per thread of the 256, and six fp64 per
                                          group in LDS (9 KB) next to agdiff_relax_bounds' 52 KB -- 61 KB of the 64 KB of static LDS;
                                          256 groups would not fit */
+#define AGDIFF_RESTRAIN_MAX_ATOMS 1024 /* most restrained atoms of ONE graph in agdiff_restrain_pairs: a sweep's new values wait in LDS
+                                          (12 KB of fp32) until every read of the sweep is done */
 #define AGDIFF_MMD_MAX_CONFS 8192 /* most reference + generated conformers of agdiff_mmd_single: one column of them is 32 KB of LDS */
 #define AGDIFF_POLY_MAX_KT 4      /* most 32-term k-tiles of the radius-edge filter polynomial (degree 127): 1, 2 what smooth
                                       checkpoints take; 3, 4 the rungs between them and the filter MLPs for sharp ones */
@@ -1079,6 +1081,51 @@ int agdiff_hold_core(float* pos /* [N][3], in place */, const float* core_pos /*
                      const int32_t* graph_ptr /* [G + 1] */, const int32_t* skip /* [G] or null: != 0 leaves the graph alone */,
                      int32_t G, int32_t N, float weight /* (0, 1] */, float* copy_out /* [N][3] or null */,
                      float* dev /* [G] or null */, void* stream);
+
+/* ---- distance restraints ---------------------------------------------------------------------------------------------------
+ * Conformers under distance restraints (a macrocycle or staple closure, an NOE contact, a pharmacophore distance, a lower bound
+ * that keeps the ensemble extended): epsnet.LangevinRun calls this after a step's update, before agdiff_hold_core when a core is
+ * held too, so that the network relaxes the rest of the molecule around the restraint (agdiff_amd/restraints.py).
+ *
+ * agdiff_restrain_pairs: flat-bottomed windows [lo, hi] on interatomic distances of a packed batch, in place.
+ *   pos [N][3]             a packed batch, read and written
+ *   graph_ptr [G + 1]      first atom of every graph (agdiff_topo_t.graph_ptr); entries are clamped to [0, N]
+ *   rs_ptr [N + 1], rs_idx [R2], rs_lo [R2], rs_hi [R2]
+ *                          the by-atom table over the batch's atoms, exactly validity.bounds_csr(N, pairs, lo, hi) with batch-level
+ *                          atom indices (R2 = 2 R entries for R pairs): row a = rs_ptr[a] .. rs_ptr[a + 1] lists (partner b, lo, hi)
+ *                          for every pair of atom a, every pair once in the row of each of its two atoms, rows in the order of the
+ *                          pair list; a pair listed twice counts twice.  The HOST checks 0 <= lo <= hi (hi may be +inf: a lower
+ *                          bound only), no NaN, a != b, both atoms in the same graph; here a partner outside the graph's atoms is
+ *                          skipped unread and row bounds are clamped to [0, R2].  rs_idx / rs_lo / rs_hi may be null for R2 == 0.
+ *   fixed [N] uint8 or null   1 = the atom is not moved by a sweep (a held core's atoms); its partners take the whole step
+ *   skip [G] int32 or null != 0: the graph is left alone (agdiff_ws_t.nan_flag + 1)
+ *   max_restrained         the largest number of atoms with a row in one graph of the batch, <= AGDIFF_RESTRAIN_MAX_ATOMS (else
+ *                          AGDIFF_ERR_LIMIT, before any launch); a graph that has more all the same is left alone, viol = NaN
+ *   weight w               in (0, 1], else AGDIFF_ERR_ARG
+ *   sweeps                 in [0, 16], else AGDIFF_ERR_ARG; 0 moves nothing and only measures
+ *   copy_out [N][3] or null  the values of the last sweep written to pos[a], for the atoms with a row, go to copy_out[a] too (the
+ *                          trajectory frame); no other entry is touched; untouched when sweeps == 0.  Not pos.
+ *   viol [G] or null       the largest |e| over the graph's rows BEFORE the first sweep; 0 for a graph without restraints
+ * One sweep, for atom a with a row of length c_a > 0, all positions read as they were before the sweep (Jacobi), in fp64 from the
+ * stored fp32.  For each row entry (b, lo, hi):
+ *   d = |x_a - x_b|;   e = d - hi if d > hi, d - lo if d < lo, else 0
+ *   s = 0 if fixed[a], 1 if fixed[b], else 1/2 (the share of atom a)
+ *   an entry with d < 1e-12 or d not finite moves nothing in that sweep
+ * then x_a <- x_a + (w / c_a) sum s (-e) (x_a - x_b) / d, rounded to fp32 once per sweep; an atom none of whose entries
+ * contributes keeps its bits.  The division by the STATIC row length c_a keeps the rule continuous in the positions and stable for
+ * an atom with many restraints for any w in (0, 1]; a single pair with w = 1 and both ends free lands exactly on its violated
+ * bound and keeps the pair's centroid (a sweep with a fixed end moves it).  Atoms with an empty row are not written; atoms of a
+ * graph whose restraints are all satisfied keep their bytes.  Positions pass through fp32 between sweeps: that rounding is part of
+ * the rule.  A graph with skip[g] != 0, or with a restrained atom (or partner) whose coordinate is not finite, is not written at all
+ * and gets viol[g] = NaN.  One 64-lane wave per graph, lanes striding over the graph's atoms and gathering their own rows: any
+ * number of atoms per graph.  A sweep's new values wait in LDS until every read of the sweep is done.  No atomics, deterministic bit
+ * for bit. */
+int agdiff_restrain_pairs(float* pos /* [N][3], in place */, const int32_t* graph_ptr /* [G + 1] */, const int32_t* rs_ptr /* [N + 1] */,
+                          const int32_t* rs_idx /* [R2] */, const float* rs_lo /* [R2] */, const float* rs_hi /* [R2] */,
+                          const uint8_t* fixed /* [N] or null */, const int32_t* skip /* [G] or null: != 0 leaves the graph alone */,
+                          int32_t G, int32_t N, int32_t R2, int32_t max_restrained, float weight /* (0, 1] */,
+                          int32_t sweeps /* [0, 16] */, float* copy_out /* [N][3] or null */, float* viol /* [G] or null */,
+                          void* stream);
 
 /* ---- distance-distribution MMD -----------------------------------------------------------------------------------------
  * The maximum mean discrepancy between the interatomic-distance distributions of the generated and the reference conformers of
