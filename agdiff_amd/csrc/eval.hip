@@ -680,6 +680,128 @@ __global__ void __launch_bounds__(64) k_restrain_pairs(float* pos, const int32_t
   }
 }
 
+// Torsion restraints of the sampler: circular windows centre +- half on dihedrals.  The dihedral of the quad
+// (a, u, v, b) with k_torsion_angles' arithmetic (fp64 from the fp32 positions), for batch-level atoms of the graph [a0, a1):
+// 0 = an angle, 1 = degenerate (an atom outside the graph, which reads nothing, or a zero normal), 2 = a coordinate that is not
+// finite.  pu, pv: the axis ends, for the rotation.
+__device__ __forceinline__ int ag_quad_angle(const float* pos, int a0, int a1, int a, int u, int v, int b, double& theta, double (&pu)[3],
+                                             double (&pv)[3]) {
+  theta = (double)NAN;
+  const unsigned n = (unsigned)(a1 - a0);
+  if ((unsigned)(a - a0) >= n || (unsigned)(u - a0) >= n || (unsigned)(v - a0) >= n || (unsigned)(b - a0) >= n) return 1;
+  const size_t oa = (size_t)3 * a, ou = (size_t)3 * u, ov = (size_t)3 * v, ob = (size_t)3 * b;
+  const double ax = pos[oa], ay = pos[oa + 1], az = pos[oa + 2];
+  pu[0] = pos[ou]; pu[1] = pos[ou + 1]; pu[2] = pos[ou + 2];
+  pv[0] = pos[ov]; pv[1] = pos[ov + 1]; pv[2] = pos[ov + 2];
+  const double bx = pos[ob], by = pos[ob + 1], bz = pos[ob + 2];
+  if (!(ag_finite(ax) && ag_finite(ay) && ag_finite(az) && ag_finite(pu[0]) && ag_finite(pu[1]) && ag_finite(pu[2]) &&
+        ag_finite(pv[0]) && ag_finite(pv[1]) && ag_finite(pv[2]) && ag_finite(bx) && ag_finite(by) && ag_finite(bz)))
+    return 2;
+  const double b1x = pu[0] - ax, b1y = pu[1] - ay, b1z = pu[2] - az;
+  const double b2x = pv[0] - pu[0], b2y = pv[1] - pu[1], b2z = pv[2] - pu[2];
+  const double b3x = bx - pv[0], b3y = by - pv[1], b3z = bz - pv[2];
+  const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
+  const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
+  const double n1sq = n1x * n1x + n1y * n1y + n1z * n1z, n2sq = n2x * n2x + n2y * n2y + n2z * n2z;
+  if (!(n1sq > 0.0 && n2sq > 0.0)) return 1;
+  const double y = sqrt(b2x * b2x + b2y * b2y + b2z * b2z) * (b1x * n2x + b1y * n2y + b1z * n2z);
+  const double x = n1x * n2x + n1y * n2y + n1z * n2z;
+  theta = atan2(y, x);
+  return 0;
+}
+
+// the excess of theta over the circular window centre +- half: 0 inside, else Delta - sign(Delta) half with Delta = theta - centre
+// wrapped into [-pi, pi] (|centre| <= pi on the host, so one turn either way is enough)
+__device__ __forceinline__ double ag_window_excess(double theta, double centre, double half) {
+  const double pi = 3.141592653589793238462;
+  double d = theta - centre;
+  if (d > pi) d -= 2.0 * pi;
+  else if (d < -pi) d += 2.0 * pi;
+  if (fabs(d) <= half) return 0.0;
+  return d > 0.0 ? d - half : d + half;
+}
+
+// One wave per graph of a packed batch.  The measure: lanes stride over the graph's restraints, nothing is written to pos before
+// it is complete; a graph with skip[g] != 0 or with a quad coordinate that is not finite is not written at all, viol = NaN (and
+// its angles NaN).  Then, with turn != 0, the wave walks the restraints in row order as k_flip_double_bonds walks its bonds: every
+// lane computes the quad (the same loads in every lane, so the decision is wave-uniform), lane 0 stores the angle as it is when
+// the restraint's turn comes, and a violated restraint with a side row has that row's atoms -- offsets from the graph's first
+// atom, so every conformer of a molecule shares the row -- turned by phi = -weight e about the axis through p_v along
+// k = (p_v - p_u) / |p_v - p_u|: r' = r cos phi + (k x r) sin phi + k (k . r) (1 - cos phi), r = p - p_v, in fp64, rounded to
+// fp32 once.  u and v lie on the axis and are skipped; so are an offset outside the graph and an atom with a coordinate that is
+// not finite.  pos is read AND written through one pointer (neither const nor __restrict__): within one restraint every
+// coordinate is read and written by the same lane, the quad's loads come before the stores in the wave's program order, and a
+// workgroup barrier after a rotation (wave-uniform) makes it visible to the next restraint's loads.  The workgroup is ONE wave.
+__global__ void __launch_bounds__(64) k_restrain_torsions(float* pos, const int32_t* __restrict__ graph_ptr, const int32_t* __restrict__ tr_ptr,
+                                                          const int32_t* __restrict__ quads, const float* __restrict__ centre,
+                                                          const float* __restrict__ half, const int32_t* __restrict__ side_row,
+                                                          const int32_t* __restrict__ side_ptr, const int32_t* __restrict__ side_idx,
+                                                          const int32_t* __restrict__ skip, int N, int T, int S, float weight, int turn,
+                                                          float* copy_out, float* __restrict__ angle, float* __restrict__ viol) {
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float nan = __int_as_float(0x7fc00000);
+  int a0, a1;
+  ag_graph_span(graph_ptr, g, N, a0, a1);
+  const int t0 = max(tr_ptr[g], 0), t1 = min(tr_ptr[g + 1], T);
+  const bool skipped = skip && skip[g] != 0;      // (wave-uniform)
+  double worst = 0.0, pu[3], pv[3];
+  bool bad = false;
+  if (!skipped) {
+    for (int t = t0 + lane; t < t1; t += 64) {    // the measure
+      double theta;
+      const int st = ag_quad_angle(pos, a0, a1, quads[4 * t], quads[4 * t + 1], quads[4 * t + 2], quads[4 * t + 3], theta, pu, pv);
+      bad = bad || st == 2;
+      if (st == 0) worst = fmax(worst, fabs(ag_window_excess(theta, centre[t], half[t])));
+      if (angle && !turn) angle[t] = (float)theta;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
+  }
+  if (skipped || __ballot(bad) != 0) {            // (wave-uniform)
+    if (lane == 0) viol[g] = nan;
+    if (angle)
+      for (int t = t0 + lane; t < t1; t += 64) angle[t] = nan;
+    return;
+  }
+  if (lane == 0) viol[g] = (float)worst;
+  if (!turn) return;
+  const int send = (S > 0 && side_ptr && side_idx) ? side_ptr[S] : 0;
+  const double w = weight;
+  for (int t = t0; t < t1; ++t) {
+    const int u = quads[4 * t + 1], v = quads[4 * t + 2];
+    double theta;
+    const int st = ag_quad_angle(pos, a0, a1, quads[4 * t], u, v, quads[4 * t + 3], theta, pu, pv);
+    if (angle && lane == 0) angle[t] = (float)theta;
+    if (st != 0) continue;
+    const double e = ag_window_excess(theta, centre[t], half[t]);
+    const int row = side_row[t];
+    if (e == 0.0 || (unsigned)row >= (unsigned)S) continue;
+    const int s0 = max(side_ptr[row], 0), s1 = min(side_ptr[row + 1], send);
+    if (s1 <= s0) continue;                       // (all of these wave-uniform; the normals are not zero here, so |p_v - p_u| > 0)
+    const double kx0 = pv[0] - pu[0], ky0 = pv[1] - pu[1], kz0 = pv[2] - pu[2];
+    const double inv = 1.0 / sqrt(kx0 * kx0 + ky0 * ky0 + kz0 * kz0);
+    const double kx = kx0 * inv, ky = ky0 * inv, kz = kz0 * inv;
+    double sn, cs;
+    sincos(-w * e, &sn, &cs);
+    for (int k = s0 + lane; k < s1; k += 64) {
+      const int off = side_idx[k];
+      if ((unsigned)off >= (unsigned)(a1 - a0)) continue;
+      const int m = a0 + off;
+      if (m == u || m == v) continue;
+      const size_t o = (size_t)3 * m;
+      const double rx = (double)pos[o] - pv[0], ry = (double)pos[o + 1] - pv[1], rz = (double)pos[o + 2] - pv[2];
+      if (!(ag_finite(rx) && ag_finite(ry) && ag_finite(rz))) continue;
+      const double kr = (kx * rx + ky * ry + kz * rz) * (1.0 - cs);
+      const float v0 = (float)(pv[0] + rx * cs + (ky * rz - kz * ry) * sn + kx * kr);
+      const float v1 = (float)(pv[1] + ry * cs + (kz * rx - kx * rz) * sn + ky * kr);
+      const float v2 = (float)(pv[2] + rz * cs + (kx * ry - ky * rx) * sn + kz * kr);
+      pos[o] = v0; pos[o + 1] = v1; pos[o + 2] = v2;
+      if (copy_out) { copy_out[o] = v0; copy_out[o + 1] = v1; copy_out[o + 2] = v2; }
+    }
+    __syncthreads();
+  }
+}
+
 // ---- handedness: the sampler cannot tell a molecule from its mirror image (the score network sees distances only), so the RMSD
 // to the mirror image, the parity of the stereocentres and the inversion of a wrong-handed conformer live here ----------------
 
@@ -1923,6 +2045,22 @@ extern "C" int agdiff_restrain_pairs(float* pos, const int32_t* graph_ptr, const
   if (G == 0) return AGDIFF_OK;
   k_restrain_pairs<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, graph_ptr, rs_ptr, rs_idx, rs_lo, rs_hi, fixed, skip, N, R2,
                                                                            weight, sweeps, copy_out, viol);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_restrain_torsions(float* pos, const int32_t* graph_ptr, const int32_t* tr_ptr, const int32_t* quads, const float* centre,
+                                        const float* half, const int32_t* side_row, const int32_t* side_ptr, const int32_t* side_idx,
+                                        const int32_t* skip, int32_t G, int32_t N, int32_t T, int32_t S, float weight, int32_t turn,
+                                        float* copy_out, float* angle, float* viol, void* stream) {
+  if (!pos || !graph_ptr || !tr_ptr || !viol || G < 0 || N <= 0 || T < 0 || S < 0 || !(weight > 0.0f && weight <= 1.0f))
+    return AGDIFF_ERR_ARG;
+  if (T > 0 && (!quads || !centre || !half || !side_row)) return AGDIFF_ERR_ARG;
+  if (S > 0 && !side_ptr) return AGDIFF_ERR_ARG;
+  if (copy_out == pos) return AGDIFF_ERR_ARG;
+  if (G == 0) return AGDIFF_OK;
+  k_restrain_torsions<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, graph_ptr, tr_ptr, quads, centre, half, side_row, side_ptr,
+                                                                              side_idx, skip, N, T, S, weight, turn, copy_out, angle, viol);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

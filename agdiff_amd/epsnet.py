@@ -665,6 +665,19 @@ class DualEncoderEpsNetwork(nn.Module):
                            tensor [G]: each graph's largest violation in the returned positions (NaN for a quarantined graph).  Such
                            a run goes launch by launch (no fused front, no step graphs); no pairs or an empty list: the run is what
                            it is without the keywords
+          torsion_quads    [T, 4] batch-level atoms (a, u, v, b), graph by graph, with torsion_target / torsion_tol [T] in radians:
+                           sample under torsion restraints (agdiff_amd/torsion_restraints.py).  After the update of
+                           every step with sigma < torsion_start_sigma (default inf: every step) one agdiff_restrain_torsions launch
+                           turns one side of every bond whose dihedral lies outside target +- tol the fraction torsion_weight (in
+                           (0, 1], default 1) of the way onto the violated edge, after the distance restraints and before the core
+                           hold (with a core held, the side without a core atom turns; a bond with core atoms on both sides is only
+                           measured).  torsion_sides: (side_row, side_ptr, side_idx) as torsion_restraints.pack_torsion_restraints
+                           returns them with the quads; without it the sides come from the batch's bonds, once per distinct
+                           topology.  The launch after the last step always runs, at the given weight.  The run (begin_sampling)
+                           then has `torsion_viol` [G] and `torsion_angle` [T], after finish() float32 host tensors: each graph's
+                           largest excess and each dihedral in the returned positions (NaN for a quarantined graph).  Launch by
+                           launch, like a run under distance restraints; no quads or an empty list: the run is what it is without
+                           the keywords
           traj_overlap_min_bytes  the trajectory goes to the host while the run samples when a poll interval's chunk
                            (nan_check_every x N x 12 B) is at least this large (default 16 MiB); else one copy at the end
         """
@@ -685,6 +698,11 @@ class DualEncoderEpsNetwork(nn.Module):
         from .restraints import SAMPLER_KEYWORDS, sampler_arguments
         if any(k in kwargs for k in SAMPLER_KEYWORDS):                                       # (likewise)
             sampler_arguments(atom_type.shape[0], batch, **{k: kwargs[k] for k in SAMPLER_KEYWORDS if k in kwargs})
+        from . import torsion_restraints
+        if any(k in kwargs for k in torsion_restraints.SAMPLER_KEYWORDS):                    # (likewise)
+            torsion_restraints.sampler_arguments(atom_type.shape[0], batch, bond_index=bond_index, bond_type=bond_type,
+                                                 frozen=kwargs.get("core_select"), num_graphs=num_graphs,
+                                                 **{k: kwargs[k] for k in torsion_restraints.SAMPLER_KEYWORDS if k in kwargs})
         self._require_gpu()
         return LangevinRun(self, atom_type, pos_init, bond_index, bond_type, batch, num_graphs, extend_order,
                            n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global,
@@ -726,7 +744,9 @@ class LangevinRun:
                  extend_radius=True, raise_on_nan=True, noise_mode="chunked", traj_overlap_min_bytes=16 << 20, topology=None,
                  noise_seed=None, stream_ids=None, *, rmsd_target=None, rmsd_select=None, rmsd_mirror=False, core_pos=None,
                  core_select=None, core_weight=1.0, core_start_sigma=float("inf"), restraint_pairs=None, restraint_lo=None,
-                 restraint_hi=None, restraint_weight=1.0, restraint_start_sigma=float("inf"), restraint_sweeps=1, **_ignored):
+                 restraint_hi=None, restraint_weight=1.0, restraint_start_sigma=float("inf"), restraint_sweeps=1, torsion_quads=None,
+                 torsion_target=None, torsion_tol=None, torsion_sides=None, torsion_weight=1.0, torsion_start_sigma=float("inf"),
+                 **_ignored):
         if noise_mode not in ("chunked", "per_step", "counter"):
             raise ValueError("noise_mode must be 'chunked', 'per_step' or 'counter'")
         if noise_mode == "counter" and (noise_seed is None or stream_ids is None):
@@ -736,6 +756,12 @@ class LangevinRun:
         core = core_arguments(atom_type.shape[0], core_pos, core_select, core_weight, core_start_sigma)
         restr = sampler_arguments(atom_type.shape[0], batch, restraint_pairs, restraint_lo, restraint_hi, restraint_weight,
                                   restraint_start_sigma, restraint_sweeps)
+        from . import torsion_restraints
+        tors = torsion_restraints.sampler_arguments(atom_type.shape[0], batch, torsion_quads, torsion_target, torsion_tol, torsion_sides,
+                                                    torsion_weight, torsion_start_sigma, bond_index=bond_index, bond_type=bond_type,
+                                                    frozen=None if core is None else core[1], num_graphs=num_graphs)
+        if tors is not None and tors[4] is None:
+            raise ValueError("torsion restraints need the batch's bonds (bond_index, bond_type) or a side table (torsion_sides)")
         self.model, self.lib = model, _lib.load()
         dev = model._device()
         self.sigmas = ((1.0 - model.alphas).sqrt() / model.alphas.sqrt()).detach().cpu()
@@ -798,6 +824,21 @@ class LangevinRun:
             rs_ptr, rs_idx, rs_lo, rs_hi, self._restr_most, self._restr_weight, self._restr_start, self._restr_sweeps = restr
             self._restr = tuple(torch.from_numpy(x).to(dev) for x in (rs_ptr, rs_idx, rs_lo, rs_hi))
             self._restr_viol = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
+        # torsion_quads [T, 4] + torsion_target / torsion_tol [T]: torsion restraints (agdiff_amd/torsion_restraints.py, DESIGN.md
+        # 4.19).  After the update of every step with sigma < torsion_start_sigma one agdiff_restrain_torsions launch turns one side of
+        # every violated bond towards its window, in self.pos and in the frame the update has just written, AFTER the distance
+        # restraints and BEFORE the core hold (the sides avoid the core's atoms: frozen = core_select); the launch after the run's
+        # last step always runs, at the given weight, and one measuring launch after the closing hold leaves `torsion_viol` [G] and
+        # `torsion_angle` [T]: what is left in what the run returns (on the host after finish()).  Launch by launch (_fused_front).
+        self._tors, self.torsion_viol, self.torsion_angle = None, None, None
+        if tors is not None:
+            tr_ptr, quads, centre, half, (side_row, side_ptr, side_idx), self._tors_weight, self._tors_start = tors
+            self._tors_S = int(side_ptr.shape[0]) - 1
+            self._tors_graph = np.repeat(np.arange(tr_ptr.shape[0] - 1), np.diff(tr_ptr))
+            self._tors = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (tr_ptr, quads, centre, half, side_row, side_ptr))
+            self._tors += (torch.from_numpy(np.ascontiguousarray(side_idx)).to(dev) if side_idx.size else None,)
+            self._tors_viol = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
+            self._tors_angle = torch.full((int(quads.shape[0]),), float("nan"), dtype=torch.float32, device=dev)
         self.noise, self.on_step = noise, on_step
         self.step_lr, self.global_start_sigma = step_lr, global_start_sigma
         self.skip_discarded, self.nan_every = bool(skip_discarded_global), int(nan_check_every)
@@ -836,7 +877,7 @@ class LangevinRun:
         self._use_graphs = bool((sg is True or (sg == "auto" and N <= model.STEP_GRAPH_MAX_NODES)) and on_step is None and
                                 noise_mode == "chunked" and self.pk.poly_kt > 0 and getattr(model, "fused_front", True) and
                                 not getattr(model, "front_split_graph", False) and not self.topo.large and self._rmsd is None and
-                                self._core is None and self._restr is None)
+                                self._core is None and self._restr is None and self._tors is None)
         self._graphs, self._step_table, self._step_index, self._dev_index = {}, None, None, None
         # (a capture needs a stream of its own: the legacy default stream, which torch hands out as the current one, cannot be captured)
         self._gstream = torch.cuda.Stream(device=dev) if self._use_graphs else None
@@ -902,11 +943,11 @@ class LangevinRun:
         radius graph of step t + 1): whenever the radius edges have their polynomials and the graph is built here.  Not for a
         batch with a molecule of more than AGDIFF_MAX_ATOMS_PER_GRAPH atoms (topo.large): agdiff_sampler_front keeps a
         molecule's masks in LDS; such a batch runs update, graph build (agdiff_graph_build_large) and forward launch by launch,
-        and with them no step graphs (they replay the fused front).  Nor for a run that holds a core or restrains distances:
-        agdiff_hold_core / agdiff_restrain_pairs have to run between a step's update and the next step's radius graph, which
-        agdiff_sampler_front does in one launch."""
+        and with them no step graphs (they replay the fused front).  Nor for a run that holds a core or restrains distances or
+        torsions: agdiff_hold_core / agdiff_restrain_pairs / agdiff_restrain_torsions have to run between a step's update and the
+        next step's radius graph, which agdiff_sampler_front does in one launch."""
         return (self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large and self._core is None and
-                self._restr is None)
+                self._restr is None and self._tors is None)
 
     def _fill_args(self, a, k, dev, N):
         sig, step_size, noise_scale, use_global = self._sched[k]
@@ -1084,10 +1125,14 @@ class LangevinRun:
                                                       ctypes.byref(a), stream), "agdiff_langevin_update")
                 if self._restr is not None:
                     self._restrain(k, sig)
+                if self._tors is not None:
+                    self._restrain_torsions(k, sig)
                 if self._core is not None:
                     self._hold_core(k, sig)
                 if self._restr is not None and k == len(self.steps) - 1:
                     self._restrain_launch(0, None)                   # what is left in what the run returns
+                if self._tors is not None and k == len(self.steps) - 1:
+                    self._torsion_launch(0, None)                    # likewise
                 self.k += 1
                 self._traj_ready = self.k
                 if self.on_step is not None:
@@ -1126,6 +1171,24 @@ class LangevinRun:
                                                   _lib.ptr(rs_hi), fixed, skip, self.topo.G, self.topo.N, int(rs_idx.shape[0]),
                                                   self._restr_most, self._restr_weight, int(sweeps), copy_out, _lib.ptr(self._restr_viol),
                                                   _lib.stream_ptr()), "agdiff_restrain_pairs")
+
+    def _restrain_torsions(self, k, sigma):
+        """The torsion launch after the update of step k (launch-by-launch path only), after the distance restraints and before the
+        core hold: for a step with sigma < torsion_start_sigma, and after the LAST step of the schedule whatever sigma says, at the
+        given weight."""
+        if k == len(self.steps) - 1 or sigma < self._tors_start:
+            self._torsion_launch(1, self._traj_row(k))
+
+    def _torsion_launch(self, turn, copy_out):
+        """One agdiff_restrain_torsions launch on the current stream over self.pos (turn 0: only measures), the graphs the update
+        kernels have quarantined skipped (ws.nan_flag[1:]), viol -> torsion_viol, angle -> torsion_angle."""
+        tr_ptr, quads, centre, half, side_row, side_ptr, side_idx = self._tors
+        skip = ctypes.c_void_p(self.ws.nan_flag.data_ptr() + 4)          # (element 0 is the "any graph" flag)
+        _lib.check(self.lib.agdiff_restrain_torsions(self.pos_p, _lib.ptr(self.topo.graph_ptr), _lib.ptr(tr_ptr), _lib.ptr(quads),
+                                                     _lib.ptr(centre), _lib.ptr(half), _lib.ptr(side_row), _lib.ptr(side_ptr),
+                                                     _lib.ptr(side_idx), skip, self.topo.G, self.topo.N, int(quads.shape[0]), self._tors_S,
+                                                     self._tors_weight, int(turn), copy_out, _lib.ptr(self._tors_angle),
+                                                     _lib.ptr(self._tors_viol), _lib.stream_ptr()), "agdiff_restrain_torsions")
 
     def check_nan(self):
         """dualenc.py:539-541.  ws.nan_flag[0] is set by the update kernel as soon as any position is NaN.  Polled every
@@ -1225,6 +1288,11 @@ class LangevinRun:
         if self._restr is not None:
             self.restraint_viol = self._restr_viol.cpu()
             self.restraint_viol[self.nan_graphs()] = float("nan")        # (also a graph that left the range at the very last poll)
+        if self._tors is not None:
+            bad = self.nan_graphs()
+            self.torsion_viol, self.torsion_angle = self._tors_viol.cpu(), self._tors_angle.cpu()
+            self.torsion_viol[bad] = float("nan")                         # (likewise)
+            self.torsion_angle[bad[torch.from_numpy(self._tors_graph)]] = float("nan")
         if self.traj is not None and self._traj_overlap:
             self._traj_send(self.k)
             self._traj_land()

@@ -14,8 +14,9 @@ is forced after the run, and `restr_viol` says what is left.  DESIGN.md 4.18.
     sample_restrained    one molecule x num_samples conformers, with the reference driver's retry rule
     python -m agdiff_amd.restraints   a sampling job under the test set's restraints, or --report on a finished one
 
-The CHEMISTRY IS UNVERIFIED: nobody has run this on a trained checkpoint.  No angle or torsion restraints, no symmetry-equivalent
-atom mappings, no --dist-mode shard; packed multi-molecule jobs through driver.run_job are a follow-up.
+The CHEMISTRY IS UNVERIFIED: nobody has run this on a trained checkpoint.  Torsion restraints are torsion_restraints.py's (a
+molecule may carry both kinds); no angle restraints, no symmetry-equivalent atom mappings, no --dist-mode shard; packed
+multi-molecule jobs through driver.run_job are a follow-up.
 """
 import math
 import os

@@ -1127,6 +1127,56 @@ int agdiff_restrain_pairs(float* pos /* [N][3], in place */, const int32_t* grap
                           int32_t sweeps /* [0, 16] */, float* copy_out /* [N][3] or null */, float* viol /* [G] or null */,
                           void* stream);
 
+/* ---- torsion restraints ----------------------------------------------------------------------------------------------------
+ * Conformers under torsion restraints (a torsion scan, a fixed phi / psi pair, an amide held trans, a biaryl twist held to a
+ * docking pose -- what a distance window cannot say: a 1-4 distance fixes |theta| at best, never its sign): epsnet.LangevinRun
+ * calls this after a step's update, after agdiff_restrain_pairs and before agdiff_hold_core
+ * (agdiff_amd/torsion_restraints.py).
+ *
+ * agdiff_restrain_torsions: circular windows centre +- half on dihedrals of a packed batch, in place.
+ *   pos [N][3]             a packed batch, read and written
+ *   graph_ptr [G + 1]      first atom of every graph (agdiff_topo_t.graph_ptr); entries are clamped to [0, N]
+ *   tr_ptr [G + 1]         the restraints of graph g are rows tr_ptr[g] .. tr_ptr[g + 1] of the four arrays below, walked in
+ *                          row order; entries are clamped to [0, T]
+ *   quads [T][4]           batch-level atoms (a, u, v, b): theta = atan2(|b2| b1 . n2, n1 . n2), b1 = p_u - p_a, b2 = p_v - p_u,
+ *                          b3 = p_b - p_v, n1 = b1 x b2, n2 = b2 x b3, agdiff_torsion_angles' formula in fp64 from the stored fp32
+ *   centre [T], half [T]   the window in radians, |centre| <= pi and half in [0, pi] (the HOST checks); half = pi: always satisfied
+ *   side_row [T]           row of the side table whose atoms the restraint turns, -1 (or anything outside [0, S)): measure only
+ *   side_ptr [S + 1], side_idx   the side table: row r = side_ptr[r] .. side_ptr[r + 1] lists OFFSETS FROM THE GRAPH'S FIRST ATOM,
+ *                          so all conformers of a molecule share one row.  A row always lists atoms that turn with the v, b end
+ *                          of its quad (the host reverses a quad whose smaller side is u's: theta(a, u, v, b) = theta(b, v, u, a)).
+ *                          An offset outside the graph, or one naming u or v (they lie on the axis), is skipped, and so is a listed
+ *                          atom with a coordinate that is not finite: each stays bit for bit.  May be null for S == 0.
+ *   skip [G] int32 or null != 0: the graph is left alone (agdiff_ws_t.nan_flag + 1)
+ *   weight w               in (0, 1], else AGDIFF_ERR_ARG
+ *   turn                   0: only measure, nothing is written to pos or copy_out
+ *   copy_out [N][3] or null  receives every value stored to pos and nothing else (the trajectory frame).  Not pos.
+ *   angle [T] or null      theta as found when the restraint's turn comes (turn == 0: as it is), NaN for a degenerate quad -- a
+ *                          zero normal, or an atom outside its graph, in which case it reads nothing -- which is not turned and does
+ *                          not enter viol; NaN for every restraint of a graph that is left alone
+ *   viol [G]               the largest |e| in radians over the graph's restraints BEFORE the call, 0 without restraints
+ * The excess: Delta = theta - centre wrapped into [-pi, pi]; |Delta| <= half: satisfied, nothing of the restraint is written;
+ * else e = Delta - sign(Delta) half.  The window is circular: centre 170 degrees with half 20 degrees contains -175 degrees.
+ * A restraint with e != 0, turn != 0 and a non-empty side row turns every listed atom by phi = -w e about the axis through p_v
+ * along k = (p_v - p_u) / |p_v - p_u|, right-handed: r' = r cos phi + (k x r) sin phi + k (k . r) (1 - cos phi), r = p - p_v, in
+ * fp64, rounded to fp32 once.  Turning that side by +phi changes theta by +phi, so theta' = theta - w e, and w = 1 lands on the
+ * violated edge of the window.  The rotation is proper and rigid: every distance within either side and every tetrahedral parity
+ * is kept.  A rigid turn about a bridge leaves every dihedral about another bond unchanged, so restraints on distinct bridges
+ * are independent and one pass at w = 1 satisfies all of them.
+ * A measure pass over the graph's restraints comes before anything is written.  A graph with skip[g] != 0, or with a quad
+ * coordinate that is not finite, is not written at all and gets viol[g] = NaN.  One 64-lane wave per graph walks the restraints in
+ * row order, lanes striding over the side row, with a workgroup barrier after each rotation: any number of atoms and of
+ * restraints, no LDS.  No atomics, deterministic bit for bit. */
+int agdiff_restrain_torsions(float* pos /* [N][3], in place */, const int32_t* graph_ptr /* [G + 1] */,
+                             const int32_t* tr_ptr /* [G + 1]: the restraints of graph g are rows tr_ptr[g] .. tr_ptr[g + 1] */,
+                             const int32_t* quads /* [T][4] batch-level atoms (a, u, v, b) */,
+                             const float* centre /* [T] rad */, const float* half /* [T] rad, in [0, pi] */,
+                             const int32_t* side_row /* [T]: row of the side table, -1 = measure only */,
+                             const int32_t* side_ptr /* [S + 1] */, const int32_t* side_idx /* offsets from the graph's first atom */,
+                             const int32_t* skip /* [G] or NULL */, int32_t G, int32_t N, int32_t T, int32_t S,
+                             float weight, int32_t turn /* 0: only measure */, float* copy_out /* [N][3] or NULL */,
+                             float* angle /* [T] or NULL */, float* viol /* [G] */, void* stream);
+
 /* ---- distance-distribution MMD -----------------------------------------------------------------------------------------
  * The maximum mean discrepancy between the interatomic-distance distributions of the generated and the reference conformers of
  * one molecule, as the ConfGF / CGCF / GraphDG line reports it ("all", and "single" per atom pair; their "pair" mode, over all
