@@ -10,7 +10,8 @@ For the reference alone every case stays inside the tolerance: float32 against f
 Not here: the kernel's segmented walk (HeadPolyArgs.seg_tile_live) -- no entry point reaches it, every launcher passes null, so
 agdiff_pair_head_poly_rows is tested on the canonical radius list of agdiff_sampler_front instead; k_gin_layer_persistent -- it runs
 only above 65,536 nodes, where tests/test_hip_node_kernels.py::test_gin_large_shapes holds it to the reference (a lone node in a
-wave's second round included)."""
+wave's second round included); the output paths of k_edge_encoder (rows, operand form, row_index, the pos_index / mir_index scatter, a
+wave's second tile) -- tests/test_hip_edge_kernels.py."""
 import ctypes
 
 import numpy as np
