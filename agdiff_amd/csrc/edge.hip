@@ -240,6 +240,17 @@ struct ConvArgs {
 #define AG_CONV_LDS_BLOCKS 80   // resident 2-KiB weight blocks: filt_w1 (48: both convs' first layer) | filt_w2a (32)
 #define AG_CONV_NCH 12          // 16-channel tiles of the 192 filter channels (conv1: 0..7, conv2: 8..11)
 
+// The hidden activation of the filter MLPs as the second layer's operand.  f32 / f16x3: s = max(u, log2(1 + 2^u)) =
+// softplus(beta x) / ln 2, the shift of ShiftedSoftplus folded into filt_b2 (ssp = ln 2 (s - 1)).  bf16x3: s - 1 itself -- s sits
+// near 1 while the filter lives in s - 1 (~0.2), and 16 bits spent on s left the aggregate of a 100-edge list at 5.8e-5 normwise
+// against the mode's gate of 3e-5 (tests/test_hip_fused_kernels.py; 8.6e-6 with s - 1).  The packer folds the -1 into filt_b1
+// (u' = u - 1) and leaves filt_b2 unshifted, so that s - 1 = max(u', log2(1/2 + 2^u')): the same instructions.
+template <int MODE>
+__device__ __forceinline__ float ag_conv_ssp(float u) {
+  if constexpr (MODE == AG_BF3) return fmaxf(u, ag_log2(0.5f + ag_exp2(fminf(u, 126.0f))));
+  else return ag_ssp_base2(u);
+}
+
 // encoder/schnet.py:136-162 for conv1 (F=128) and conv2 (F=64) of one InteractionBlock:
 //   W_e = nn(edge_attr_e) * (lw(d_e) * C(d_e));  agg[dst] += x[src] * W_e   (aggr='add')
 // Persistent launch, one 8-wave workgroup per CU (2 waves per SIMD, ~240 VGPRs: the tile body is a software
@@ -431,7 +442,7 @@ __global__ void __launch_bounds__(64 * AG_CONV_WAVES, AG_CONV_WAVES / 4) k_cfcon
             }
             if (m > 0) {
               float v0 = (t < 2) ? hp0[2 * t] : hp1[2 * t - 4], v1 = (t < 2) ? hp0[2 * t + 1] : hp1[2 * t - 3];
-              v0 = ag_ssp_base2(v0); v1 = ag_ssp_base2(v1);
+              v0 = ag_conv_ssp<MODE>(v0); v1 = ag_conv_ssp<MODE>(v1);
               asm volatile("" : "+v"(v0), "+v"(v1));      // keep the softplus here (the IR sinks it to its use otherwise)
               ag_cvt_pair(hidb[m - 1], 2 * t, v0, v1);
             }

@@ -628,11 +628,14 @@ class PackedParams:
             f64 = lambda key: _np(sd, key).astype(np.float64)
             arrays[n + "filt_w1_pk"] = pack_blocks(
                 np.concatenate([k1 * f64(c1 + ".nn.0.weight"), k2 * f64(c2_ + ".nn.0.weight")], 0), kouter=True)
-            arrays[n + "filt_b1"] = np.concatenate([k1 * f64(c1 + ".nn.0.bias"), k2 * f64(c2_ + ".nn.0.bias")])
+            # split-bf16 (mode 1): the second layer's operand is s - 1, not s (csrc/edge.hip: ag_conv_ssp) -- u' = u - 1 through the
+            # first bias, and the second bias keeps its value instead of taking the shift
+            shift = 1.0 if mode == 1 else 0.0
+            arrays[n + "filt_b1"] = np.concatenate([k1 * f64(c1 + ".nn.0.bias"), k2 * f64(c2_ + ".nn.0.bias")]) - shift
             arrays[n + "filt_w2a_pk"] = pack_blocks(LN2 * f64(c1 + ".nn.2.weight"))
             arrays[n + "filt_w2b_pk"] = pack_blocks(LN2 * f64(c2_ + ".nn.2.weight"))
-            arrays[n + "filt_b2"] = np.concatenate([f64(c1 + ".nn.2.bias") - LN2 * f64(c1 + ".nn.2.weight").sum(1),
-                                                    f64(c2_ + ".nn.2.bias") - LN2 * f64(c2_ + ".nn.2.weight").sum(1)])
+            arrays[n + "filt_b2"] = np.concatenate([f64(c1 + ".nn.2.bias") - (1.0 - shift) * LN2 * f64(c1 + ".nn.2.weight").sum(1),
+                                                    f64(c2_ + ".nn.2.bias") - (1.0 - shift) * LN2 * f64(c2_ + ".nn.2.weight").sum(1)])
             arrays[n + "dist_seg"] = np.concatenate([dist_segments(_np(sd, c + ".distance_weighting.layer1.weight")[:, 0],
                                                                    _np(sd, c + ".distance_weighting.layer1.bias"),
                                                                    _np(sd, c + ".distance_weighting.layer2.weight")[0],

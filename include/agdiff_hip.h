@@ -81,12 +81,13 @@ typedef struct agdiff_conv_params {
    * ShiftedSoftplus (schnet.py:71-80) is evaluated in base 2 with its constants folded into the two linear
    * layers by the host: with c = beta * log2(e) per conv, layer 1 yields u = c (W1 a + b1); the kernel forms
    * s = max(u, log2(1 + 2^u)); since softplus(beta x) - ln 2 = ln 2 (s - 1), layer 2 uses ln 2 * W2 and
-   * b2 - ln 2 * W2 1. */
+   * b2 - ln 2 * W2 1.  Precision 1 (split-bf16) keeps the shift out of the bias: layer 1 yields u' = u - 1, the
+   * kernel forms s - 1 = max(u', log2(1/2 + 2^u')) -- the operand whose 16 bits the filter gets -- and layer 2 uses b2. */
   const float* filt_w1_pk;   /* pkk [4][12]: rows 0..127 c1 * conv1.nn.0.weight, 128..191 c2 * conv2.nn.0.weight */
-  const float* filt_b1;      /* [192] c * nn.0.bias */
+  const float* filt_b1;      /* [192] c * nn.0.bias (split-bf16: minus 1, the kernel then forms s - 1 instead of s) */
   const float* filt_w2a_pk;  /* pk [8][4]: ln2 * conv1.nn.2.weight */
   const float* filt_w2b_pk;  /* pk [4][2]: ln2 * conv2.nn.2.weight */
-  const float* filt_b2;      /* [192] nn.2.bias - ln2 * rowsum(nn.2.weight) */
+  const float* filt_b2;      /* [192] nn.2.bias - ln2 * rowsum(nn.2.weight) (split-bf16: nn.2.bias) */
   const float* dist_seg;     /* [2][100]: DistanceWeightingNetwork (schnet.py:83-100) of conv1 / conv2 by segments: the network's
                                 pre-sigmoid value layer2(relu(layer1(d))) is piecewise linear in d with at most 32 kinks
                                 (d = -b1_k / w1_k); bp[32] = the kinks in ascending order (padded with +inf), then
