@@ -412,6 +412,136 @@ __global__ void __launch_bounds__(64) k_leader_prune(const uint64_t* __restrict_
   if (lane == 0) n_kept[0] = k;
 }
 
+// Taylor-Butina clustering over the threshold bit-matrix (the rule: include/agdiff_hip.h, agdiff_butina_cluster): ONE workgroup
+// of AG_BUTINA_THREADS / 64 waves.  In LDS: the neighbour count of every conformer (s_cnt, one pad slot per 64 so that the lanes
+// that own columns 64 l + b of a row spread over the banks), the live set and the current cluster as 64 words each, and per
+// conformer its centroid, per centroid its cluster's size and rank, as 16-bit values (all < 65536) -- 42 KB.
+// Every iteration: a block-wide arg-max over the packed keys count << 12 | (4095 - index) of the live conformers (a count reaches
+// 4096: 13 bits), then wave 0 ANDs the centroid's row with the live set.  reorder = 1: the counts follow the live set through the
+// REMOVED members' rows -- each still-live j with bit (m, j) loses one, by LDS atomics -- so every row is read once over the whole
+// run.  Once the best count is 1 (in either mode) nobody live has a neighbour left to take, so the rest are singletons in index
+// order and are finished in one pass.  The outer loop is counted and its centroid always leaves the live set; every barrier in it sits under a
+// condition read from LDS after a barrier, the same in every thread.
+#define AG_BUTINA_THREADS 1024
+#define AG_BUTINA_WAVES (AG_BUTINA_THREADS / 64)
+#define AG_BUTINA_DEPTH 4                           // rows a wave keeps in flight
+__device__ __forceinline__ int ag_butina_slot(int i) { return i + (i >> 6); }
+
+__global__ void __launch_bounds__(AG_BUTINA_THREADS) k_butina_cluster(const uint64_t* __restrict__ bits, int G, int words, int reorder,
+                                                                      int32_t* __restrict__ leader, int32_t* __restrict__ count,
+                                                                      int32_t* __restrict__ rank, int32_t* __restrict__ n_clusters) {
+  __shared__ int32_t s_cnt[AGDIFF_PRUNE_MAX_CONFS + 64];
+  __shared__ uint16_t s_leader[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ uint16_t s_size[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ uint16_t s_rank[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ uint64_t s_live[64];
+  __shared__ uint64_t s_mem[64];
+  __shared__ int32_t s_best[AG_BUTINA_WAVES];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (t < 64) s_live[t] = G >= 64 * t + 64 ? ~0ull : (G > 64 * t ? (1ull << (G - 64 * t)) - 1 : 0);   // columns >= G never count
+  __syncthreads();
+  {                                                 // the counts over all G conformers: one wave per row, diagonal taken as set
+    const uint64_t all = s_live[lane];
+    for (int base = wv * AG_BUTINA_DEPTH; base < G; base += AG_BUTINA_WAVES * AG_BUTINA_DEPTH) {
+      uint64_t w[AG_BUTINA_DEPTH];
+#pragma unroll
+      for (int d = 0; d < AG_BUTINA_DEPTH; ++d) w[d] = (base + d < G && lane < words) ? bits[(size_t)(base + d) * words + lane] : 0;
+#pragma unroll
+      for (int d = 0; d < AG_BUTINA_DEPTH; ++d) {
+        const int r = base + d;
+        if (r < G) {                                // (wave-uniform)
+          const uint64_t x = w[d] | (lane == (r >> 6) ? 1ull << (r & 63) : 0);
+          int p = __popcll(x & all);
+          ag_wave_sum(p);
+          if (lane == 0) s_cnt[ag_butina_slot(r)] = p;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  int nclus = 0;
+  for (int it = 0; it < G; ++it) {
+    int key = -1;                                   // (a dead conformer; a live one has key >= 0)
+    for (int i = t; i < G; i += AG_BUTINA_THREADS) {
+      const int c = s_cnt[ag_butina_slot(i)];
+      const int k = ((c > 0 ? c : 0) << 12) | (AGDIFF_PRUNE_MAX_CONFS - 1 - i);
+      key = max(key, ((s_live[i >> 6] >> (i & 63)) & 1) ? k : -1);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = max(key, __shfl_xor(key, o));
+    if (lane == 0) s_best[wv] = key;
+    __syncthreads();
+    int best = s_best[0];
+#pragma unroll
+    for (int w = 1; w < AG_BUTINA_WAVES; ++w) best = max(best, s_best[w]);
+    if (best < 0) break;                            // nobody is live
+    const int c = AGDIFF_PRUNE_MAX_CONFS - 1 - (best & (AGDIFF_PRUNE_MAX_CONFS - 1));
+    if ((best >> 12) <= 1) {                        // only singletons are left: index order
+      const int pc = __popcll(s_live[lane]);        // every wave: the live conformers below each word, by a prefix sum over the lanes
+      int upto = pc;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(upto, o);
+        upto += lane >= o ? v : 0;
+      }
+      const int total = __shfl(upto, 63);
+      for (int base = 64 * wv; base < G; base += AG_BUTINA_THREADS) {      // (wave-uniform: word base / 64, conformer base + lane)
+        const int before = __shfl(upto - pc, base >> 6);
+        const uint64_t lw = s_live[base >> 6];
+        const int i = base + lane;
+        if ((lw >> lane) & 1) {                     // (live bits lie below G)
+          s_leader[i] = (uint16_t)i;
+          s_size[i] = 1;
+          s_rank[i] = (uint16_t)(nclus + before + __popcll(lw & ((1ull << lane) - 1)));
+        }
+      }
+      nclus += total;
+      break;
+    }
+    if (wv == 0) {                                  // the cluster of c: c and its live neighbours
+      const uint64_t w = (lane < words ? bits[(size_t)c * words + lane] : 0) | (lane == (c >> 6) ? 1ull << (c & 63) : 0);
+      const uint64_t mem = w & s_live[lane];
+      s_mem[lane] = mem;
+      s_live[lane] &= ~mem;
+      for (uint64_t m = mem; m; m &= m - 1) s_leader[64 * lane + __ffsll((long long)m) - 1] = (uint16_t)c;
+      int p = __popcll(mem);
+      ag_wave_sum(p);
+      if (lane == 0) { s_size[c] = (uint16_t)p; s_rank[c] = (uint16_t)it; }
+    }
+    nclus = it + 1;
+    __syncthreads();
+    if (reorder) {                                  // (block-uniform) the removed members' rows take them out of the live counts
+      const uint64_t live = s_live[lane];
+      for (int l = wv; l < words; l += AG_BUTINA_WAVES) {
+        uint64_t m = s_mem[l];                      // (wave-uniform)
+        while (m) {
+          int r[AG_BUTINA_DEPTH];
+          uint64_t w[AG_BUTINA_DEPTH];
+#pragma unroll
+          for (int d = 0; d < AG_BUTINA_DEPTH; ++d) {
+            r[d] = m ? 64 * l + __ffsll((long long)m) - 1 : -1;
+            m &= m - 1;
+          }
+#pragma unroll
+          for (int d = 0; d < AG_BUTINA_DEPTH; ++d) w[d] = (r[d] >= 0 && lane < words) ? bits[(size_t)r[d] * words + lane] : 0;
+#pragma unroll
+          for (int d = 0; d < AG_BUTINA_DEPTH; ++d)
+            for (uint64_t x = w[d] & live; x; x &= x - 1) atomicSub(&s_cnt[ag_butina_slot(64 * lane + __ffsll((long long)x) - 1)], 1);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  for (int i = t; i < G; i += AG_BUTINA_THREADS) {
+    const int l = s_leader[i];
+    leader[i] = l;
+    count[i] = l == i ? (int)s_size[i] : 0;
+    rank[i] = s_rank[l];
+  }
+  if (t == 0) n_clusters[0] = nclus;
+}
+
 // eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
 // accumulated: returns the largest eigenvalue and its unit eigenvector q
 __device__ double ag_eigvec_max4(const double (&k)[10], double (&q)[4]) {
@@ -1831,6 +1961,23 @@ extern "C" int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* kee
   if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
   const int words = ag_bits_pitch(G) / 8;                 // 64-bit words per row
   k_leader_prune<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(bits, G, words, keep, leader, count, n_kept);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_butina_cluster(const uint64_t* bits, int32_t G, int32_t reorder, int32_t* leader, int32_t* count, int32_t* rank,
+                                     int32_t* n_clusters, void* stream) {
+  if (!bits || !leader || !count || !rank || !n_clusters || G < 0 || (reorder != 0 && reorder != 1) || ((uintptr_t)bits & 7))
+    return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) {                                     // no launch: n_clusters = 0 by a memset on the stream
+    const hipError_t e = hipMemsetAsync(n_clusters, 0, sizeof(int32_t), (hipStream_t)stream);
+    if (e == hipSuccess) return AGDIFF_OK;
+    (void)hipGetLastError();
+    return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;      // (without a device there is no n_clusters to write)
+  }
+  const int words = ag_bits_pitch(G) / 8;                 // 64-bit words per row
+  k_butina_cluster<<<dim3(1), dim3(AG_BUTINA_THREADS), 0, (hipStream_t)stream>>>(bits, G, words, reorder, leader, count, rank, n_clusters);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -784,6 +784,28 @@ int agdiff_rmsd_self(const float* pos, const int32_t* atom_idx, const int32_t* p
 int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* keep, int32_t* leader, int32_t* count, int32_t* n_kept,
                         void* stream);
 
+/* Taylor-Butina clustering (rdkit Butina.ClusterData) over `bits` in the layout above: which conformer families there are, how
+ * populated each is, and which conformer sits in the middle of each.  The rule:
+ *   - every conformer starts live; repeat until nobody is live:
+ *       - among the live conformers take c with the largest neighbour count, ties to the LOWEST index;
+ *       - the cluster of c is c itself plus every live j with bit (c, j);
+ *       - the members of that cluster stop being live.
+ *   - the neighbour count of i is the number of conformers j with bit (i, j) set,
+ *       reorder = 1: over the conformers STILL LIVE when the choice is made -- the counts shrink as clusters are removed
+ *                    (Butina's algorithm proper; ClusterData(reordering=True));
+ *       reorder = 0: over ALL G conformers, counted once before the first choice (reordering=False): the leader walk of
+ *                    agdiff_leader_prune run in the order (count descending, index ascending).
+ * leader [G]: the centroid of each conformer's cluster (itself for a centroid); count [G]: the cluster size at a centroid, 0
+ * elsewhere; rank [G]: the 0-based creation order of the conformer's cluster; n_clusters [1].  Every entry is written.
+ * Bits in columns >= G are ignored (the last word is masked, the padding is not trusted) and the diagonal is taken as set, so
+ * the centroid always leaves the live set: the outer loop is counted, at most G iterations.  `bits` is expected to be symmetric;
+ * on an asymmetric matrix the partition is unspecified, and the call still ends within G iterations and writes only inside its
+ * three arrays.  One workgroup, no global atomics, deterministic bit for bit.  A null pointer, `bits` not 8-byte aligned,
+ * G < 0 or reorder outside {0, 1}: AGDIFF_ERR_ARG; G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT; G == 0: n_clusters = 0 and
+ * no launch. */
+int agdiff_butina_cluster(const uint64_t* bits, int32_t G, int32_t reorder, int32_t* leader, int32_t* count, int32_t* rank,
+                          int32_t* n_clusters, void* stream);
+
 /* Rigid superposition (rdkit AlignMolConformers: atoms keep their labels, identity mapping): for each conformer the proper
  * rotation R and translation that minimise the RMSD to `target` over the atoms `atom_idx` (Horn's quaternion, fp64), applied
  * to ALL n atoms: out = R (x - c_x) + c_target, so hydrogens ride along.  No reflection: a mirror image stays apart.  When
