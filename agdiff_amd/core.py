@@ -10,12 +10,13 @@ after the run (driver.run_job(hold_core=True)).  DESIGN.md 4.16.
     core_arguments     the checks of epsnet.LangevinRun's keywords core_pos / core_select / core_weight / core_start_sigma
     hold_core          one stand-alone launch on a packed batch
     to_template_frame  a molecule's conformers superposed on the template over the core atoms
-"""
-import math
 
+The hold inside a run is constraints.CoreHold: the last entry of constraints.ORDER.
+"""
 import numpy as np
 
 from . import _lib
+from .constraints import launch_prologue, weight_and_start
 from .molecule import as_host
 
 
@@ -36,13 +37,9 @@ def core_arguments(N, core_pos, core_select, core_weight=1.0, core_start_sigma=f
     sel = as_host(core_select)
     if tuple(sel.shape) != (N,):
         raise ValueError("core_select has shape %s, the batch %d atoms: expected [%d]" % (tuple(sel.shape), N, N))
-    w = float(core_weight)
-    if not (0.0 < w <= 1.0):
-        raise ValueError("core_weight must lie in (0, 1] (got %r): 1 holds the core exactly, less pulls it that fraction of the way" %
-                         (core_weight,))
-    start = float(core_start_sigma)
-    if math.isnan(start):
-        raise ValueError("core_start_sigma must be a number (inf: hold from the first step)")
+    w, start = weight_and_start(core_weight, core_start_sigma,
+                                "core_weight must lie in (0, 1] (got %r): 1 holds the core exactly, less pulls it that fraction of the way",
+                                "core_start_sigma must be a number (inf: hold from the first step)")
     return np.array(pos, dtype=np.float32, order="C"), np.ascontiguousarray(sel != 0, dtype=np.uint8), w, start
 
 
@@ -53,30 +50,11 @@ def hold_core(pos, core_pos, select, batch, weight=1.0, skip=None, copy_out=None
     selected atoms' new values) are optional.  dev float32 [G] on the device: the RMSD between each core before the call and
     its fit, NaN for a graph that was left alone."""
     import torch
-    from .trajectory import _graph_ptr
-    if not torch.is_tensor(pos):
-        pos = torch.from_numpy(as_host(pos, np.float32))
-    if pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pos must have shape [N, 3], got %s" % (tuple(pos.shape),))
-    N = int(pos.shape[0])
-    b = as_host(batch).reshape(-1)
-    if b.shape[0] != N:
-        raise ValueError("batch has %d entries, pos %d atoms" % (b.shape[0], N))
-    gp, G = _graph_ptr(b)
+    pos, gp, G, N, skip = launch_prologue(pos, batch, skip, copy_out, device)
     tpl, sel, w, _ = core_arguments(N, core_pos, select, weight)
-    if not (pos.is_cuda and pos.dtype == torch.float32 and pos.is_contiguous()):
-        pos = pos.to(device, torch.float32).contiguous()
-    dev_ = pos.device
-    if copy_out is not None and not (torch.is_tensor(copy_out) and copy_out.is_cuda and copy_out.dtype == torch.float32 and
-                                     copy_out.is_contiguous() and tuple(copy_out.shape) == (N, 3)):
-        raise ValueError("copy_out must be a contiguous float32 tensor [N, 3] on the GPU")
-    if skip is not None:
-        skip = torch.from_numpy(as_host(skip, np.int32).reshape(-1)).to(dev_)
-        if skip.shape[0] != G:
-            raise ValueError("skip has %d entries, the batch %d graphs" % (skip.shape[0], G))
-    out = torch.empty(G, dtype=torch.float32, device=dev_)
-    _lib.call("agdiff_hold_core", pos, torch.from_numpy(tpl).to(dev_), torch.from_numpy(sel).to(dev_), torch.from_numpy(gp).to(dev_),
-              skip, G, N, w, copy_out, out)
+    out = torch.empty(G, dtype=torch.float32, device=pos.device)
+    _lib.call("agdiff_hold_core", pos, torch.from_numpy(tpl).to(pos.device), torch.from_numpy(sel).to(pos.device), gp, skip, G, N, w, copy_out,
+              out)
     return pos, out
 
 

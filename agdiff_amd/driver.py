@@ -610,6 +610,18 @@ def _prepared_batches(model, batches, mine, confs_of, rank, world, log):
             pool.shutdown(wait=True)
 
 
+def load_model(ckpt, precision, trust, device):
+    """The score network of the reference checkpoint file `ckpt` (compat.load_checkpoint; trust: unpickle arbitrary classes) on
+    `device`, in eval mode; precision None: the model's default."""
+    from . import compat, get_model
+    ckpt = compat.load_checkpoint(ckpt, trust=trust)
+    model = get_model(compat.model_config(ckpt))
+    if precision:
+        model.precision = precision
+    model.load_state_dict(ckpt["model"])
+    return model.to(device).eval()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ckpt", required=True, help="reference checkpoint (dict with 'config' and 'model', train.py:219-231)")
@@ -700,7 +712,6 @@ def main(argv=None):
 
     import torch
     import torch.distributed as dist
-    from . import compat, get_model
     from .synth import extend_graph_order_np
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -714,19 +725,13 @@ def main(argv=None):
         own_pg = True
     torch.manual_seed(args.seed + rank)
     np.random.seed(args.seed + rank)
-    ckpt = compat.load_checkpoint(args.ckpt, trust=args.trust_ckpt)
-    cfg = compat.model_config(ckpt)
-    model = get_model(cfg)
-    if args.precision:
-        model.precision = args.precision
-    model.load_state_dict(ckpt["model"])
-    model = model.to(device).eval()
+    model = load_model(args.ckpt, args.precision, args.trust_ckpt, device)
 
     mols = [m for m in load_testset(args.testset) if args.start_idx <= m["index"] < args.end_idx]
     if args.extend_order:
         for m in mols:
             r, c, t = extend_graph_order_np(m["atom_type"].shape[0], m["edge_index"][0], m["edge_index"][1],
-                                            m["edge_type"], order=cfg.edge_order)
+                                            m["edge_type"], order=model.config.edge_order)
             m["edge_index"], m["edge_type"] = np.stack([r, c]), t
     kw = dict(n_steps=args.n_steps, step_lr=1e-6, w_global=args.w_global, global_start_sigma=args.global_start_sigma,
               clip=args.clip)

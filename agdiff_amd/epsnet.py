@@ -691,22 +691,12 @@ class DualEncoderEpsNetwork(nn.Module):
                        extend_radius=True, n_steps=5000, step_lr=0.0000010, clip=1000, clip_local=None,
                        clip_pos=None, global_start_sigma=float("inf"), w_global=0.2, **kwargs):
         """Set up one sampling job (dualenc.py:468-476) and return a LangevinRun that enqueues steps."""
-        if kwargs.get("core_pos") is not None or kwargs.get("core_select") is not None:      # (a ValueError needs no GPU)
-            from .core import core_arguments
-            core_arguments(atom_type.shape[0], kwargs.get("core_pos"), kwargs.get("core_select"), kwargs.get("core_weight", 1.0),
-                           kwargs.get("core_start_sigma", float("inf")))
-        from .restraints import SAMPLER_KEYWORDS, sampler_arguments
-        if any(k in kwargs for k in SAMPLER_KEYWORDS):                                       # (likewise)
-            sampler_arguments(atom_type.shape[0], batch, **{k: kwargs[k] for k in SAMPLER_KEYWORDS if k in kwargs})
-        from . import torsion_restraints
-        if any(k in kwargs for k in torsion_restraints.SAMPLER_KEYWORDS):                    # (likewise)
-            torsion_restraints.sampler_arguments(atom_type.shape[0], batch, bond_index=bond_index, bond_type=bond_type,
-                                                 frozen=kwargs.get("core_select"), num_graphs=num_graphs,
-                                                 **{k: kwargs[k] for k in torsion_restraints.SAMPLER_KEYWORDS if k in kwargs})
+        from .constraints import build
+        made = build(atom_type.shape[0], batch, bond_index, bond_type, num_graphs, kwargs)    # (a ValueError needs no GPU)
         self._require_gpu()
         return LangevinRun(self, atom_type, pos_init, bond_index, bond_type, batch, num_graphs, extend_order,
                            n_steps, step_lr, clip, clip_local, clip_pos, global_start_sigma, w_global,
-                           extend_radius=extend_radius, **kwargs)
+                           extend_radius=extend_radius, constraints=made, **kwargs)
 
 
 def _stream_ids_tensor(stream_ids):
@@ -746,22 +736,19 @@ class LangevinRun:
                  core_select=None, core_weight=1.0, core_start_sigma=float("inf"), restraint_pairs=None, restraint_lo=None,
                  restraint_hi=None, restraint_weight=1.0, restraint_start_sigma=float("inf"), restraint_sweeps=1, torsion_quads=None,
                  torsion_target=None, torsion_tol=None, torsion_sides=None, torsion_weight=1.0, torsion_start_sigma=float("inf"),
-                 **_ignored):
+                 constraints=None, **_ignored):
+        given = locals()
         if noise_mode not in ("chunked", "per_step", "counter"):
             raise ValueError("noise_mode must be 'chunked', 'per_step' or 'counter'")
         if noise_mode == "counter" and (noise_seed is None or stream_ids is None):
             raise ValueError("noise_mode='counter' needs noise_seed (int) and stream_ids (int64 [num_graphs])")
-        from .core import core_arguments
-        from .restraints import sampler_arguments
-        core = core_arguments(atom_type.shape[0], core_pos, core_select, core_weight, core_start_sigma)
-        restr = sampler_arguments(atom_type.shape[0], batch, restraint_pairs, restraint_lo, restraint_hi, restraint_weight,
-                                  restraint_start_sigma, restraint_sweeps)
-        from . import torsion_restraints
-        tors = torsion_restraints.sampler_arguments(atom_type.shape[0], batch, torsion_quads, torsion_target, torsion_tol, torsion_sides,
-                                                    torsion_weight, torsion_start_sigma, bond_index=bond_index, bond_type=bond_type,
-                                                    frozen=None if core is None else core[1], num_graphs=num_graphs)
-        if tors is not None and tors[4] is None:
-            raise ValueError("torsion restraints need the batch's bonds (bond_index, bond_type) or a side table (torsion_sides)")
+        # what runs after a step's update, in the order it runs in (agdiff_amd/constraints.py): begin_sampling's list, or -- for a run
+        # constructed directly -- built here from the 16 constraint keywords; every check of theirs comes before the device is touched
+        if constraints is None:
+            from .constraints import ORDER, build
+            constraints = build(atom_type.shape[0], batch, bond_index, bond_type, num_graphs,
+                                {k: given[k] for cls in ORDER for k in cls.KEYWORDS})
+        self._constraints = constraints
         self.model, self.lib = model, _lib.load()
         dev = model._device()
         self.sigmas = ((1.0 - model.alphas).sqrt() / model.alphas.sqrt()).detach().cpu()
@@ -801,44 +788,10 @@ class LangevinRun:
             if self.traj is None:
                 rows = max(1, min(2 * max(int(nan_check_every), 1), len(self.steps)))
                 self._rmsd_ring = torch.empty((rows, N, 3), dtype=torch.float32, device=dev)
-        # core_pos [N, 3] + core_select [N]: the rigid core hold (agdiff_amd/core.py).  After the update of every
-        # step with sigma < core_start_sigma one agdiff_hold_core launch puts the template's selected atoms where each graph's core
-        # is now (blended by core_weight), in self.pos and in the frame the update has just written; the hold after the run's last
-        # step always runs, with weight 1, and leaves `core_dev` [G]: how far that step had pulled each core out of shape (on the
-        # host after finish(); NaN for a graph without a core and for a quarantined one).  Nothing may run between a step's update
-        # and the next step's radius graph in agdiff_sampler_front, so such a run goes launch by launch (_fused_front).
-        self._core, self.core_dev = None, None
-        if core is not None:
-            tpl, sel, self._core_weight, self._core_start = core
-            self._core = (torch.from_numpy(tpl).to(dev), torch.from_numpy(sel).to(dev))
-            self._core_dev = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
-        # restraint_pairs [R, 2] + restraint_lo / restraint_hi [R]: distance restraints (agdiff_amd/restraints.py).
-        # After the update of every step with sigma < restraint_start_sigma one agdiff_restrain_pairs launch of restraint_sweeps
-        # sweeps pulls the violated pairs towards their windows, in self.pos and in the frame the update has just written, BEFORE the
-        # core hold (whose atoms it leaves where they are: fixed = core_select); the launch after the run's last step always runs, at
-        # the given weight (a restraint is soft), and one measuring launch after the closing hold leaves `restraint_viol` [G]: each
-        # graph's largest violation in what the run returns (on the host after finish(); NaN for a quarantined graph).  Launch by
-        # launch, like a run that holds a core (_fused_front).  No pairs: nothing of this exists and the run is what it was.
-        self._restr, self.restraint_viol = None, None
-        if restr is not None:
-            rs_ptr, rs_idx, rs_lo, rs_hi, self._restr_most, self._restr_weight, self._restr_start, self._restr_sweeps = restr
-            self._restr = tuple(torch.from_numpy(x).to(dev) for x in (rs_ptr, rs_idx, rs_lo, rs_hi))
-            self._restr_viol = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
-        # torsion_quads [T, 4] + torsion_target / torsion_tol [T]: torsion restraints (agdiff_amd/torsion_restraints.py, DESIGN.md
-        # 4.19).  After the update of every step with sigma < torsion_start_sigma one agdiff_restrain_torsions launch turns one side of
-        # every violated bond towards its window, in self.pos and in the frame the update has just written, AFTER the distance
-        # restraints and BEFORE the core hold (the sides avoid the core's atoms: frozen = core_select); the launch after the run's
-        # last step always runs, at the given weight, and one measuring launch after the closing hold leaves `torsion_viol` [G] and
-        # `torsion_angle` [T]: what is left in what the run returns (on the host after finish()).  Launch by launch (_fused_front).
-        self._tors, self.torsion_viol, self.torsion_angle = None, None, None
-        if tors is not None:
-            tr_ptr, quads, centre, half, (side_row, side_ptr, side_idx), self._tors_weight, self._tors_start = tors
-            self._tors_S = int(side_ptr.shape[0]) - 1
-            self._tors_graph = np.repeat(np.arange(tr_ptr.shape[0] - 1), np.diff(tr_ptr))
-            self._tors = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (tr_ptr, quads, centre, half, side_row, side_ptr))
-            self._tors += (torch.from_numpy(np.ascontiguousarray(side_idx)).to(dev) if side_idx.size else None,)
-            self._tors_viol = torch.full((self.topo.G,), float("nan"), dtype=torch.float32, device=dev)
-            self._tors_angle = torch.full((int(quads.shape[0]),), float("nan"), dtype=torch.float32, device=dev)
+        # the constraints' results (constraints.CoreHold / PairRestraints / TorsionRestraints .collect, in finish()); None without one.
+        # Nothing may run between a step's update and the next step's radius graph in agdiff_sampler_front, so a run with a
+        # constraint goes launch by launch (_fused_front)
+        self.core_dev = self.restraint_viol = self.torsion_viol = self.torsion_angle = None
         self.noise, self.on_step = noise, on_step
         self.step_lr, self.global_start_sigma = step_lr, global_start_sigma
         self.skip_discarded, self.nan_every = bool(skip_discarded_global), int(nan_check_every)
@@ -860,6 +813,8 @@ class LangevinRun:
         self.ws.range_rows.zero_()
         self._quarantine_non_finite_input()
         self.pos_p = _lib.ptr(self.pos)
+        for c in self._constraints:
+            c.attach(self)
         a = _lib.StepArgs()
         a.pos_in = self.pos_p
         a.pos_out = self.pos_p
@@ -877,7 +832,7 @@ class LangevinRun:
         self._use_graphs = bool((sg is True or (sg == "auto" and N <= model.STEP_GRAPH_MAX_NODES)) and on_step is None and
                                 noise_mode == "chunked" and self.pk.poly_kt > 0 and getattr(model, "fused_front", True) and
                                 not getattr(model, "front_split_graph", False) and not self.topo.large and self._rmsd is None and
-                                self._core is None and self._restr is None and self._tors is None)
+                                not self._constraints)
         self._graphs, self._step_table, self._step_index, self._dev_index = {}, None, None, None
         # (a capture needs a stream of its own: the legacy default stream, which torch hands out as the current one, cannot be captured)
         self._gstream = torch.cuda.Stream(device=dev) if self._use_graphs else None
@@ -946,8 +901,7 @@ class LangevinRun:
         and with them no step graphs (they replay the fused front).  Nor for a run that holds a core or restrains distances or
         torsions: agdiff_hold_core / agdiff_restrain_pairs / agdiff_restrain_torsions have to run between a step's update and the
         next step's radius graph, which agdiff_sampler_front does in one launch."""
-        return (self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large and self._core is None and
-                self._restr is None and self._tors is None)
+        return self.pk.poly_kt > 0 and getattr(self.model, "fused_front", True) and not self.topo.large and not self._constraints
 
     def _fill_args(self, a, k, dev, N):
         sig, step_size, noise_scale, use_global = self._sched[k]
@@ -1123,72 +1077,19 @@ class LangevinRun:
                 self._stage0_done = self._stage0_done or bool(run_global)
                 _lib.check(lib.agdiff_langevin_update(ctypes.byref(topo.struct), ctypes.byref(ws.struct),
                                                       ctypes.byref(a), stream), "agdiff_langevin_update")
-                if self._restr is not None:
-                    self._restrain(k, sig)
-                if self._tors is not None:
-                    self._restrain_torsions(k, sig)
-                if self._core is not None:
-                    self._hold_core(k, sig)
-                if self._restr is not None and k == len(self.steps) - 1:
-                    self._restrain_launch(0, None)                   # what is left in what the run returns
-                if self._tors is not None and k == len(self.steps) - 1:
-                    self._torsion_launch(0, None)                    # likewise
+                if self._constraints:                                # (in constraints.ORDER)
+                    last = k == len(self.steps) - 1
+                    for c in self._constraints:
+                        c.after_update(self, k, sig, last)
+                    if last:
+                        for c in self._constraints:
+                            c.measure(self)                          # what is left in what the run returns
                 self.k += 1
                 self._traj_ready = self.k
                 if self.on_step is not None:
                     self.on_step(k, i, self.pos)
                 if self.k % self.nan_every == 0 or self.k == len(self.steps):
                     self.check_nan()
-
-    def _hold_core(self, k, sigma):
-        """The hold after the update of step k (launch-by-launch path only): one agdiff_hold_core launch on the current stream for
-        a step with sigma < core_start_sigma, over self.pos and the frame the update has just written (_traj_row(k)), skipping
-        the graphs the update kernels have quarantined (ws.nan_flag[1:]: they carry a placeholder).  After the LAST step of the
-        schedule it runs whatever sigma and core_weight say, with weight 1: what the run returns holds the core exactly."""
-        last = k == len(self.steps) - 1
-        if not (last or sigma < self._core_start):
-            return
-        tpl, sel = self._core
-        G = self.topo.G
-        skip = ctypes.c_void_p(self.ws.nan_flag.data_ptr() + 4)          # (element 0 is the "any graph" flag)
-        _lib.check(self.lib.agdiff_hold_core(self.pos_p, _lib.ptr(tpl), _lib.ptr(sel), _lib.ptr(self.topo.graph_ptr), skip, G, self.topo.N,
-                                             1.0 if last else self._core_weight, self._traj_row(k), _lib.ptr(self._core_dev),
-                                             _lib.stream_ptr()), "agdiff_hold_core")
-
-    def _restrain(self, k, sigma):
-        """The restraint launch after the update of step k (launch-by-launch path only), before the core hold: for a step with
-        sigma < restraint_start_sigma, and after the LAST step of the schedule whatever sigma says, at the given weight."""
-        if k == len(self.steps) - 1 or sigma < self._restr_start:
-            self._restrain_launch(self._restr_sweeps, self._traj_row(k))
-
-    def _restrain_launch(self, sweeps, copy_out):
-        """One agdiff_restrain_pairs launch on the current stream over self.pos: `sweeps` sweeps (0: only measures), the atoms of a
-        held core fixed, the graphs the update kernels have quarantined skipped (ws.nan_flag[1:]), viol -> restraint_viol."""
-        rs_ptr, rs_idx, rs_lo, rs_hi = self._restr
-        fixed = _lib.ptr(self._core[1]) if self._core is not None else ctypes.c_void_p(0)
-        skip = ctypes.c_void_p(self.ws.nan_flag.data_ptr() + 4)          # (element 0 is the "any graph" flag)
-        _lib.check(self.lib.agdiff_restrain_pairs(self.pos_p, _lib.ptr(self.topo.graph_ptr), _lib.ptr(rs_ptr), _lib.ptr(rs_idx), _lib.ptr(rs_lo),
-                                                  _lib.ptr(rs_hi), fixed, skip, self.topo.G, self.topo.N, int(rs_idx.shape[0]),
-                                                  self._restr_most, self._restr_weight, int(sweeps), copy_out, _lib.ptr(self._restr_viol),
-                                                  _lib.stream_ptr()), "agdiff_restrain_pairs")
-
-    def _restrain_torsions(self, k, sigma):
-        """The torsion launch after the update of step k (launch-by-launch path only), after the distance restraints and before the
-        core hold: for a step with sigma < torsion_start_sigma, and after the LAST step of the schedule whatever sigma says, at the
-        given weight."""
-        if k == len(self.steps) - 1 or sigma < self._tors_start:
-            self._torsion_launch(1, self._traj_row(k))
-
-    def _torsion_launch(self, turn, copy_out):
-        """One agdiff_restrain_torsions launch on the current stream over self.pos (turn 0: only measures), the graphs the update
-        kernels have quarantined skipped (ws.nan_flag[1:]), viol -> torsion_viol, angle -> torsion_angle."""
-        tr_ptr, quads, centre, half, side_row, side_ptr, side_idx = self._tors
-        skip = ctypes.c_void_p(self.ws.nan_flag.data_ptr() + 4)          # (element 0 is the "any graph" flag)
-        _lib.check(self.lib.agdiff_restrain_torsions(self.pos_p, _lib.ptr(self.topo.graph_ptr), _lib.ptr(tr_ptr), _lib.ptr(quads),
-                                                     _lib.ptr(centre), _lib.ptr(half), _lib.ptr(side_row), _lib.ptr(side_ptr),
-                                                     _lib.ptr(side_idx), skip, self.topo.G, self.topo.N, int(quads.shape[0]), self._tors_S,
-                                                     self._tors_weight, int(turn), copy_out, _lib.ptr(self._tors_angle),
-                                                     _lib.ptr(self._tors_viol), _lib.stream_ptr()), "agdiff_restrain_torsions")
 
     def check_nan(self):
         """dualenc.py:539-541.  ws.nan_flag[0] is set by the update kernel as soon as any position is NaN.  Polled every
@@ -1283,16 +1184,10 @@ class LangevinRun:
                     rows[:, bad] = float("nan")
                 curves.append(rows)
             self.rmsd_curve, self.rmsd_curve_mirror = curves
-        if self._core is not None:
-            self.core_dev = self._core_dev.cpu()
-        if self._restr is not None:
-            self.restraint_viol = self._restr_viol.cpu()
-            self.restraint_viol[self.nan_graphs()] = float("nan")        # (also a graph that left the range at the very last poll)
-        if self._tors is not None:
-            bad = self.nan_graphs()
-            self.torsion_viol, self.torsion_angle = self._tors_viol.cpu(), self._tors_angle.cpu()
-            self.torsion_viol[bad] = float("nan")                         # (likewise)
-            self.torsion_angle[bad[torch.from_numpy(self._tors_graph)]] = float("nan")
+        if self._constraints:
+            bad = self.nan_graphs()                                  # (also a graph that left the range at the very last poll)
+            for c in self._constraints:
+                c.collect(self, bad)
         if self.traj is not None and self._traj_overlap:
             self._traj_send(self.k)
             self._traj_land()

@@ -14,16 +14,16 @@ is forced after the run, and `restr_viol` says what is left.  DESIGN.md 4.18.
     sample_restrained    one molecule x num_samples conformers, with the reference driver's retry rule
     python -m agdiff_amd.restraints   a sampling job under the test set's restraints, or --report on a finished one
 
+Inside a run the restraints are constraints.PairRestraints, the first entry of constraints.ORDER; the launcher's prologue, the
+sampling routine and the job's skeleton are shared with torsion_restraints.py and live in constraints.py too.
+
 The CHEMISTRY IS UNVERIFIED: nobody has run this on a trained checkpoint.  Torsion restraints are torsion_restraints.py's (a
 molecule may carry both kinds); no angle restraints, no symmetry-equivalent atom mappings, no --dist-mode shard; packed
 multi-molecule jobs through driver.run_job are a follow-up.
 """
-import math
-import os
-
 import numpy as np
 
-from . import _lib
+from . import _lib, constraints
 from .molecule import as_host
 
 MAX_SWEEPS = 16
@@ -75,12 +75,9 @@ def _table(N, pairs, lo, hi, batch):
 
 
 def _settings(weight, start_sigma, sweeps):
-    w = float(weight)
-    if not (0.0 < w <= 1.0):
-        raise ValueError("the restraint weight must lie in (0, 1] (got %r): 1 puts a lone violated pair onto its bound in one sweep" % (weight,))
-    start = float(start_sigma)
-    if math.isnan(start):
-        raise ValueError("the restraint start sigma must be a number (inf: restrain from the first step)")
+    w, start = constraints.weight_and_start(
+        weight, start_sigma, "the restraint weight must lie in (0, 1] (got %r): 1 puts a lone violated pair onto its bound in one sweep",
+        "the restraint start sigma must be a number (inf: restrain from the first step)")
     if isinstance(sweeps, bool) or int(sweeps) != sweeps or not (0 <= int(sweeps) <= MAX_SWEEPS):
         raise ValueError("restraint sweeps must be an integer in [0, %d] (got %r)" % (MAX_SWEEPS, sweeps))
     return w, start, int(sweeps)
@@ -113,7 +110,7 @@ def sampler_arguments(N, batch, restraint_pairs=None, restraint_lo=None, restrai
     return out
 
 
-SAMPLER_KEYWORDS = ("restraint_pairs", "restraint_lo", "restraint_hi", "restraint_weight", "restraint_start_sigma", "restraint_sweeps")
+SAMPLER_KEYWORDS = constraints.PairRestraints.KEYWORDS
 
 
 def restrain_pairs(pos, pairs, lo, hi, batch, weight=1.0, sweeps=1, fixed=None, skip=None, copy_out=None, device="cuda"):
@@ -124,38 +121,19 @@ def restrain_pairs(pos, pairs, lo, hi, batch, weight=1.0, sweeps=1, fixed=None, 
     atoms that have a restraint) are optional.  sweeps = 0 moves nothing and only measures.  viol float32 [G] on the device: each
     graph's largest violation BEFORE the call, 0 without restraints, NaN for a graph that was left alone."""
     import torch
-    from .trajectory import _graph_ptr
-    if not torch.is_tensor(pos):
-        pos = torch.from_numpy(as_host(pos, np.float32))
-    if pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pos must have shape [N, 3], got %s" % (tuple(pos.shape),))
-    N = int(pos.shape[0])
-    b = as_host(batch).reshape(-1)
-    if b.shape[0] != N:
-        raise ValueError("batch has %d entries, pos %d atoms" % (b.shape[0], N))
-    gp, G = _graph_ptr(b)
+    pos, gp, G, N, skip = constraints.launch_prologue(pos, batch, skip, copy_out, device)
     w, _, sweeps = _settings(weight, float("inf"), sweeps)
     rs_ptr, rs_idx, rs_lo, rs_hi, most = _table(N, pairs if pairs is not None else np.zeros((0, 2), dtype=np.int32),
-                                                lo if pairs is not None else [], hi if pairs is not None else [], b)
-    if not (pos.is_cuda and pos.dtype == torch.float32 and pos.is_contiguous()):
-        pos = pos.to(device, torch.float32).contiguous()
-    dev_ = pos.device
-    if copy_out is not None and not (torch.is_tensor(copy_out) and copy_out.is_cuda and copy_out.dtype == torch.float32 and
-                                     copy_out.is_contiguous() and tuple(copy_out.shape) == (N, 3)):
-        raise ValueError("copy_out must be a contiguous float32 tensor [N, 3] on the GPU")
+                                                lo if pairs is not None else [], hi if pairs is not None else [], batch)
     if fixed is not None:
         fixed = as_host(fixed).reshape(-1)
         if fixed.shape[0] != N:
             raise ValueError("fixed has %d entries, pos %d atoms" % (fixed.shape[0], N))
-        fixed = torch.from_numpy(np.ascontiguousarray(fixed != 0, dtype=np.uint8)).to(dev_)
-    if skip is not None:
-        skip = torch.from_numpy(as_host(skip, np.int32).reshape(-1)).to(dev_)
-        if skip.shape[0] != G:
-            raise ValueError("skip has %d entries, the batch %d graphs" % (skip.shape[0], G))
-    D = lambda x: torch.from_numpy(x).to(dev_)
-    out = torch.empty(G, dtype=torch.float32, device=dev_)
+        fixed = torch.from_numpy(np.ascontiguousarray(fixed != 0, dtype=np.uint8)).to(pos.device)
+    D = lambda x: torch.from_numpy(x).to(pos.device)
+    out = torch.empty(G, dtype=torch.float32, device=pos.device)
     R2 = int(rs_idx.shape[0])
-    _lib.call("agdiff_restrain_pairs", pos, D(gp), D(rs_ptr), D(rs_idx) if R2 else None, D(rs_lo) if R2 else None, D(rs_hi) if R2 else None,
+    _lib.call("agdiff_restrain_pairs", pos, gp, D(rs_ptr), D(rs_idx) if R2 else None, D(rs_lo) if R2 else None, D(rs_hi) if R2 else None,
               fixed, skip, G, N, R2, most, w, sweeps, copy_out, out)
     return pos, out
 
@@ -244,66 +222,21 @@ def sample_restrained(model, mol, num_samples, sampler_kwargs, device, weight=1.
                       counter_seed=None, max_retry=2, log=print):
     """`num_samples` conformers of ONE molecule in one batch (the reference driver's own granularity), under the restraints the
     molecule dict carries as restr_pairs / restr_lo / restr_hi (molecule-level indices; without them it is sampled unrestrained):
-    (pos_gen float32 [G, n, 3] numpy, viol float32 [G], ok).  Packs with driver.pack_batch and samples with driver.run_part; the
-    retry rule is scripts/test.py's, as driver.sample_passes applies it: a NaN anywhere samples the molecule again with
-    clip_local=20, at most `max_retry` attempts in all (with counter noise a retry draws with attempt + 1); a run that only left the
-    split-fp16 range is run again in split-bf16 and is not counted.  viol: each conformer's largest violation at the end of the
-    run (zeros without restraints); ok False: every attempt failed, pos_gen and viol are NaN.  Holds no core."""
-    from . import driver
-    G = int(num_samples)
-    packed = driver.pack_batch([mol], lambda _num_refs: G)
-    n = int(packed["spans"][0][1])
-    driver.check_counter(model, packed, counter_seed)
-    own = _of_molecule(mol)
-    extra = {}
-    if own is not None:
-        pr, lo, hi = pack_restraints(packed, [own])
-        extra = dict(restraint_pairs=pr, restraint_lo=lo, restraint_hi=hi, restraint_weight=weight, restraint_start_sigma=start_sigma,
-                     restraint_sweeps=sweeps)
-        sampler_arguments(packed["atom_type"].shape[0], packed["batch"], **extra)          # (a ValueError before any sampling)
-
-    def run_pass(sub, todo, clip_local, wide, tries, first):
-        run, pos, _ = driver.run_part(model, sub, device, sampler_kwargs, counter_seed, tries, wide, clip_local=clip_local, save_traj=False,
-                                      **extra)
-        per_graph = {"viol": run.restraint_viol} if own is not None else {}
-        return pos.cpu(), None, run.nan_graphs().numpy(), getattr(run, "range_graphs", ()), per_graph
-
-    ok, got = driver.sample_passes(packed, run_pass, max_retry, log)
-    pos = got["pos"].numpy().astype(np.float32).reshape(G, n, 3)
-    if own is None:
-        viol = np.zeros(G, dtype=np.float32) if ok[0] else np.full(G, np.nan, dtype=np.float32)
-    else:
-        viol = got["viol"].numpy().astype(np.float32) if "viol" in got else np.full(G, np.nan, dtype=np.float32)
-    return pos, viol, bool(ok[0])
+    (pos_gen float32 [G, n, 3] numpy, viol float32 [G], ok).  Under DISTANCE restraints only: torsion restraints the molecule carries as
+    well (tors_quads / ...) are not applied here -- torsion_restraints.sample_restrained samples under both.  The packing, the checks
+    and the retry rule are constraints.sample_restrained's.  viol: each conformer's largest violation at the end of the run (zeros
+    without restraints); ok False: every attempt failed, pos_gen and viol are NaN.  Holds no core."""
+    settings = dict(weight=weight, start_sigma=start_sigma, sweeps=sweeps)
+    res = constraints.sample_restrained(model, mol, num_samples, sampler_kwargs, device, pairs=settings, counter_seed=counter_seed,
+                                        max_retry=max_retry, log=log)
+    viol = res["restraint_viol"] if "restraint_viol" in res else constraints.no_violation(int(num_samples), res["ok"])
+    return res["pos"], viol, res["ok"]
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--ckpt", default=None, help="reference checkpoint (dict with 'config' and 'model'); not with --report")
-    ap.add_argument("--testset", required=True, help="test set with restr_pairs_<i> / restr_lo_<i> / restr_hi_<i> (add_restraints)")
-    ap.add_argument("--out", required=True, help="output directory (samples_all.npz); with --report the .npz to write")
-    ap.add_argument("--num-confs", default="2x")
-    ap.add_argument("--start-idx", type=int, default=0)
-    ap.add_argument("--end-idx", type=int, default=200)
-    ap.add_argument("--n-steps", type=int, default=5000)
-    ap.add_argument("--w-global", type=float, default=1.0)
-    ap.add_argument("--global-start-sigma", type=float, default=0.5)
-    ap.add_argument("--clip", type=float, default=1000.0)
-    ap.add_argument("--weight", type=float, default=1.0,
-                    help="the fraction of the way a lone violated pair is moved onto its bound per sweep, in (0, 1]")
-    ap.add_argument("--start-sigma", type=float, default=float("inf"),
-                    help="restrain only after steps whose noise level sigma is below this (default: from the first step); the launch "
-                         "after the last step always runs")
-    ap.add_argument("--sweeps", type=int, default=1, help="Jacobi sweeps per step, 1 .. 16")
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--noise", default="default", choices=["default", "counter"], help="as agdiff_amd.driver's")
-    ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
-    ap.add_argument("--trust-ckpt", action="store_true", help="unpickle arbitrary classes from the checkpoint")
-    ap.add_argument("--report", action="store_true", help="measure a finished job (--samples) instead of sampling")
-    ap.add_argument("--samples", default=None, help="--report: the samples_all.npz to measure")
-    ap.add_argument("--device", default="cuda")
-    return ap
+    return constraints.job_parser(main.__doc__, "test set with restr_pairs_<i> / restr_lo_<i> / restr_hi_<i> (add_restraints)",
+                                  "the fraction of the way a lone violated pair is moved onto its bound per sweep, in (0, 1]",
+                                  extra=[("--sweeps", dict(type=int, default=1, help="Jacobi sweeps per step, 1 .. 16"))])
 
 
 def main(argv=None):
@@ -317,67 +250,26 @@ def main(argv=None):
     python -m agdiff_amd.restraints --report --samples samples_all.npz --testset test.npz --out viol.npz
     measures a finished job: `restr_viol_<i>` for every molecule of the samples."""
     args = build_parser().parse_args(argv)
-    from . import driver
-    restraints = load_restraints(args.testset)
-    if args.report:
-        if not args.samples:
-            raise SystemExit("--report needs --samples")
-        z = np.load(args.samples, allow_pickle=False)
-        out = {}
-        for key in z.files:
-            if key.startswith("pos_gen_"):
-                i = int(key.split("_")[-1])
-                out["restr_viol_%d" % i] = measure(z[key], restraints.get(i), device=args.device)
-        _summary(out, restraints, print)
-        np.savez_compressed(args.out, **out)
-        return out
-    if not args.ckpt:
-        raise SystemExit("sampling needs --ckpt")
-    _settings(args.weight, args.start_sigma, args.sweeps)
-    if args.sweeps < 1:
-        raise SystemExit("--sweeps must be >= 1")
-    import torch
-    from . import compat, get_model
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    torch.cuda.set_device(device)
-    torch.manual_seed(args.seed)
-    np.random.seed(args.seed)
-    ckpt = compat.load_checkpoint(args.ckpt, trust=args.trust_ckpt)
-    cfg = compat.model_config(ckpt)
-    model = get_model(cfg)
-    if args.precision:
-        model.precision = args.precision
-    model.load_state_dict(ckpt["model"])
-    model = model.to(device).eval()
-    mols = [m for m in driver.load_testset(args.testset) if args.start_idx <= m["index"] < args.end_idx]
-    confs_of = driver.num_confs(args.num_confs)
-    kw = dict(n_steps=args.n_steps, step_lr=1e-6, w_global=args.w_global, global_start_sigma=args.global_start_sigma, clip=args.clip)
-    counter_seed = int(args.seed) if args.noise == "counter" else None
-    os.makedirs(args.out, exist_ok=True)
-    out = {}
-    for m in mols:
-        i = m["index"]
-        if i in restraints:
-            m["restr_pairs"], m["restr_lo"], m["restr_hi"] = restraints[i]
-        pos, viol, ok = sample_restrained(model, m, confs_of(m["num_refs"]), kw, device, weight=args.weight, start_sigma=args.start_sigma,
-                                          sweeps=args.sweeps, counter_seed=counter_seed)
-        if not ok:
-            print("molecule %s failed twice (NaN); skipped" % m["name"])
-            continue
-        out["pos_gen_%d" % i], out["name_%d" % i], out["restr_viol_%d" % i] = pos, np.str_(m["name"]), viol
-    _summary(out, restraints, print)
-    driver._save_npz_atomic(os.path.join(args.out, "samples_all.npz"), out)
-    return out
+    own = load_restraints(args.testset)
 
+    def check():
+        _settings(args.weight, args.start_sigma, args.sweeps)
+        if args.sweeps < 1:
+            raise SystemExit("--sweeps must be >= 1")
 
-def _summary(out, restraints, log):
-    worst = [float(np.nanmax(v)) for k, v in out.items() if k.startswith("restr_viol_") and int(k.split("_")[-1]) in restraints and
-             v.size and not np.isnan(v).all()]
-    if worst:
-        log("distance restraints: %d restrained molecules; largest violation left %.4f A, median of the molecules' largest %.4f A"
-            % (len(worst), max(worst), float(np.median(worst))))
-    else:
-        log("distance restraints: no restrained molecule in this job")
+    def attach(m):
+        if m["index"] in own:
+            m["restr_pairs"], m["restr_lo"], m["restr_hi"] = own[m["index"]]
+
+    def sample(model, m, G, kw, device, counter_seed):
+        pos, viol, ok = sample_restrained(model, m, G, kw, device, weight=args.weight, start_sigma=args.start_sigma, sweeps=args.sweeps,
+                                          counter_seed=counter_seed)
+        return dict(pos_gen=pos, restr_viol=viol), ok
+
+    return constraints.restrained_job(args, own, check, attach, sample,
+                                      lambda i, pos_gen: dict(restr_viol=measure(pos_gen, own.get(i), device=args.device)),
+                                      ("restr_viol", "distance restraints",
+                                       "largest violation left %.4f A, median of the molecules' largest %.4f A"))
 
 
 if __name__ == "__main__":

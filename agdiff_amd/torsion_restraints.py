@@ -20,16 +20,18 @@ launches move the angle again, and `tors_viol` says what is left.  DESIGN.md 4.1
     sample_restrained      one molecule x num_samples conformers, with the reference driver's retry rule
     python -m agdiff_amd.torsion_restraints   a sampling job under the test set's restraints, or --report on a finished one
 
+Inside a run the restraints are constraints.TorsionRestraints, the second entry of constraints.ORDER; the launcher's prologue, the
+sampling routine and the job's skeleton are shared with restraints.py and live in constraints.py too.
+
 The CHEMISTRY IS UNVERIFIED: nobody has run this on a trained checkpoint.  No angle restraints, no ring bonds (a ring bond cannot
 be turned rigidly), no symmetry-equivalent atom mappings, no --dist-mode shard; packed multi-molecule jobs through driver.run_job
 are a follow-up.
 """
 import math
-import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, constraints
 from .ezbonds import _side
 from .molecule import as_host, bonded_neighbours
 
@@ -122,13 +124,9 @@ def _quad_arrays(quads, target, tol):
 
 
 def _settings(weight, start_sigma):
-    w = float(weight)
-    if not (0.0 < w <= 1.0):
-        raise ValueError("the torsion weight must lie in (0, 1] (got %r): 1 puts a violated angle onto the edge of its window" % (weight,))
-    start = float(start_sigma)
-    if math.isnan(start):
-        raise ValueError("the torsion start sigma must be a number (inf: restrain from the first step)")
-    return w, start
+    return constraints.weight_and_start(weight, start_sigma,
+                                        "the torsion weight must lie in (0, 1] (got %r): 1 puts a violated angle onto the edge of its window",
+                                        "the torsion start sigma must be a number (inf: restrain from the first step)")
 
 
 def _side_table(T, sides):
@@ -234,7 +232,7 @@ def restraint_arguments(N, quads, target, tol, batch, sides=None, weight=1.0, st
     return (tr_ptr, q, tg, tl, table) + settings
 
 
-SAMPLER_KEYWORDS = ("torsion_quads", "torsion_target", "torsion_tol", "torsion_sides", "torsion_weight", "torsion_start_sigma")
+SAMPLER_KEYWORDS = constraints.TorsionRestraints.KEYWORDS
 
 
 def sampler_arguments(N, batch, torsion_quads=None, torsion_target=None, torsion_tol=None, torsion_sides=None, torsion_weight=1.0,
@@ -254,32 +252,14 @@ def restrain_torsions(pos, quads, target, tol, batch, sides, weight=1.0, turn=Tr
     dihedral as found when its turn came (NaN: degenerate, or its graph was left alone); viol float32 [G]: each graph's largest
     excess in radians BEFORE the call, 0 without restraints, NaN for a graph that was left alone."""
     import torch
-    from .trajectory import _graph_ptr
-    if not torch.is_tensor(pos):
-        pos = torch.from_numpy(as_host(pos, np.float32))
-    if pos.dim() != 2 or pos.shape[1] != 3:
-        raise ValueError("pos must have shape [N, 3], got %s" % (tuple(pos.shape),))
-    N = int(pos.shape[0])
-    b = as_host(batch).reshape(-1)
-    if b.shape[0] != N:
-        raise ValueError("batch has %d entries, pos %d atoms" % (b.shape[0], N))
-    gp, G = _graph_ptr(b)
-    args = restraint_arguments(N, quads, target if quads is not None else None, tol if quads is not None else None, b,
-                               sides if quads is not None else None, weight, num_graphs=G)
-    if not (pos.is_cuda and pos.dtype == torch.float32 and pos.is_contiguous()):
-        pos = pos.to(device, torch.float32).contiguous()
+    pos, gp, G, N, skip = constraints.launch_prologue(pos, batch, skip, copy_out, device)
     dev_ = pos.device
-    if copy_out is not None and not (torch.is_tensor(copy_out) and copy_out.is_cuda and copy_out.dtype == torch.float32 and
-                                     copy_out.is_contiguous() and tuple(copy_out.shape) == (N, 3)):
-        raise ValueError("copy_out must be a contiguous float32 tensor [N, 3] on the GPU")
-    if skip is not None:
-        skip = torch.from_numpy(as_host(skip, np.int32).reshape(-1)).to(dev_)
-        if skip.shape[0] != G:
-            raise ValueError("skip has %d entries, the batch %d graphs" % (skip.shape[0], G))
+    args = restraint_arguments(N, quads, target if quads is not None else None, tol if quads is not None else None, batch,
+                               sides if quads is not None else None, weight, num_graphs=G)
     D = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev_)
     viol = torch.empty(G, dtype=torch.float32, device=dev_)
     if args is None:
-        _lib.call("agdiff_restrain_torsions", pos, D(gp), torch.zeros(G + 1, dtype=torch.int32, device=dev_), None, None, None, None, None, None,
+        _lib.call("agdiff_restrain_torsions", pos, gp, torch.zeros(G + 1, dtype=torch.int32, device=dev_), None, None, None, None, None, None,
                   skip, G, N, 0, 0, 1.0, 0, copy_out, None, viol)
         return pos, torch.empty(0, dtype=torch.float32, device=dev_), viol
     tr_ptr, q, tg, tl, table, w, _ = args
@@ -288,7 +268,7 @@ def restrain_torsions(pos, quads, target, tol, batch, sides, weight=1.0, turn=Tr
         table = (np.full(T, -1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32))
     row, sp, si = table
     angle = torch.empty(T, dtype=torch.float32, device=dev_)
-    _lib.call("agdiff_restrain_torsions", pos, D(gp), D(tr_ptr), D(q), D(tg), D(tl), D(row), D(sp), D(si) if si.size else None, skip, G, N, T,
+    _lib.call("agdiff_restrain_torsions", pos, gp, D(tr_ptr), D(q), D(tg), D(tl), D(row), D(sp), D(si) if si.size else None, skip, G, N, T,
               int(sp.shape[0]) - 1, w, 1 if turn else 0, copy_out, angle, viol)
     return pos, angle, viol
 
@@ -430,77 +410,21 @@ def sample_restrained(model, mol, num_samples, sampler_kwargs, device, weight=1.
     unrestrained): (pos_gen float32 [G, n, 3] numpy, viol float32 [G], angle float32 [G, T], ok).  A molecule that also carries
     restr_pairs / restr_lo / restr_hi (restraints.py) is sampled under both, the distance restraints with restraint_weight /
     _start_sigma / _sweeps.  Packs with driver.pack_batch and samples with driver.run_part; the retry rule is scripts/test.py's, as
-    driver.sample_passes applies it (restraints.sample_restrained).  viol: each conformer's largest excess in radians at the end of
-    the run, angle its final dihedrals (zeros and [G, 0] without restraints); ok False: every attempt failed, all three NaN.  Holds
-    no core."""
-    from . import driver, restraints
+    driver.sample_passes applies it: the packing, the checks and the sampling are constraints.sample_restrained's.  viol: each
+    conformer's largest excess in radians at the end of the run, angle its final dihedrals (zeros and [G, 0] without restraints); ok
+    False: every attempt failed, all three NaN.  Holds no core."""
     G = int(num_samples)
-    packed = driver.pack_batch([mol], lambda _num_refs: G)
-    n = int(packed["spans"][0][1])
-    N = packed["atom_type"].shape[0]
-    driver.check_counter(model, packed, counter_seed)
-    own = _of_molecule(mol)
-    extra, T = {}, 0
-    if own is not None:
-        q, tg, tl, sides = pack_torsion_restraints(packed, [own])
-        T = q.shape[0] // G
-        extra = dict(torsion_quads=q, torsion_target=tg, torsion_tol=tl, torsion_sides=sides, torsion_weight=weight,
-                     torsion_start_sigma=start_sigma)
-        sampler_arguments(N, packed["batch"], **extra)                                     # (a ValueError before any sampling)
-    pairs = restraints._of_molecule(mol)
-    if pairs is not None:
-        pr, lo, hi = restraints.pack_restraints(packed, [pairs])
-        both = dict(restraint_pairs=pr, restraint_lo=lo, restraint_hi=hi, restraint_weight=restraint_weight,
-                    restraint_start_sigma=restraint_start_sigma, restraint_sweeps=restraint_sweeps)
-        restraints.sampler_arguments(N, packed["batch"], **both)
-        extra.update(both)
-
-    def run_pass(sub, todo, clip_local, wide, tries, first):
-        run, pos, _ = driver.run_part(model, sub, device, sampler_kwargs, counter_seed, tries, wide, clip_local=clip_local, save_traj=False,
-                                      **extra)
-        per_graph = {}
-        if own is not None:                                          # (per graph along the LAST dimension: angle as [T, G])
-            per_graph = {"viol": run.torsion_viol, "angle": run.torsion_angle.reshape(G, T).t().contiguous()}
-        return pos.cpu(), None, run.nan_graphs().numpy(), getattr(run, "range_graphs", ()), per_graph
-
-    ok, got = driver.sample_passes(packed, run_pass, max_retry, log)
-    pos = got["pos"].numpy().astype(np.float32).reshape(G, n, 3)
-    if own is None:
-        viol = np.zeros(G, dtype=np.float32) if ok[0] else np.full(G, np.nan, dtype=np.float32)
-        angle = np.zeros((G, 0), dtype=np.float32)
-    else:
-        viol = got["viol"].numpy().astype(np.float32) if "viol" in got else np.full(G, np.nan, dtype=np.float32)
-        angle = (np.ascontiguousarray(got["angle"].numpy().astype(np.float32).T) if "angle" in got
-                 else np.full((G, T), np.nan, dtype=np.float32))
-    return pos, viol, angle, bool(ok[0])
+    res = constraints.sample_restrained(model, mol, G, sampler_kwargs, device, torsions=dict(weight=weight, start_sigma=start_sigma),
+                                        pairs=dict(weight=restraint_weight, start_sigma=restraint_start_sigma, sweeps=restraint_sweeps),
+                                        counter_seed=counter_seed, max_retry=max_retry, log=log)
+    if "torsion_viol" not in res:
+        return res["pos"], constraints.no_violation(G, res["ok"]), np.zeros((G, 0), dtype=np.float32), res["ok"]
+    return res["pos"], res["torsion_viol"], res["torsion_angle"], res["ok"]
 
 
 def build_parser():
-    import argparse
-    ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--ckpt", default=None, help="reference checkpoint (dict with 'config' and 'model'); not with --report")
-    ap.add_argument("--testset", required=True, help="test set with tors_quads_<i> / tors_target_<i> / tors_tol_<i> (add_torsion_restraints)")
-    ap.add_argument("--out", required=True, help="output directory (samples_all.npz); with --report the .npz to write")
-    ap.add_argument("--num-confs", default="2x")
-    ap.add_argument("--start-idx", type=int, default=0)
-    ap.add_argument("--end-idx", type=int, default=200)
-    ap.add_argument("--n-steps", type=int, default=5000)
-    ap.add_argument("--w-global", type=float, default=1.0)
-    ap.add_argument("--global-start-sigma", type=float, default=0.5)
-    ap.add_argument("--clip", type=float, default=1000.0)
-    ap.add_argument("--weight", type=float, default=1.0,
-                    help="the fraction of the way a violated angle is turned onto the edge of its window per step, in (0, 1]")
-    ap.add_argument("--start-sigma", type=float, default=float("inf"),
-                    help="restrain only after steps whose noise level sigma is below this (default: from the first step); the launch "
-                         "after the last step always runs")
-    ap.add_argument("--seed", type=int, default=2021)
-    ap.add_argument("--noise", default="default", choices=["default", "counter"], help="as agdiff_amd.driver's")
-    ap.add_argument("--precision", default=None, choices=[None, "f32", "bf16x3", "f16x3"])
-    ap.add_argument("--trust-ckpt", action="store_true", help="unpickle arbitrary classes from the checkpoint")
-    ap.add_argument("--report", action="store_true", help="measure a finished job (--samples) instead of sampling")
-    ap.add_argument("--samples", default=None, help="--report: the samples_all.npz to measure")
-    ap.add_argument("--device", default="cuda")
-    return ap
+    return constraints.job_parser(main.__doc__, "test set with tors_quads_<i> / tors_target_<i> / tors_tol_<i> (add_torsion_restraints)",
+                                  "the fraction of the way a violated angle is turned onto the edge of its window per step, in (0, 1]")
 
 
 def main(argv=None):
@@ -518,67 +442,27 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     from . import driver, restraints
     own = load_torsion_restraints(args.testset)
-    if args.report:
-        if not args.samples:
-            raise SystemExit("--report needs --samples")
-        z = np.load(args.samples, allow_pickle=False)
-        mols = {m["index"]: m for m in driver.load_testset(args.testset)}
-        out = {}
-        for key in z.files:
-            if key.startswith("pos_gen_"):
-                i = int(key.split("_")[-1])
-                out["tors_viol_%d" % i], out["tors_angle_%d" % i] = measure(mols[i], z[key], own.get(i), device=args.device)
-        _summary(out, own, print)
-        np.savez_compressed(args.out, **out)
-        return out
-    if not args.ckpt:
-        raise SystemExit("sampling needs --ckpt")
-    _settings(args.weight, args.start_sigma)
-    import torch
-    from . import compat, get_model
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    torch.cuda.set_device(device)
-    torch.manual_seed(args.seed)
-    np.random.seed(args.seed)
-    ckpt = compat.load_checkpoint(args.ckpt, trust=args.trust_ckpt)
-    cfg = compat.model_config(ckpt)
-    model = get_model(cfg)
-    if args.precision:
-        model.precision = args.precision
-    model.load_state_dict(ckpt["model"])
-    model = model.to(device).eval()
-    mols = [m for m in driver.load_testset(args.testset) if args.start_idx <= m["index"] < args.end_idx]
-    pairs = restraints.load_restraints(args.testset)
-    confs_of = driver.num_confs(args.num_confs)
-    kw = dict(n_steps=args.n_steps, step_lr=1e-6, w_global=args.w_global, global_start_sigma=args.global_start_sigma, clip=args.clip)
-    counter_seed = int(args.seed) if args.noise == "counter" else None
-    os.makedirs(args.out, exist_ok=True)
-    out = {}
-    for m in mols:
-        i = m["index"]
-        if i in own:
-            m["tors_quads"], m["tors_target"], m["tors_tol"] = own[i]
-        if i in pairs:
-            m["restr_pairs"], m["restr_lo"], m["restr_hi"] = pairs[i]
-        pos, viol, angle, ok = sample_restrained(model, m, confs_of(m["num_refs"]), kw, device, weight=args.weight,
-                                                 start_sigma=args.start_sigma, counter_seed=counter_seed)
-        if not ok:
-            print("molecule %s failed twice (NaN); skipped" % m["name"])
-            continue
-        out["pos_gen_%d" % i], out["name_%d" % i], out["tors_viol_%d" % i], out["tors_angle_%d" % i] = pos, np.str_(m["name"]), viol, angle
-    _summary(out, own, print)
-    driver._save_npz_atomic(os.path.join(args.out, "samples_all.npz"), out)
-    return out
+    pairs = {} if args.report else restraints.load_restraints(args.testset)
+    mols = {m["index"]: m for m in driver.load_testset(args.testset)} if args.report else {}
 
+    def attach(m):
+        if m["index"] in own:
+            m["tors_quads"], m["tors_target"], m["tors_tol"] = own[m["index"]]
+        if m["index"] in pairs:
+            m["restr_pairs"], m["restr_lo"], m["restr_hi"] = pairs[m["index"]]
 
-def _summary(out, own, log):
-    worst = [float(np.nanmax(v)) for k, v in out.items() if k.startswith("tors_viol_") and int(k.split("_")[-1]) in own and
-             v.size and not np.isnan(v).all()]
-    if worst:
-        log("torsion restraints: %d restrained molecules; largest excess left %.5f rad, median of the molecules' largest %.5f rad"
-            % (len(worst), max(worst), float(np.median(worst))))
-    else:
-        log("torsion restraints: no restrained molecule in this job")
+    def sample(model, m, G, kw, device, counter_seed):
+        pos, viol, angle, ok = sample_restrained(model, m, G, kw, device, weight=args.weight, start_sigma=args.start_sigma,
+                                                 counter_seed=counter_seed)
+        return dict(pos_gen=pos, tors_viol=viol, tors_angle=angle), ok
+
+    def report(i, pos_gen):
+        viol, angle = measure(mols[i], pos_gen, own.get(i), device=args.device)
+        return dict(tors_viol=viol, tors_angle=angle)
+
+    return constraints.restrained_job(args, own, lambda: _settings(args.weight, args.start_sigma), attach, sample, report,
+                                      ("tors_viol", "torsion restraints",
+                                       "largest excess left %.5f rad, median of the molecules' largest %.5f rad"))
 
 
 if __name__ == "__main__":

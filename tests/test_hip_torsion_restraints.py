@@ -428,6 +428,48 @@ def test_sampler_with_distance_restraints_and_a_core_as_well():
     assert _same_bits(traj[0], held.cpu())
 
 
+def test_sampler_gates_each_constraint_by_its_own_start_sigma():
+    """The three constraints of one run, each with a start sigma of its own: pairs from step 2, torsions from step 4, the hold from
+    step 6 (A); the same with the hold's start below the whole schedule (B); and with the torsions' there as well (C).  All three
+    carry the core keywords, so `fixed` and `frozen` are the same in each; a frame is compared with the public launchers applied by
+    hand to the frame of the run that lacks just that constraint at that step."""
+    from agdiff_amd.core import hold_core
+    from agdiff_amd.restraints import restrain_pairs
+    from agdiff_amd.torsion_restraints import batch_sides
+    S = _sampler()
+    select, template, pairs, quads = _core(S)
+    G = S["G"]
+    lo, hi = np.full(G, 0.30, dtype=np.float32), np.full(G, 0.35, dtype=np.float32)
+    tg, tl = np.full(G, -2.0, dtype=np.float32), np.full(G, 0.1, dtype=np.float32)
+    lo_run, _, lo_traj = S["loose_off"]
+    sig = [s[0] for s in lo_run._sched]
+    assert len(sig) == 10 and all(a > b_ for a, b_ in zip(sig, sig[1:]))
+    between = lambda k: 0.5 * (sig[k - 1] + sig[k])        # between two sigmas of the schedule: step k is the first one gated in
+    below = 0.5 * sig[-1]                                  # below the whole schedule: only the closing launch runs
+    kw = dict(restraint_pairs=pairs, restraint_lo=lo, restraint_hi=hi, torsion_quads=quads, torsion_target=tg, torsion_tol=tl,
+              core_pos=template, core_select=select, restraint_start_sigma=between(2))
+    runs = {"A": S["run"](torsion_start_sigma=between(4), core_start_sigma=between(6), **kw),
+            "B": S["run"](torsion_start_sigma=between(4), core_start_sigma=below, **kw),
+            "C": S["run"](torsion_start_sigma=below, core_start_sigma=below, **kw)}
+    (_, _, A), (_, _, B), (_, _, C) = runs["A"], runs["B"], runs["C"]
+    for k in range(2):
+        assert _same_bits(A[k], lo_traj[k]), k
+    step, _ = restrain_pairs(lo_traj[2].cuda().contiguous(), pairs, lo, hi, S["batch"], fixed=select)
+    assert _same_bits(C[2], step.cpu()) and not _same_bits(C[2], lo_traj[2])
+    for k in range(4):
+        assert _same_bits(B[k], C[k]), k
+    oq, sides = batch_sides(S["N"], S["bi"], S["bt"], S["batch"], quads, frozen=select)
+    turned = _launch(C[4].numpy(), oq, tg, tl, S["batch"], sides)[0]
+    assert _same_bits(B[4], turned) and not _same_bits(B[4], C[4])
+    for k in range(6):
+        assert _same_bits(A[k], B[k]), k
+    held, _ = hold_core(B[6].cuda().contiguous(), template, select, S["batch"])
+    assert _same_bits(A[6], held.cpu()) and not _same_bits(A[6], B[6])
+    for name, (run, pos, traj) in runs.items():
+        assert len(traj) == 10 and not S["fused"](run) and torch.equal(traj[-1], pos), name
+        assert torch.isfinite(run.core_dev).all() and torch.isfinite(run.restraint_viol).all() and torch.isfinite(run.torsion_viol).all(), name
+
+
 def test_sampler_leaves_a_quarantined_graph_alone():
     S = _sampler()
     bad_init = S["pos_init"].clone()
