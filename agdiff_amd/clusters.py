@@ -57,10 +57,11 @@ def _empty(total, gen, distances, hand, ez_state):
 
 
 def cluster_conformers(item, threshold, metric="rmsd", reorder=True, align=True, device="cuda", valid=None, fix_handedness=False,
-                       fix_double_bonds=False, distances=True):
+                       fix_double_bonds=False, distances=True, tfd_rings=False):
     """Taylor-Butina clustering of the item's generated conformers: two conformers are neighbours when their best RMSD (metric="tfd":
     their torsion fingerprint deviation, agdiff_amd.torsions; the item must carry its bonds) is at most `threshold`.  The item, the
-    threshold, `valid`, `fix_handedness` and `fix_double_bonds` are those of ensemble.prune_conformers, and the fixes run first.
+    threshold, `valid`, `fix_handedness`, `fix_double_bonds` and `tfd_rings` (the rings as terms of the TFD) are those of
+    ensemble.prune_conformers, and the fixes run first.
     Returns a dict of tensors on `device`:
         centroids  int32 [K]    the centroid of every cluster in creation order, as indices into the item's conformers
         leader     int32 [G]    every conformer's centroid (itself for a centroid); -1 for a conformer that `valid` masks out
@@ -75,6 +76,8 @@ def cluster_conformers(item, threshold, metric="rmsd", reorder=True, align=True,
     import torch
     if metric not in ("rmsd", "tfd"):
         raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
+    if tfd_rings and metric != "tfd":
+        raise ValueError("tfd_rings goes with metric='tfd'")
     t = check_threshold(threshold, "RMSD")
     gen = _lib.conformers(item["pos_gen"], num_atoms(item))
     G = total = gen.shape[0]
@@ -103,7 +106,9 @@ def cluster_conformers(item, threshold, metric="rmsd", reorder=True, align=True,
         gen = gen[sel].contiguous()
     if metric == "tfd":
         from .torsions import _self_tfd
-        gen, out, bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=t, want_out=distances)
+        # (the keyword is passed only when set: without the switch this is, argument for argument, the call it was before)
+        gen, out, bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=t, want_out=distances,
+                                   **({"rings": True} if tfd_rings else {}))
         idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
     else:
         gen, idx, out, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=distances)
@@ -146,6 +151,8 @@ def _parser():
     how.add_argument("--rms", type=float, default=None, help="RMSD threshold in Angstrom (heavy atoms)")
     how.add_argument("--tfd", type=float, default=None,
                      help="torsion fingerprint deviation threshold in [0, 1] (agdiff_amd.torsions) instead of an RMSD")
+    ap.add_argument("--tfd-rings", action="store_true",
+                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are two families")
     ap.add_argument("--static", action="store_true",
                     help="count the neighbours once, over all conformers (ClusterData(reordering=False)); the default counts the "
                          "conformers still unclustered at every choice")
@@ -196,7 +203,8 @@ def main(argv=None):
             out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
             valid = flat if valid is None else valid & flat
         res = cluster_conformers(item, threshold, metric=metric, reorder=not args.static, align=args.align, device=args.device,
-                                 valid=valid, fix_handedness=args.fix_handedness, fix_double_bonds=args.fix_double_bonds)
+                                 valid=valid, fix_handedness=args.fix_handedness, fix_double_bonds=args.fix_double_bonds,
+                                 tfd_rings=args.tfd_rings)
         out["centroid_%d" % i] = res["centroids"].cpu().numpy()
         for key in ("cluster", "leader", "count", "population", "dist", "pos"):
             out["%s_%d" % (key, i)] = res[key].cpu().numpy()

@@ -1049,9 +1049,29 @@ __global__ void __launch_bounds__(64) k_flip_double_bonds(float* pos, const int3
 // ---- torsion fingerprint deviation: RMSD grows with the molecule and mixes ring breathing with rotamer changes; the dihedrals of
 // the rotatable bonds are what defines a conformer, so the matrix, the threshold bits and the mirror value exist over them too ----
 
+// The dihedral of the quad (a, u, v, b) from its twelve coordinates (fp32 values taken to fp64), theta = atan2(|b2| b1 . n2, n1 . n2):
+// the ONE copy of the arithmetic, called by k_torsion_angles (coordinates from global memory) and k_ring_coords (from LDS).  NaN for
+// a degenerate quad (a zero normal) or an input that is not finite.
+__device__ __forceinline__ double ag_dihedral(double ax, double ay, double az, double ux, double uy, double uz, double vx, double vy,
+                                              double vz, double bx, double by, double bz) {
+  const double b1x = ux - ax, b1y = uy - ay, b1z = uz - az;
+  const double b2x = vx - ux, b2y = vy - uy, b2z = vz - uz;
+  const double b3x = bx - vx, b3y = by - vy, b3z = bz - vz;
+  const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
+  const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
+  const double n1sq = n1x * n1x + n1y * n1y + n1z * n1z, n2sq = n2x * n2x + n2y * n2y + n2z * n2z;
+  // (fp32 inputs: every difference and product above is finite in fp64 iff the twelve coordinates are; an Inf or NaN among
+  // them reaches n1sq or n2sq or both of y and x below)
+  const double y = sqrt(b2x * b2x + b2y * b2y + b2z * b2z) * (b1x * n2x + b1y * n2y + b1z * n2z);
+  const double x = n1x * n2x + n1y * n2y + n1z * n2z;
+  const bool finite = ag_finite(ax) && ag_finite(ay) && ag_finite(az) && ag_finite(ux) && ag_finite(uy) && ag_finite(uz) &&
+                      ag_finite(vx) && ag_finite(vy) && ag_finite(vz) && ag_finite(bx) && ag_finite(by) && ag_finite(bz);
+  return (finite && n1sq > 0.0 && n2sq > 0.0) ? atan2(y, x) : (double)NAN;
+}
+
 // one wave per conformer, lanes over the columns (strided past 64), shaped like k_chiral_verdict: the dihedral of every quad
-// (a, u, v, b) in fp64 from the fp32 positions, theta = atan2(|b2| b1 . n2, n1 . n2).  NaN for a degenerate quad (a zero normal),
-// an input that is not finite, or a quad that names an atom outside [0, n), which reads nothing.
+// (a, u, v, b) in fp64 from the fp32 positions (ag_dihedral).  NaN for a degenerate quad, an input that is not finite, or a quad
+// that names an atom outside [0, n), which reads nothing.
 __global__ void __launch_bounds__(64) k_torsion_angles(const float* __restrict__ pos, const int32_t* __restrict__ quads, int n, int Q,
                                                        float* __restrict__ out) {
   const int g = blockIdx.x, lane = threadIdx.x;
@@ -1059,25 +1079,9 @@ __global__ void __launch_bounds__(64) k_torsion_angles(const float* __restrict__
   for (int c = lane; c < Q; c += 64) {
     const int a = quads[4 * c], u = quads[4 * c + 1], v = quads[4 * c + 2], b = quads[4 * c + 3];
     double theta = (double)NAN;
-    if (ag_atoms_in_range(n, a, u, v, b)) {
-      const double ax = p[3 * a], ay = p[3 * a + 1], az = p[3 * a + 2];
-      const double ux = p[3 * u], uy = p[3 * u + 1], uz = p[3 * u + 2];
-      const double vx = p[3 * v], vy = p[3 * v + 1], vz = p[3 * v + 2];
-      const double bx = p[3 * b], by = p[3 * b + 1], bz = p[3 * b + 2];
-      const double b1x = ux - ax, b1y = uy - ay, b1z = uz - az;
-      const double b2x = vx - ux, b2y = vy - uy, b2z = vz - uz;
-      const double b3x = bx - vx, b3y = by - vy, b3z = bz - vz;
-      const double n1x = b1y * b2z - b1z * b2y, n1y = b1z * b2x - b1x * b2z, n1z = b1x * b2y - b1y * b2x;
-      const double n2x = b2y * b3z - b2z * b3y, n2y = b2z * b3x - b2x * b3z, n2z = b2x * b3y - b2y * b3x;
-      const double n1sq = n1x * n1x + n1y * n1y + n1z * n1z, n2sq = n2x * n2x + n2y * n2y + n2z * n2z;
-      // (fp32 inputs: every difference and product above is finite in fp64 iff the twelve coordinates are; an Inf or NaN among
-      // them reaches n1sq or n2sq or both of y and x below)
-      const double y = sqrt(b2x * b2x + b2y * b2y + b2z * b2z) * (b1x * n2x + b1y * n2y + b1z * n2z);
-      const double x = n1x * n2x + n1y * n2y + n1z * n2z;
-      const bool finite = ag_finite(ax) && ag_finite(ay) && ag_finite(az) && ag_finite(ux) && ag_finite(uy) && ag_finite(uz) &&
-                          ag_finite(vx) && ag_finite(vy) && ag_finite(vz) && ag_finite(bx) && ag_finite(by) && ag_finite(bz);
-      if (finite && n1sq > 0.0 && n2sq > 0.0) theta = atan2(y, x);
-    }
+    if (ag_atoms_in_range(n, a, u, v, b))
+      theta = ag_dihedral(p[3 * a], p[3 * a + 1], p[3 * a + 2], p[3 * u], p[3 * u + 1], p[3 * u + 2], p[3 * v], p[3 * v + 1],
+                          p[3 * v + 2], p[3 * b], p[3 * b + 1], p[3 * b + 2]);
     out[(size_t)g * Q + c] = (float)theta;
   }
 }
@@ -1137,6 +1141,200 @@ __global__ void __launch_bounds__(256) k_tfd_matrix(const float* __restrict__ an
     const double norm = 3.141592653589793238462 * wsum;
     v = (float)(best / norm);
     vm = (float)(best_mirror / norm);
+  }
+  if (valid) {
+    const size_t at = (size_t)(j0 + ty) * G + i0 + tx;
+    if (out) out[at] = v;
+    if (out_mirror) out_mirror[at] = vm;
+  }
+  if (bits) {                                       // (every lane of the wave arrives here)
+    // the threshold is taken on the fp32 value as stored, so that bits == (out <= thresh) exactly
+    const unsigned long long flags = __ballot(valid && v <= thresh);
+    const int pieces = pitch >> 1, tiles_g = (G + 15) / 16;
+    if (j0 + ty < R) {
+      uint16_t* row = bits + (size_t)(j0 + ty) * pieces;
+      if (tx == 0) row[blockIdx.x] = (uint16_t)(flags >> (16 * (ty & 3)));
+      if ((int)blockIdx.x == tiles_g - 1 && tx >= 1 && tiles_g - 1 + tx < pieces) row[tiles_g - 1 + tx] = 0;
+    }
+  }
+}
+
+// ---- ring conformations: the rotatable bonds are bridges, so nothing above sees a ring.  The shape of every ring (the ring torsion
+// value and the Cremer-Pople puckering coordinates; include/agdiff_hip.h has the definitions), and the TFD over terms that carry a
+// scale and a parity of their own, so that rings stand next to bonds ----
+
+constexpr int AG_RING_SLOTS = 512;   // (ring, position) slots of one pass of k_ring_coords: four fp64 each (16 KB of LDS) + the ring ids
+
+// One wave per conformer, like k_torsion_angles / k_planar_groups, but a molecule has 1 .. 6 rings and one lane per ring would idle
+// the wave: the lanes walk the (ring, position) slots of the table, strided past 64, in passes of whole rings of at most
+// AG_RING_SLOTS slots (the launcher has checked 4 <= N <= AGDIFF_RING_MAX_ATOMS, so a ring always fits).  Per pass:
+//   1  slot (r, j): the position of atom r_j as fp64 into LDS -- NaN when ANY atom of the ring is outside [0, n): the ring reads
+//      nothing, and NaN positions make every number of it NaN below
+//   2  slot (r, j): |theta(r_j, r_j+1, r_j+2, r_j+3)| from LDS (ag_dihedral) into LDS
+//   3  one lane per ring, j ascending: tau = sum |theta_j| / N; centroid, R', R'', the normal, z_j (written over the ring's own
+//      |theta_j|), Q = sqrt(sum z_j^2); z_j = NaN when |R' x R''|^2 is zero or a coordinate is not finite
+//   4  slot (r, m), 2 <= m <= N / 2: the mode's sum over z_j, j ascending -> (q_m, phi_m), or the signed q_(N/2)
+// Every sum is made by one lane in a fixed order from values that depend on the ring alone, so a ring's numbers do not depend on
+// the launch, on which slots it occupies or on what else the table holds.  Each output has one writer.
+__global__ void __launch_bounds__(64) k_ring_coords(const float* __restrict__ pos, const int32_t* __restrict__ ring_ptr,
+                                                    const int32_t* __restrict__ ring_idx, int n, int Rg, float* __restrict__ tau,
+                                                    float* __restrict__ amp, float* __restrict__ pucker) {
+  __shared__ double sx[AG_RING_SLOTS], sy[AG_RING_SLOTS], sz[AG_RING_SLOTS], sv[AG_RING_SLOTS];
+  __shared__ int16_t sring[AG_RING_SLOTS];
+  const int g = blockIdx.x, lane = threadIdx.x;
+  const float* p = pos + (size_t)g * n * 3;
+  const size_t K = (size_t)(ring_ptr[Rg] - 3 * Rg);
+  for (int r0 = 0; r0 < Rg;) {
+    const int s0 = ring_ptr[r0];
+    int r1 = r0 + 1;
+    while (r1 < Rg && ring_ptr[r1 + 1] - s0 <= AG_RING_SLOTS) ++r1;
+    const int S = ring_ptr[r1] - s0;
+    if (S <= 0 || S > AG_RING_SLOTS) return;        // (a table the launcher would have refused; uniform over the wave)
+    for (int r = r0 + lane; r < r1; r += 64)
+      for (int s = ring_ptr[r] - s0; s < ring_ptr[r + 1] - s0; ++s) sring[s] = (int16_t)(r - r0);
+    __syncthreads();
+    for (int s = lane; s < S; s += 64) {            // 1
+      const int r = r0 + sring[s], b = ring_ptr[r], N = ring_ptr[r + 1] - b;
+      bool ok = true;
+      for (int j = 0; j < N; ++j) ok = ok && ag_atoms_in_range(n, ring_idx[b + j]);
+      const int a = ring_idx[s0 + s];
+      sx[s] = ok ? (double)p[3 * a] : (double)NAN;
+      sy[s] = ok ? (double)p[3 * a + 1] : (double)NAN;
+      sz[s] = ok ? (double)p[3 * a + 2] : (double)NAN;
+    }
+    __syncthreads();
+    for (int s = lane; s < S; s += 64) {            // 2
+      const int r = r0 + sring[s], lb = ring_ptr[r] - s0, N = ring_ptr[r + 1] - s0 - lb, j = s - lb;
+      const int i1 = lb + (j + 1) % N, i2 = lb + (j + 2) % N, i3 = lb + (j + 3) % N;
+      sv[s] = fabs(ag_dihedral(sx[s], sy[s], sz[s], sx[i1], sy[i1], sz[i1], sx[i2], sy[i2], sz[i2], sx[i3], sy[i3], sz[i3]));
+    }
+    __syncthreads();
+    for (int r = r0 + lane; r < r1; r += 64) {      // 3
+      const int lb = ring_ptr[r] - s0, N = ring_ptr[r + 1] - s0 - lb;
+      const double inv = 1.0 / N;
+      double t = 0.0;
+      for (int j = 0; j < N; ++j) t += sv[lb + j];
+      if (tau) tau[(size_t)g * Rg + r] = (float)(t * inv);
+      double cx = 0.0, cy = 0.0, cz = 0.0;
+      for (int j = 0; j < N; ++j) { cx += sx[lb + j]; cy += sy[lb + j]; cz += sz[lb + j]; }
+      // (fp32 values: the three sums are finite iff every coordinate of the ring is)
+      const bool fin = ag_finite(cx) && ag_finite(cy) && ag_finite(cz);
+      cx *= inv; cy *= inv; cz *= inv;
+      double ax = 0.0, ay = 0.0, az = 0.0, bx = 0.0, by = 0.0, bz = 0.0;     // R', R''
+      for (int j = 0; j < N; ++j) {
+        double sn, cs;
+        sincospi((double)((2 * j) % (2 * N)) * inv, &sn, &cs);
+        const double dx = sx[lb + j] - cx, dy = sy[lb + j] - cy, dz = sz[lb + j] - cz;
+        ax += dx * sn; ay += dy * sn; az += dz * sn;
+        bx += dx * cs; by += dy * cs; bz += dz * cs;
+      }
+      double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+      const double nsq = nx * nx + ny * ny + nz * nz;
+      const bool ok = fin && nsq > 0.0 && ag_finite(nsq);
+      const double s = 1.0 / sqrt(nsq);
+      nx *= s; ny *= s; nz *= s;
+      double zz = 0.0;
+      for (int j = 0; j < N; ++j) {
+        const double z = ok ? (sx[lb + j] - cx) * nx + (sy[lb + j] - cy) * ny + (sz[lb + j] - cz) * nz : (double)NAN;
+        zz += z * z;
+        sv[lb + j] = z;
+      }
+      if (amp) amp[(size_t)g * Rg + r] = (float)sqrt(zz);
+    }
+    __syncthreads();
+    if (pucker) {
+      for (int s = lane; s < S; s += 64) {          // 4
+        const int r = r0 + sring[s], lb = ring_ptr[r] - s0, N = ring_ptr[r + 1] - s0 - lb, m = s - lb;
+        float* o = pucker + (size_t)g * K + (size_t)(ring_ptr[r] - 3 * r);
+        if (m >= 2 && m <= (N - 1) / 2) {
+          double a = 0.0, b = 0.0;
+          for (int j = 0; j < N; ++j) {
+            double sn, cs;
+            sincospi((double)((2 * m * j) % (2 * N)) / N, &sn, &cs);
+            a += sv[lb + j] * cs;
+            b += sv[lb + j] * sn;
+          }
+          const double f = sqrt(2.0 / N);
+          a *= f;
+          b *= -f;
+          double phi = atan2(b, a);
+          if (phi < 0.0) phi += 6.283185307179586476925;
+          const float ph = (float)phi;
+          o[2 * (m - 2)] = (float)sqrt(a * a + b * b);
+          o[2 * (m - 2) + 1] = ph >= 6.2831855f ? 0.0f : ph;       // (the fp32 nearest to 2 pi lies above it)
+        } else if (!(N & 1) && m == N / 2) {
+          double a = 0.0;
+          for (int j = 0; j < N; ++j) a += (j & 1) ? -sv[lb + j] : sv[lb + j];
+          o[N - 4] = (float)(a * sqrt(1.0 / N));
+        }
+      }
+    }
+    __syncthreads();                                // (the next pass writes the LDS this one reads)
+    r0 = r1;
+  }
+}
+
+// k_tfd_matrix with a scale and a parity per term (k_tfd_matrix itself is left as it is: its values are pinned bit for bit): the
+// same tiles, LDS pitch, bit layout and output rules.  The T pairs (1 / s_t, the mirror's sign: +1 where a reflection leaves the
+// value, -1 where it negates it) are staged in LDS as fp64 in front of the angle rows.
+//   S_p(x -> y) = sum_t w_t min(1, delta(x[tmap[0][t]], y[tmap[p][t]]) (1 / s_t)) / sum_t w_t, a NaN value counting 1.
+// As there, both directions accumulate in the same order with a delta that is symmetric in its arguments, so a self matrix is
+// symmetric bit for bit.
+__device__ __forceinline__ double ag_term_diff(double d, double rs) {     // d = |alpha - beta|, rs = 1 / s_t
+  const double r = fmin(fmin(d, 6.283185307179586476925 - d) * rs, 1.0);
+  return d != d ? 1.0 : r;
+}
+
+__global__ void __launch_bounds__(256) k_tfd_matrix_terms(const float* __restrict__ ang_x, const float* __restrict__ ang_y,
+                                                          const int32_t* __restrict__ tmap, const float* __restrict__ w,
+                                                          const float* __restrict__ scale, const int32_t* __restrict__ even, int R,
+                                                          int G, int Q, int T, int P, float thresh, float* __restrict__ out,
+                                                          float* __restrict__ out_mirror, uint16_t* __restrict__ bits, int pitch) {
+  const int lp = Q | 1;                             // LDS pitch in floats: odd
+  // [T][2] fp64 at the base of the dynamic LDS, 16 bytes a term.  ag_eval_smem is declared as float (4-byte aligned): the base is
+  // 8-byte aligned because this kernel has NO static __shared__, so the dynamic segment starts at LDS offset 0.  Adding a static
+  // __shared__ here would need the term pairs moved or the base rounded up.
+  double* sterm = reinterpret_cast<double*>(ag_eval_smem);
+  float* sx = ag_eval_smem + 4 * T;
+  float* sy = sx + 16 * lp;
+  const int j0 = blockIdx.y * 16, i0 = blockIdx.x * 16;
+  for (int t = threadIdx.x; t < T; t += 256) {
+    sterm[2 * t] = 1.0 / (double)scale[t];
+    sterm[2 * t + 1] = even[t] ? 1.0 : -1.0;
+  }
+  for (int t = threadIdx.x; t < 16 * Q; t += 256) {
+    const int c = t / Q, o = t % Q;
+    sx[c * lp + o] = (j0 + c < R) ? ang_x[(size_t)(j0 + c) * Q + o] : 0.0f;
+    sy[c * lp + o] = (i0 + c < G) ? ang_y[(size_t)(i0 + c) * Q + o] : 0.0f;
+  }
+  __syncthreads();
+  const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+  const bool valid = j0 + ty < R && i0 + tx < G;
+  float v = 0.0f, vm = 0.0f;
+  if (valid && T > 0) {
+    const float* x = sx + ty * lp;
+    const float* y = sy + tx * lp;
+    double wsum = 0.0;
+    for (int t = 0; t < T; ++t) wsum += w ? (double)w[t] : 1.0;
+    double best = 1e300, best_mirror = 1e300;
+    for (int p = 0; p < P; ++p) {
+      const int32_t* mp = tmap + (size_t)p * T;
+      double sxy = 0.0, syx = 0.0, mxy = 0.0, myx = 0.0;
+      for (int t = 0; t < T; ++t) {
+        const int c0 = tmap[t], cp = mp[t];
+        const double wt = w ? (double)w[t] : 1.0;
+        const double rs = sterm[2 * t], sg = sterm[2 * t + 1];
+        const double x0 = x[c0], yp = y[cp], y0 = y[c0], xp = x[cp];
+        sxy += wt * ag_term_diff(fabs(x0 - yp), rs);
+        syx += wt * ag_term_diff(fabs(y0 - xp), rs);
+        mxy += wt * ag_term_diff(fabs(x0 - sg * yp), rs);
+        myx += wt * ag_term_diff(fabs(sg * y0 - xp), rs);
+      }
+      best = fmin(best, fmin(sxy, syx));
+      best_mirror = fmin(best_mirror, fmin(mxy, myx));
+    }
+    v = (float)(best / wsum);
+    vm = (float)(best_mirror / wsum);
   }
   if (valid) {
     const size_t at = (size_t)(j0 + ty) * G + i0 + tx;
@@ -2047,6 +2245,50 @@ extern "C" int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const i
   if (smem_for(Q) > 48 * 1024 && !ag_allow_big_lds(attr_done, smem_for(AGDIFF_TFD_MAX_COLUMNS), k_tfd_matrix)) return AGDIFF_ERR_LAUNCH;
   k_tfd_matrix<<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem_for(Q), (hipStream_t)stream>>>(
       ang_x, ang_y, tmap, w, R, G, Q, T, P, thresh, out, out_mirror, (uint16_t*)bits, ag_bits_pitch(G));
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_ring_coords(const float* pos, const int32_t* ring_ptr, const int32_t* ring_idx, int32_t G, int32_t n, int32_t Rg,
+                                  float* tau, float* amp, float* pucker, void* stream) {
+  if (!pos || G < 0 || n <= 0 || Rg < 0 || (Rg > 0 && (!ring_ptr || !ring_idx)) || (!tau && !amp && !pucker)) return AGDIFF_ERR_ARG;
+  if (G == 0 || Rg == 0) return AGDIFF_OK;
+  // the ring sizes, read back in pieces of a fixed host buffer (consecutive pieces share one word): the kernel's passes rely on them
+  int32_t host[1024];
+  for (int32_t r0 = 0; r0 < Rg; r0 += 1023) {
+    const int32_t words = (Rg - r0 < 1023 ? Rg - r0 : 1023) + 1;
+    if (hipMemcpyAsync(host, ring_ptr + r0, (size_t)words * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+        hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
+      (void)hipGetLastError();
+      return AGDIFF_ERR_LAUNCH;
+    }
+    if (r0 == 0 && host[0] != 0) return AGDIFF_ERR_ARG;
+    for (int32_t k = 0; k + 1 < words; ++k) {
+      const int64_t size = (int64_t)host[k + 1] - host[k];
+      if (size < 4 || size > AGDIFF_RING_MAX_ATOMS) return AGDIFF_ERR_LIMIT;
+    }
+  }
+  k_ring_coords<<<dim3((unsigned)G), dim3(64), 0, (hipStream_t)stream>>>(pos, ring_ptr, ring_idx, n, Rg, tau, amp, pucker);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_tfd_matrix_terms(const float* ang_x, const float* ang_y, const int32_t* tmap, const float* w, const float* scale,
+                                       const int32_t* even, int32_t R, int32_t G, int32_t Q, int32_t T, int32_t P, float thresh,
+                                       float* out, float* out_mirror, uint64_t* bits, void* stream) {
+  if (R < 0 || G < 0 || Q < 0 || T < 0 || T > Q || P < 1 || (Q > 0 && (!ang_x || !ang_y)) || (T > 0 && (!tmap || !scale || !even)))
+    return AGDIFF_ERR_ARG;
+  if ((!out && !out_mirror && !bits) || (out_mirror && out_mirror == out)) return AGDIFF_ERR_ARG;
+  if (bits && (!(thresh >= 0.0f) || ((uintptr_t)bits & 7))) return AGDIFF_ERR_ARG;
+  if (Q > AGDIFF_TFD_MAX_COLUMNS) return AGDIFF_ERR_LIMIT;
+  if (R == 0 || G == 0) return AGDIFF_OK;
+  const auto smem_for = [](int q, int t) { return (size_t)t * 2 * sizeof(double) + (size_t)2 * 16 * (q | 1) * sizeof(float); };
+  static std::atomic<uint64_t> attr_done{0};
+  if (smem_for(Q, T) > 48 * 1024 &&
+      !ag_allow_big_lds(attr_done, smem_for(AGDIFF_TFD_MAX_COLUMNS, AGDIFF_TFD_MAX_COLUMNS), k_tfd_matrix_terms))
+    return AGDIFF_ERR_LAUNCH;
+  k_tfd_matrix_terms<<<dim3((unsigned)((G + 15) / 16), (unsigned)((R + 15) / 16)), dim3(256), smem_for(Q, T), (hipStream_t)stream>>>(
+      ang_x, ang_y, tmap, w, scale, even, R, G, Q, T, P, thresh, out, out_mirror, (uint16_t*)bits, ag_bits_pitch(G));
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -157,12 +157,15 @@ def get_rmsd_confusion_matrix(data, useFF=False, device="cuda", hands=False):
     return (out, mirror) if hands else out
 
 
-def get_tfd_confusion_matrix(data, hands=False, device="cuda", weights=None):
+def get_tfd_confusion_matrix(data, hands=False, device="cuda", weights=None, rings=False):
     """The confusion matrix of get_rmsd_confusion_matrix with the torsion fingerprint deviation (agdiff_amd.torsions: the mean
     circular difference of the rotatable bonds' dihedrals, in [0, 1], minimised over the molecule's symmetry) in the RMSD's place:
     float32 [num_ref, num_gen] on `device`.  The item must carry its bonds.  hands=True: (proper, mirror), mirror being the TFD
-    of every generated conformer's mirror image (a reflection negates every dihedral)."""
+    of every generated conformer's mirror image (a reflection negates every dihedral).  rings=True: with the molecule's rings as
+    terms behind the rotatable bonds (agdiff_amd.rings; a reflection leaves a ring's value as it is)."""
     from .torsions import tfd_matrix
+    if rings:                # (passed only when set: without it this is the call it was before)
+        return tfd_matrix(data, hands=hands, weights=weights, device=device, rings=True)
     return tfd_matrix(data, hands=hands, weights=weights, device=device)
 
 
@@ -221,10 +224,11 @@ class CovMatEvaluator(object):
     `mirror_nearest`, per molecule the fraction of generated conformers whose nearest reference is reached through the mirror
     image.  No stereo tags are needed: it shows what handedness costs a run.  `confusion_fn` must then return (proper, mirror).
     metric="tfd": the same reductions and table over get_tfd_confusion_matrix; the thresholds then default to 0.01 .. 0.60 in
-    steps of 0.01 (for the RMSD, as in the reference, 0.05 .. 3.00 Angstrom in steps of 0.05)."""
+    steps of 0.01 (for the RMSD, as in the reference, 0.05 .. 3.00 Angstrom in steps of 0.05).  tfd_rings=True: with the rings as
+    terms of the TFD (get_tfd_confusion_matrix(rings=True))."""
 
     def __init__(self, num_workers=8, use_force_field=False, thresholds=None, ratio=2,
-                 filter_disconnected=True, print_fn=print, confusion_fn=None, either_hand=False, metric="rmsd"):
+                 filter_disconnected=True, print_fn=print, confusion_fn=None, either_hand=False, metric="rmsd", tfd_rings=False):
         if use_force_field:
             raise NotImplementedError("MMFF relaxation needs rdkit; not available here")
         if metric not in ("rmsd", "tfd"):
@@ -232,7 +236,12 @@ class CovMatEvaluator(object):
         if thresholds is None:
             thresholds = np.arange(0.05, 3.05, 0.05) if metric == "rmsd" else TFD_THRESHOLDS
         self.metric = metric
+        if tfd_rings and metric != "tfd":
+            raise ValueError("tfd_rings goes with metric='tfd'")
+        self.tfd_rings = bool(tfd_rings)
         self._confusion = get_rmsd_confusion_matrix if metric == "rmsd" else get_tfd_confusion_matrix
+        if self.tfd_rings:
+            self._confusion = lambda data, hands=False: get_tfd_confusion_matrix(data, hands=hands, rings=True)
         self.num_workers = num_workers
         self.use_force_field = use_force_field
         self.thresholds = np.array(thresholds).flatten()
@@ -346,6 +355,8 @@ def main(argv=None):
                     help="also print the table computed from min(proper, mirror): what the run would score were handedness free")
     ap.add_argument("--metric", default="rmsd", choices=["rmsd", "tfd"],
                     help="'tfd': COV / MAT over the torsion fingerprint deviation (thresholds 0.01 .. 0.60) instead of the RMSD")
+    ap.add_argument("--tfd-rings", action="store_true",
+                    help="with --metric tfd: the rings are terms of the TFD too (agdiff_amd.rings)")
     ap.add_argument("--ez-report", action="store_true",
                     help="also print, per molecule with E/Z tags (ez_quads_<i> + ez_<i>: agdiff_amd.ezbonds), the share of generated "
                          "conformers with a double bond of the wrong parity; the tags and bonds are read from --testset, or from --refs "
@@ -353,7 +364,7 @@ def main(argv=None):
     ap.add_argument("--testset", default=None, help="with --ez-report: the test set that carries the tags (default: --refs)")
     args = ap.parse_args(argv)
     items = [item for _, item in reference_items(args.refs, args.samples)]
-    res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand, metric=args.metric)(items)
+    res = CovMatEvaluator(ratio=args.ratio, either_hand=args.either_hand, metric=args.metric, tfd_rings=args.tfd_rings)(items)
     print_covmat_results(res)
     if args.ez_report:
         res.ez_wrong = ez_report(args.samples, args.testset or args.refs)

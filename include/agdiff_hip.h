@@ -9,7 +9,8 @@
  * [host]; all tensors are dense, row-major; indices are int32 on this side of the boundary
  * (the Python host converts from/to the reference's int64).  Every function enqueues work on
  * `stream` (a hipStream_t passed as void*) and returns 0, or a negative agdiff_status code
- * after validating its arguments on the host.  Nothing here allocates, frees or synchronises.
+ * after validating its arguments on the host.  Nothing here allocates, frees or synchronises -- with one exception, named at
+ * its entry: agdiff_ring_coords copies its ring sizes back to the host and waits for `stream` before it launches.
  *
  * Struct fields are only `void*`-sized pointers, int64_t, int32_t and float so that the
  * Python binding (agdiff_amd/_lib.py) can mirror them mechanically by parsing this header.
@@ -42,6 +43,7 @@ extern "C" {
 #define AGDIFF_RMSD_MAX_ATOMS 256  /* most (heavy) atoms per conformer in agdiff_rmsd_matrix / agdiff_rmsd_self */
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
 #define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
+#define AGDIFF_RING_MAX_ATOMS 32 /* most atoms of one ring of agdiff_ring_coords (the fewest: 4) */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
 #define AGDIFF_PLANAR_MAX_ATOMS 8 /* most atoms of one planar group of agdiff_planar_groups: a double bond with three neighbours at
                                      each end (planarity.py's rules give no more; an aromatic ring has 5 or 6) */
@@ -875,8 +877,9 @@ int agdiff_flip_double_bonds(float* pos /* [G][n][3], in place */, const int32_t
 /* ---- torsion fingerprint deviation -----------------------------------------------------------------------------------
  * The second standard metric between conformers next to the RMSD: the mean circular difference of the rotatable bonds'
  * dihedrals, in [0, 1] and independent of the molecule's size (rdkit Chem.TorsionFingerprints.GetTFDBetweenConformers /
- * GetTFDMatrix, which the reference never calls; ring torsions and rdkit's distance-from-centre weights are not built, a caller
- * passes weights).  The host finds the torsions (agdiff_amd/torsions.py).  Two calls, no atomics, deterministic bit for bit.
+ * GetTFDMatrix, which the reference never calls; rdkit's distance-from-centre weights are not built, a caller passes weights; the
+ * ring terms are opt-in, further down: agdiff_ring_coords, agdiff_tfd_matrix_terms).  The host finds the torsions
+ * (agdiff_amd/torsions.py).  Two calls, no atomics, deterministic bit for bit.
  *
  * agdiff_torsion_angles: what rdkit's rdMolTransforms.GetDihedralRad gives for every quad of every conformer.
  *   pos [G][n][3]
@@ -909,6 +912,56 @@ int agdiff_torsion_angles(const float* pos, const int32_t* quads, int32_t G, int
 int agdiff_tfd_matrix(const float* ang_x, const float* ang_y, const int32_t* tmap, const float* w, int32_t R, int32_t G,
                       int32_t Q, int32_t T, int32_t P, float thresh, float* out, float* out_mirror, uint64_t* bits,
                       void* stream);
+
+/* ---- ring conformations ----------------------------------------------------------------------------------------------
+ * The rotatable bonds above are bridges, so the TFD does not see a ring: chair and twist-boat cyclohexane are "the same
+ * conformer".  Two opt-in calls: the shape of every ring of every conformer (the ring torsion value of Schulz-Gasch et al. 2012
+ * and the Cremer-Pople puckering coordinates), and the TFD over a term list that holds rings next to bonds.  The host finds the
+ * rings (agdiff_amd/rings.py: the chordless cycles of 4 .. 12 heavy atoms; a caller may name others).  rdkit is not a
+ * dependency and agreement with its TFD is NOT claimed (it is believed not to cap a term at 1).  No atomics, deterministic bit
+ * for bit.
+ *
+ * agdiff_ring_coords:
+ *   pos [G][n][3]
+ *   ring_ptr [Rg + 1] int32   ring r holds the atoms ring_idx[ring_ptr[r] .. ring_ptr[r + 1]) in walking order, N_r of them,
+ *                             4 <= N_r <= AGDIFF_RING_MAX_ATOMS; ring_ptr[0] = 0.  DEVICE memory, like every table here; the
+ *                             launcher reads the Rg + 1 words back to check the sizes (one stream synchronisation: the call
+ *                             cannot be captured into a graph) and returns AGDIFF_ERR_LIMIT for a ring of fewer than 4 or more
+ *                             than AGDIFF_RING_MAX_ATOMS atoms, AGDIFF_ERR_ARG when ring_ptr[0] != 0.
+ *   ring_idx [ring_ptr[Rg]]   atom indices.  A ring that names an atom outside [0, n) reads nothing and has NaN in all its numbers.
+ *   tau [G][Rg] or null       (1 / N) sum_j |theta(r_j, r_j+1, r_j+2, r_j+3)|, indices mod N, j ascending, theta exactly the
+ *                             dihedral of agdiff_torsion_angles (fp64 from the fp32 positions); in [0, pi], stored as fp32; NaN
+ *                             when one of the N dihedrals is NaN.  Invariant under the start atom, the walking direction, rigid
+ *                             motion AND reflection.  It cannot tell a chair from its ring-flipped chair: only the sign of q_3 can.
+ *   Cremer-Pople (J. Am. Chem. Soc. 97, 1354 (1975)), all in fp64, every sum j ascending, stored as fp32:
+ *     c = mean r_j, d_j = r_j - c, R' = sum d_j sin(2 pi j / N), R'' = sum d_j cos(2 pi j / N), n = R' x R'' / |R' x R''|,
+ *     z_j = d_j . n;  for m = 2 .. floor((N - 1) / 2):  q_m cos(phi_m) =  sqrt(2 / N) sum z_j cos(2 pi m j / N),
+ *                                                       q_m sin(phi_m) = -sqrt(2 / N) sum z_j sin(2 pi m j / N),
+ *     q_m >= 0, phi_m in [0, 2 pi) (a phase that the fp32 store would round up to 2 pi is stored as 0); for even N the signed
+ *     q_(N/2) = sqrt(1 / N) sum (-1)^j z_j.  Every trig argument is sincospi(((2 m j) mod 2N) / N): exact at the symmetric points.
+ *     sum_m q_m^2 (+ q_(N/2)^2) = Q^2.  Amplitudes do not depend on where and which way the ring is walked; phases do.
+ *   amp [G][Rg] or null       the total amplitude Q = sqrt(sum z_j^2)
+ *   pucker [G][K] or null     K = ring_ptr[Rg] - 3 Rg: ring r's N_r - 3 numbers start at ring_ptr[r] - 3 r, in the order
+ *                             q_2, phi_2, ..., q_M, phi_M[, q_(N/2)]
+ *   amp and pucker of a ring are NaN when |R' x R''|^2 is zero or one of its coordinates is not finite.
+ * At least one output must be given; G = 0 or Rg = 0 launches nothing.  One wave per conformer, the lanes over the (ring,
+ * position) slots: a slot's dihedral, then one lane per ring for the sums that need the whole ring, then a slot per mode. */
+int agdiff_ring_coords(const float* pos, const int32_t* ring_ptr, const int32_t* ring_idx, int32_t G, int32_t n, int32_t Rg,
+                       float* tau, float* amp, float* pucker, void* stream);
+
+/* agdiff_tfd_matrix_terms: agdiff_tfd_matrix over value tables whose terms have a scale and a parity of their own -- the table of a
+ * conformer is its Q dihedral columns followed by its ring columns tau_r, the term list the T rotatable bonds followed by the
+ * rings.  Arguments, tiling, bit layout and output rules are agdiff_tfd_matrix's (Q and T count the ring columns and terms), plus
+ *   scale [T] float > 0    s_t: pi for a bond; for a ring of N atoms pi exp(-0.025 (N - 14)^2), as published (36.34 degrees for
+ *                          N = 6, 23.76 for 5, 14.78 for 4, 180 for 14)
+ *   even [T] int32         1 when a reflection leaves the term's value as it is (a ring's tau), 0 when it negates it (a dihedral)
+ *   S_p(x -> y) = sum_t w[t] min(1, delta(x[tmap[0][t]], y[tmap[p][t]]) (1 / s_t)) / sum_t w[t],  t ascending, fp64; a term with a
+ *   NaN value counts 1.  The cap keeps the value in [0, 1]: a chair (tau = 60 degrees) against a flat ring would otherwise score
+ *   1.65 on that term.  out_mirror negates y only where even[t] = 0.  For ring values in [0, pi] delta is the plain |difference|.
+ * Both are required.  With every scale pi and every flag 0 the values are agdiff_tfd_matrix's up to the rounding of 1 / pi. */
+int agdiff_tfd_matrix_terms(const float* ang_x, const float* ang_y, const int32_t* tmap, const float* w, const float* scale,
+                            const int32_t* even, int32_t R, int32_t G, int32_t Q, int32_t T, int32_t P, float thresh, float* out,
+                            float* out_mirror, uint64_t* bits, void* stream);
 
 /* ---- geometry validity -----------------------------------------------------------------------------------------------
  * A sampled conformer can be finite and still broken: a bond stretched to 2.5 A, two ring systems pushed through each other, a
