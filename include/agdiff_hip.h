@@ -750,7 +750,10 @@ int agdiff_langevin_step(const agdiff_params_t* p, const agdiff_topo_t* topo, co
  *                                           atom_idx[perms[p][k]]; null = the identity only (no symmetry: an upper bound
  *                                           of GetBestRMS)
  *   scratch [(R + G) * (3 m + 1)] floats    centred coordinates of the selected atoms (written by the call)
- *   out [R][G] */
+ *   out [R][G]
+ * A conformer with a selected coordinate that is not finite (NaN, +inf or -inf) is +inf in its whole row (a reference)
+ * or column (a generated one), in out and in out_mirror of agdiff_rmsd_matrix_hands, and every other entry keeps its
+ * bits; the atoms that atom_idx does not list are never read. */
 int agdiff_rmsd_matrix(const float* pos_ref, const float* pos_gen, const int32_t* atom_idx, const int32_t* perms,
                        int32_t R, int32_t G, int32_t n, int32_t m, int32_t P, float* scratch, float* out, void* stream);
 
@@ -775,7 +778,9 @@ int agdiff_matrix_minima(const float* mat, int32_t R, int32_t G, float* row_min,
  *                                      piece w of row i = columns 16 w .. 16 w + 15 (bit c = column 16 w + c), row pitch
  *                                      = 2 T bytes rounded up to 8; G rows; 8-byte aligned.  Read as little-endian 64-bit
  *                                      words, word l of a row holds columns 64 l .. 64 l + 63.
- * At least one of out / bits must be given. */
+ * At least one of out / bits must be given.  A conformer with a selected coordinate that is not finite is +inf in its row and
+ * its column, except on the diagonal, which stays 0; its bits follow out <= thresh like every other bit (clear for a finite
+ * thresh, the diagonal set); every other entry and bit is unchanged. */
 int agdiff_rmsd_self(const float* pos, const int32_t* atom_idx, const int32_t* perms, int32_t G, int32_t n, int32_t m,
                      int32_t P, float thresh, float* scratch, float* out, uint64_t* bits, void* stream);
 

@@ -116,6 +116,10 @@ def test_self_matrix_matches_oracle(n, G, with_perms):
     assert G < 4 or twins
     full = get_rmsd_confusion_matrix(dict(_item(at, gen, perms), pos_ref=gen.reshape(-1, 3))).cpu().numpy()
     assert np.abs(g - full).max() < ATOL
+    # csrc/eval.hip, header: the two kernels agree bit for bit because they call one pair routine.  The self kernel computes (i, j),
+    # i < j, with x = conformer i; the matrix kernel's x is the generated conformer, its column: that is entry [j][i] of the full matrix
+    iu = np.triu_indices(G, 1)
+    assert np.array_equal(g[iu].view(np.int32), full.T[iu].view(np.int32))
 
 
 # ------------------------------------------------------------------------------------------------ 2. the threshold bits
