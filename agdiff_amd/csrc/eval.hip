@@ -542,6 +542,106 @@ __global__ void __launch_bounds__(AG_BUTINA_THREADS) k_butina_cluster(const uint
   if (t == 0) n_clusters[0] = nclus;
 }
 
+// MaxMin picking over the float matrix (the rule: include/agdiff_hip.h, agdiff_maxmin_pick): ONE workgroup of AG_MAXMIN_THREADS / 64
+// waves.  Thread t owns the columns t, t + 1024, ... (AG_MAXMIN_COLS of them at the limit) and keeps their near, owner and state
+// in registers; a column >= G is ineligible from the start and is never read or written.  Every iteration: the last pick's row is
+// read with one coalesced 4-byte load per owned column (no alignment beyond the element's, any G), the min-update, then a
+// block-wide arg-max over the 64-bit keys  bits(near) << 32 | ~index  of the eligible unpicked columns -- near is a finite
+// non-negative fp32 there with -0 taken as +0, so its bit pattern orders as the value does, and the complement of the index
+// sends ties to the lowest; 0 is no candidate (a real key has a low half >= ~4095).  The arg-max is a wave reduction by shuffles,
+// 16 partials through LDS and a second reduction that every wave does for itself; the partials are double-buffered, so an
+// iteration costs ONE barrier: the buffer written in iteration r + 1 was last read before the barrier of iteration r.  The
+// outer loop is counted (at most K iterations, one dependent row read each) and every thread leaves it on the same value read
+// from LDS after the barrier.
+#define AG_MAXMIN_THREADS 1024
+#define AG_MAXMIN_WAVES (AG_MAXMIN_THREADS / 64)
+#define AG_MAXMIN_COLS (AGDIFF_PRUNE_MAX_CONFS / AG_MAXMIN_THREADS)
+static_assert(AG_MAXMIN_COLS * AG_MAXMIN_THREADS == AGDIFF_PRUNE_MAX_CONFS && AG_MAXMIN_WAVES == 16, "k_maxmin_pick: 4096 columns, 16 waves");
+
+__device__ __forceinline__ uint64_t ag_max_u64_xor(uint64_t k, int o) {
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)k, o);
+  const uint64_t other = ((uint64_t)hi << 32) | lo;
+  return other > k ? other : k;
+}
+
+__global__ void __launch_bounds__(AG_MAXMIN_THREADS) k_maxmin_pick(const float* __restrict__ dist, int G, int K, int first, float stop,
+                                                                   int32_t* __restrict__ picks, float* __restrict__ radius,
+                                                                   int32_t* __restrict__ owner, float* __restrict__ near,
+                                                                   int32_t* __restrict__ n_picked, float* __restrict__ cover) {
+  enum { OPEN = 0, PICKED = 1, OUT = 2 };           // eligible and unpicked / a pick / ineligible for good (or a column >= G)
+  __shared__ uint64_t s_part[2][AG_MAXMIN_WAVES];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  float nr[AG_MAXMIN_COLS];
+  int ow[AG_MAXMIN_COLS], state[AG_MAXMIN_COLS];
+#pragma unroll
+  for (int c = 0; c < AG_MAXMIN_COLS; ++c) {
+    const int j = t + c * AG_MAXMIN_THREADS;
+    nr[c] = j == first ? 0.0f : __builtin_inff();
+    ow[c] = j == first ? 0 : -1;
+    state[c] = j >= G ? OUT : (j == first ? PICKED : OPEN);
+  }
+  if (t == 0) { picks[0] = first; radius[0] = __builtin_inff(); }
+  int n = 1, last = first;
+  float cov = 0.0f;
+  for (int r = 0; r < K; ++r) {                     // pick r's row; n == r + 1 here
+    const float* __restrict__ row = dist + (size_t)last * (size_t)G;
+    float v[AG_MAXMIN_COLS];
+#pragma unroll
+    for (int c = 0; c < AG_MAXMIN_COLS; ++c) {
+      const int j = t + c * AG_MAXMIN_THREADS;
+      v[c] = (j < G && state[c] == OPEN) ? row[j] : 0.0f;
+    }
+    uint64_t key = 0;
+#pragma unroll
+    for (int c = 0; c < AG_MAXMIN_COLS; ++c) {
+      const int j = t + c * AG_MAXMIN_THREADS;
+      if (state[c] == OPEN) {
+        const float x = v[c] == 0.0f ? 0.0f : v[c];                  // (-0 is +0)
+        if (!(x >= 0.0f) || x == __builtin_inff()) {
+          state[c] = OUT;
+        } else {
+          if (x < nr[c]) { nr[c] = x; ow[c] = r; }
+          const uint64_t k = ((uint64_t)__float_as_uint(nr[c]) << 32) | (uint32_t)~(uint32_t)j;
+          key = k > key ? k : key;
+        }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = ag_max_u64_xor(key, o);
+    if (lane == 0) s_part[r & 1][wv] = key;
+    __syncthreads();
+    uint64_t best = s_part[r & 1][lane & (AG_MAXMIN_WAVES - 1)];
+#pragma unroll
+    for (int o = AG_MAXMIN_WAVES / 2; o > 0; o >>= 1) best = ag_max_u64_xor(best, o);
+    if (best == 0) break;                           // no candidate is left: cover = 0
+    const int cand = (int)~(uint32_t)best;
+    const float far = __uint_as_float((uint32_t)(best >> 32));
+    if (!(n < K && far > stop)) {                   // the candidate is not picked: the walk ends
+      cov = far;
+      break;
+    }
+#pragma unroll
+    for (int c = 0; c < AG_MAXMIN_COLS; ++c)
+      if (t + c * AG_MAXMIN_THREADS == cand) { state[c] = PICKED; nr[c] = 0.0f; ow[c] = n; }
+    if (t == 0) { picks[n] = cand; radius[n] = far; }
+    last = cand;
+    ++n;
+  }
+#pragma unroll
+  for (int c = 0; c < AG_MAXMIN_COLS; ++c) {
+    const int j = t + c * AG_MAXMIN_THREADS;
+    if (j < G) {
+      owner[j] = state[c] == OUT ? -1 : ow[c];
+      near[j] = state[c] == OUT ? __builtin_nanf("") : nr[c];
+    }
+  }
+  for (int i = n + t; i < K; i += AG_MAXMIN_THREADS) {
+    picks[i] = -1;
+    radius[i] = __builtin_nanf("");
+  }
+  if (t == 0) { n_picked[0] = n; cover[0] = cov; }
+}
+
 // eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
 // accumulated: returns the largest eigenvalue and its unit eigenvector q
 __device__ double ag_eigvec_max4(const double (&k)[10], double (&q)[4]) {
@@ -2176,6 +2276,26 @@ extern "C" int agdiff_butina_cluster(const uint64_t* bits, int32_t G, int32_t re
   }
   const int words = ag_bits_pitch(G) / 8;                 // 64-bit words per row
   k_butina_cluster<<<dim3(1), dim3(AG_BUTINA_THREADS), 0, (hipStream_t)stream>>>(bits, G, words, reorder, leader, count, rank, n_clusters);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32_t first, float stop, int32_t* picks, float* radius,
+                                  int32_t* owner, float* near, int32_t* n_picked, float* cover, void* stream) {
+  if (!dist || !picks || !radius || !owner || !near || !n_picked || !cover || G < 0) return AGDIFF_ERR_ARG;
+  if (G > 0 && (K < 1 || K > G || first < 0 || first >= G || stop != stop)) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) {                                     // no launch: n_picked = 0 and cover = 0 (all bits clear) by memsets on the stream
+    for (void* p : {(void*)n_picked, (void*)cover}) {
+      const hipError_t e = hipMemsetAsync(p, 0, 4, (hipStream_t)stream);
+      if (e == hipSuccess) continue;
+      (void)hipGetLastError();
+      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
+    }
+    return AGDIFF_OK;
+  }
+  k_maxmin_pick<<<dim3(1), dim3(AG_MAXMIN_THREADS), 0, (hipStream_t)stream>>>(dist, G, K, first, stop, picks, radius, owner, near, n_picked,
+                                                                            cover);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -1,0 +1,264 @@
+"""A diverse subset of a molecule's sampled conformers, of a given size -- "give me exactly 10 conformers that span what was sampled",
+for a docking run, a QM refinement or a shape screen with a budget: MaxMin picking (farthest-point sampling, what rdkit's
+MaxMinPicker is used for) over the float RMSD or TFD matrix.
+
+Everything runs on the GPU (csrc/eval.hip), and there is no CPU fallback:
+    agdiff_rmsd_self / agdiff_tfd_matrix   the symmetry-aware float matrix
+    agdiff_maxmin_pick                     the walk over that matrix, one workgroup
+    agdiff_align_conformers                Kabsch superposition of the picks
+
+The rule (include/agdiff_hip.h): pick 0 is given; after every pick each conformer's distance to its nearest pick is updated (a strict
+<, so on ties a conformer stays with the EARLIER pick); the next pick is the conformer farthest from all picks -- ties to the
+LOWEST index -- as long as fewer than k are picked and that distance is above the stop threshold.  The distance at which each
+pick was taken is the k-centre covering radius before it: how many conformers cover the ensemble to within r is read off `radius`.
+ensemble.prune_conformers and clusters.cluster_conformers take a threshold and return however many conformers it leaves; this
+takes the count.  Agreement with rdkit's MaxMinPicker is not claimed: that one draws its first pick at random.
+
+    python -m agdiff_amd.picks --samples out/samples_all.npz --testset test.npz (--count K and/or --radius T) [--tfd] [--tfd-rings]
+                               [--first I] [--align] [--fix-handedness] [--fix-double-bonds] [--drop-invalid] [--drop-bent]
+                               --out picks.npz
+"""
+import numpy as np
+
+from . import _lib
+from .ensemble import MAX_CONFS, _align, _self_rmsd, _valid_mask
+from .evaluation import selection_of
+from .ezbonds import fix_double_bonds as _fix_double_bonds
+from .molecule import check_threshold, num_atoms, sampled_items
+from .planarity import check_planarity
+from .stereo import fix_handedness as _fix_handedness
+from .validity import check_geometry
+
+
+def maxmin_pick(dist, G, k, stop=-1.0, first=0):
+    """agdiff_maxmin_pick on a float32 matrix [G, G] on the GPU: (picks int32 [k], radius float32 [k], owner int32 [G], near
+    float32 [G], n_picked int32 [1], cover float32 [1]) -- the picks in order (-1 from n_picked on), the distance at which each
+    was taken (+inf for pick 0, NaN from n_picked on), the rank of every conformer's nearest pick and the distance to it (-1 and
+    NaN for a conformer the matrix marks as unusable), the number of picks, and the covering radius they leave.  A negative
+    `stop` is no threshold.  More than AGDIFF_PRUNE_MAX_CONFS conformers: AgdiffLimitError."""
+    import torch
+    _lib.require_device_table(dist, "dist must be a contiguous float32 tensor [G, G] on the GPU")
+    if tuple(dist.shape) != (G, G):
+        raise ValueError("dist must be [%d, %d] (got %s)" % (G, G, tuple(dist.shape)))
+    dev = dist.device
+    picks = torch.empty(k, dtype=torch.int32, device=dev)
+    radius = torch.empty(k, dtype=torch.float32, device=dev)
+    owner = torch.empty(G, dtype=torch.int32, device=dev)
+    near = torch.empty(G, dtype=torch.float32, device=dev)
+    n_picked = torch.empty(1, dtype=torch.int32, device=dev)
+    cover = torch.empty(1, dtype=torch.float32, device=dev)
+    _lib.call("agdiff_maxmin_pick", dist, int(G), int(k), int(first), float(stop), picks, radius, owner, near, n_picked, cover)
+    return picks, radius, owner, near, n_picked, cover
+
+
+def _empty(total, gen, hand, ez_state):
+    """the result with no conformer to pick from: `total` conformers, all masked out"""
+    import torch
+    dev = gen.device
+    none = lambda dtype: torch.empty(0, dtype=dtype, device=dev)
+    res = {"picks": none(torch.int32), "radius": none(torch.float32),
+           "owner": torch.full((total,), -1, dtype=torch.int32, device=dev),
+           "near": torch.full((total,), float("nan"), dtype=torch.float32, device=dev), "count": none(torch.int32),
+           "cover": 0.0, "pos": gen[:0]}
+    if hand is not None:
+        res["hand"] = hand
+    if ez_state is not None:
+        res["ez_state"] = ez_state
+    return res
+
+
+def pick_conformers(item, k=None, radius=None, metric="rmsd", first=None, align=True, device="cuda", valid=None, fix_handedness=False,
+                    fix_double_bonds=False, tfd_rings=False):
+    """MaxMin picking among the item's generated conformers by their best RMSD (metric="tfd": their torsion fingerprint deviation,
+    agdiff_amd.torsions; the item must carry its bonds).  The item, `valid`, `fix_handedness`, `fix_double_bonds` and `tfd_rings`
+    are those of clusters.cluster_conformers, and the fixes run first.  A conformer with a coordinate that is not finite is left
+    out like one that `valid` masks.
+        k       at most this many picks (clamped to the number of usable conformers)
+        radius  stop once every usable conformer is within `radius` of a pick: a conformer is picked only while the farthest one
+                is farther than that.  At least one of k and radius; radius alone picks until cover <= radius.
+        first   pick 0, an index into the item's conformers; default: the first usable one.  A masked `first`: ValueError.
+    Returns a dict of tensors on `device`, in the item's own conformer indices:
+        picks   int32 [K']    the picks in pick order
+        radius  float32 [K']  the distance from the picks before it at which each was taken (+inf for pick 0), non-increasing: the
+                              covering radius of the first r picks is radius[r]
+        owner   int32 [G]     the rank (index into picks) of every conformer's nearest pick, the earlier one on ties; -1 when masked
+        near    float32 [G]   the distance to it as the matrix stores it, 0 for a pick; NaN when masked
+        count   int32 [K']    the conformers each pick owns, itself included
+        cover   float         the covering radius of all K' picks: every usable conformer is within it of a pick
+        pos     [K', n, 3]    the picks; with align=True superposed on pick 0 over the heavy atoms (that one is returned as it is,
+                              bit for bit)
+        hand, ez_state        as prune_conformers returns them, when the fixes ran
+    With no usable conformer the K'-sized tensors are empty, `owner` is all -1 and `cover` is 0.  At most AGDIFF_PRUNE_MAX_CONFS
+    conformers."""
+    import torch
+    if metric not in ("rmsd", "tfd"):
+        raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
+    if tfd_rings and metric != "tfd":
+        raise ValueError("tfd_rings goes with metric='tfd'")
+    if k is None and radius is None:
+        raise ValueError("at least one of k and radius must be given")
+    if k is not None and (int(k) != k or k < 1):
+        raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
+    stop = -1.0 if radius is None else check_threshold(radius, "RMSD")
+    gen = _lib.conformers(item["pos_gen"], num_atoms(item))
+    G = total = gen.shape[0]
+    if G == 0:
+        raise ValueError("no conformers to pick from")
+    if G > MAX_CONFS:
+        raise _lib.AgdiffLimitError("pick_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
+    mask = None if valid is None else _valid_mask(valid, G)
+    if first is not None:
+        if int(first) != first or not 0 <= first < G:
+            raise ValueError("first must be the index of a conformer, 0 .. %d (got %r)" % (G - 1, first))
+        if mask is not None and not mask[int(first)]:
+            raise ValueError("first = %d is a conformer that valid masks out" % first)
+    hand = None
+    if fix_handedness:
+        gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
+        hand = _fix_handedness(item, gen)
+    ez_state = None
+    if fix_double_bonds:
+        gen = gen.to(device).contiguous()
+        if not fix_handedness:
+            gen = gen.clone()                            # (the caller's tensor is never written)
+        ez_state = _fix_double_bonds(item, gen)
+    gen = gen.to(device).contiguous()
+    finite = torch.isfinite(gen).reshape(G, -1).all(dim=1).cpu().numpy()
+    if not finite.all():                                 # a coordinate that is not finite: masked before the matrix is made
+        mask = finite if mask is None else mask & finite
+        if first is not None and not mask[int(first)]:
+            raise ValueError("first = %d is a conformer with a coordinate that is not finite" % first)
+    sel = None
+    if mask is not None:                                 # compacted on the device; the kernels below see the usable ones only
+        sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
+        G = int(sel.shape[0])
+        if G == 0:
+            return _empty(total, gen, hand, ez_state)
+        gen = gen[sel].contiguous()
+    start = 0 if first is None else (int(first) if mask is None else int(mask[:int(first)].sum()))
+    if metric == "tfd":
+        from .torsions import _self_tfd
+        # (the keyword is passed only when set, as clusters.cluster_conformers does)
+        gen, out, _ = _self_tfd(dict(item, pos_gen=gen), device, **({"rings": True} if tfd_rings else {}))
+        idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
+    else:
+        gen, idx, out, _ = _self_rmsd(dict(item, pos_gen=gen), device)
+    limit = G if k is None else min(int(k), G)
+    picks, rad, owner, near, n_picked, cover = maxmin_pick(out, G, limit, stop=stop, first=start)
+    n = int(n_picked.item())
+    picks, rad = picks[:n], rad[:n]
+    pos = gen[picks.long()]
+    if align:
+        start_pos = pos[0].clone()
+        pos, _ = _align(pos.contiguous(), idx, start_pos)
+        pos[0] = start_pos
+    count = torch.bincount(owner[owner >= 0].long(), minlength=n).to(torch.int32)
+    res = {"picks": picks, "radius": rad, "owner": owner, "near": near, "count": count, "cover": float(cover.item()), "pos": pos}
+    if sel is not None:                                  # back to the item's own conformer indices
+        own = torch.full((total,), -1, dtype=torch.int32, device=owner.device)
+        own[sel] = owner
+        nr = torch.full((total,), float("nan"), dtype=torch.float32, device=owner.device)
+        nr[sel] = near
+        res["picks"], res["owner"], res["near"] = sel[picks.long()].to(torch.int32), own, nr
+    if hand is not None:
+        res["hand"] = hand
+    if ez_state is not None:
+        res["ez_state"] = ez_state
+    return res
+
+
+def _parser():
+    import argparse
+
+    class Parser(argparse.ArgumentParser):
+        def parse_args(self, *a, **kw):                  # (an "at least one of" group: argparse has only "exactly one of")
+            args = super().parse_args(*a, **kw)
+            if args.count is None and args.radius is None:
+                self.error("at least one of --count and --radius is required")
+            if args.tfd_rings and not args.tfd:
+                self.error("--tfd-rings goes with --tfd")
+            return args
+    ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--samples", required=True)
+    ap.add_argument("--testset", required=True)
+    ap.add_argument("--count", type=int, default=None, help="pick at most this many conformers per molecule")
+    ap.add_argument("--radius", type=float, default=None,
+                    help="stop once every conformer is within this distance of a pick (Angstrom of heavy-atom RMSD; with --tfd a TFD "
+                         "in [0, 1]); with --count, whichever comes first")
+    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
+    ap.add_argument("--tfd-rings", action="store_true",
+                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+    ap.add_argument("--first", type=int, default=None, help="the conformer picked first (default: the first one that is not left out)")
+    ap.add_argument("--align", action="store_true", help="superpose the picks on the first of them")
+    ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
+    ap.add_argument("--fix-double-bonds", action="store_true",
+                    help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
+                         "in --testset: python -m agdiff_amd.ezbonds); also writes ez_state_<i> [G, D]")
+    ap.add_argument("--drop-invalid", action="store_true",
+                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the picking")
+    ap.add_argument("--drop-bent", action="store_true",
+                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out of it")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda")
+    return ap
+
+
+def main(argv=None):
+    """python -m agdiff_amd.picks --samples samples_all.npz --testset test.npz (--count K and/or --radius T) [--tfd] [--align] --out picks.npz
+    Picks a diverse subset of a finished job's conformers (agdiff_amd.driver: `pos_gen_<i>`), MaxMin over the RMSD or TFD matrix.
+    The bonds come from the test set, so the molecules' symmetry is honoured.  Writes per molecule `pick_<i>` [K'] (pick order),
+    `radius_<i>` [K'] (the distance at which each pick was taken; +inf for the first), `owner_<i>` [G] (the rank of the nearest
+    pick; -1 when left out), `near_<i>` [G] (the distance to it; NaN when left out), `count_<i>` [K'], `cover_<i>` (the covering
+    radius of the picks), `pos_<i>` [K', n, 3] (+ `name_<i>`).  At least one of --count / --radius.  --fix-handedness,
+    --fix-double-bonds, --drop-invalid, --drop-bent: as in python -m agdiff_amd.clusters, with the same `hand_<i>`, `ez_state_<i>`,
+    `valid_<i>` and `flat_<i>`.  Prints the conformers, the picks and the largest covering radius over the molecules."""
+    args = _parser().parse_args(argv)
+    metric = "tfd" if args.tfd else "rmsd"
+    if args.radius is not None:
+        check_threshold(args.radius, "RMSD")
+    out, total, picked, covers = {}, 0, 0, []
+    for mol, item in sampled_items(args.testset, args.samples):
+        i = mol["index"]
+        if args.fix_handedness:
+            if mol.get("stereo") is None:
+                raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
+            item["stereo"] = mol["stereo"]
+        if args.fix_double_bonds:
+            if mol.get("ez_quads") is None or mol.get("ez") is None:
+                raise ValueError("--fix-double-bonds: %s has no ez_quads_%d / ez_%d (python -m agdiff_amd.ezbonds adds them)"
+                                 % (args.testset, i, i))
+            item["ez_quads"], item["ez"] = mol["ez_quads"], mol["ez"]
+        valid = None
+        if args.drop_invalid:
+            valid = check_geometry(item, device=args.device)["valid"]
+            out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
+        if args.drop_bent:
+            flat = check_planarity(item, device=args.device)["flat"]
+            out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
+            valid = flat if valid is None else valid & flat
+        res = pick_conformers(item, k=args.count, radius=args.radius, metric=metric, first=args.first, align=args.align,
+                              device=args.device, valid=valid, fix_handedness=args.fix_handedness,
+                              fix_double_bonds=args.fix_double_bonds, tfd_rings=args.tfd_rings)
+        out["pick_%d" % i] = res["picks"].cpu().numpy()
+        for key in ("radius", "owner", "near", "count", "pos"):
+            out["%s_%d" % (key, i)] = res[key].cpu().numpy()
+        out["cover_%d" % i] = np.float32(res["cover"])
+        out["name_%d" % i] = np.str_(mol["name"])
+        if "hand" in res:
+            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
+        if "ez_state" in res:
+            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
+        total += int(res["owner"].shape[0])
+        picked += int(res["picks"].shape[0])
+        covers.append(res["cover"])
+    np.savez_compressed(args.out, **out)
+    print("picked %d of %d conformers by %s (%s); largest covering radius over the molecules: %.3f"
+          % (picked, total, "TFD" if args.tfd else "RMSD",
+             ", ".join(([] if args.count is None else ["at most %d per molecule" % args.count])
+                       + ([] if args.radius is None else ["until within %.3f" % args.radius])),
+             max(covers) if covers else 0.0))
+    return out
+
+
+if __name__ == "__main__":
+    main()

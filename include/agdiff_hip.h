@@ -813,6 +813,39 @@ int agdiff_leader_prune(const uint64_t* bits, int32_t G, int32_t* keep, int32_t*
 int agdiff_butina_cluster(const uint64_t* bits, int32_t G, int32_t reorder, int32_t* leader, int32_t* count, int32_t* rank,
                           int32_t* n_clusters, void* stream);
 
+/* MaxMin picking (farthest-point sampling; what rdkit's MaxMinPicker is used for) over the FLOAT matrix that agdiff_rmsd_self or
+ * agdiff_tfd_matrix writes: a diverse subset of at most K conformers, the k-centre covering radius after every pick, and every
+ * conformer's nearest pick.  dist is [G][G] fp32, contiguous.  Only the rows of picked conformers are ever read, so the rule is
+ * defined by rows and symmetry is not required; the diagonal is never trusted (a picked column is not looked at).  The rule:
+ *   - eligibility: every conformer starts eligible.  Whenever a pick p's row is read, every column j that is unpicked and still
+ *     eligible is checked: if dist[p][j] is not a finite number >= 0 (NaN, +inf, -inf or negative), j becomes INELIGIBLE FOR GOOD.
+ *     (That is what agdiff_rmsd_self stores for a conformer with a coordinate that is not finite: +inf across its row and column.)
+ *     -0.0f counts as 0, and is taken as +0.0f.
+ *   - pick 0 is `first`, as given; radius[0] = +inf.
+ *   - after each pick p (its rank r), every eligible unpicked j is updated: if dist[p][j] < near[j] -- a strict < on the fp32
+ *     values, near[j] = +inf before the first pick -- then near[j] = dist[p][j] and owner[j] = r.  On ties owner[j] stays with
+ *     the EARLIER pick.
+ *   - the candidate is the eligible unpicked j with the largest near[j], ties to the LOWEST index.
+ *   - the candidate is picked iff fewer than K conformers are picked AND near[candidate] > stop (strict); then radius[r] =
+ *     near[candidate] as it was when chosen.  A negative `stop` is no threshold.
+ *   - the walk ends at the first candidate that is not picked, or when no candidate exists.
+ * Outputs, every entry written:
+ *   picks [K], radius [K]   in pick order; the entries from n_picked on are -1 and NaN
+ *   owner [G]               the rank (index into picks) of each conformer's nearest pick, its own rank for a pick; -1 for an
+ *                           ineligible conformer
+ *   near [G]                the distance to that pick; 0 for a pick, NaN for an ineligible conformer
+ *   n_picked [1]            the number of picks made (>= 1 for G > 0)
+ *   cover [1]               the near of the last candidate, the one that was not picked; 0 when no candidate was left.  Every
+ *                           eligible conformer is within `cover` of a pick.
+ * Every float written is a copy of a matrix entry (or 0, +inf, NaN): nothing is computed, so everything is exact.  radius[1:] is
+ * non-increasing and cover <= radius[n_picked - 1].  One workgroup, no global atomics, deterministic bit for bit; the outer loop
+ * is counted, at most K iterations, one row read each.  `dist` needs 4-byte alignment only, and any G, odd ones included.
+ * A null pointer or G < 0: AGDIFF_ERR_ARG; for G > 0, K outside [1, G], `first` outside [0, G) or a NaN `stop`: AGDIFF_ERR_ARG;
+ * G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT (the argument errors come first); G == 0: n_picked = 0, cover = 0 and no launch.
+ * Agreement with rdkit's MaxMinPicker is not claimed: that one draws its first pick at random, this one is deterministic. */
+int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32_t first, float stop, int32_t* picks, float* radius,
+                       int32_t* owner, float* near, int32_t* n_picked, float* cover, void* stream);
+
 /* Rigid superposition (rdkit AlignMolConformers: atoms keep their labels, identity mapping): for each conformer the proper
  * rotation R and translation that minimise the RMSD to `target` over the atoms `atom_idx` (Horn's quaternion, fp64), applied
  * to ALL n atoms: out = R (x - c_x) + c_target, so hydrogens ride along.  No reflection: a mirror image stays apart.  When
