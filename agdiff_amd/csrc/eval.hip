@@ -642,6 +642,200 @@ __global__ void __launch_bounds__(AG_MAXMIN_THREADS) k_maxmin_pick(const float* 
   if (t == 0) { n_picked[0] = n; cover[0] = cov; }
 }
 
+// Alternating k-medoids over the float matrix (the rule: include/agdiff_hip.h, agdiff_kmedoids).  Unlike the two walks above an
+// iteration is parallel inside, so it is a SEQUENCE OF LAUNCHES, and the kernel boundary is the only grid-wide ordering there is:
+//   k_kmed_init     one workgroup: checks the seeds (range, duplicates by LDS counters, eligibility), sets up the control words;
+//                   on a bad seed it writes the status-2 fill and sets `done`, so nothing after it does anything
+//   k_kmed_assign   64 columns per workgroup, its 4 waves take the ranks r = w, w + 4, ... of the K medoid rows (coalesced 4-byte
+//                   loads, unrolled); the keys (Q + 1) << 12 | r -- 0 << 12 | r for the medoid's own column -- are min-reduced
+//                   through LDS: lowest Q, then lowest rank.  Writes labels and near.
+//   k_kmed_costs    one wave per candidate row i: sum of Q(dist[i][j]) over the members j != i of i's cluster, uint64 partials
+//                   reduced by shuffles; writes the key cost << 12 | i (all ones for an ineligible row)
+//   k_kmed_choose   one workgroup (G keys, nothing to stream): per-cluster arg-min by LDS atomic min on the keys, the incumbent
+//                   rule, the changed flag; counts the update and sets status / done
+//   k_kmed_finish   one workgroup: size, within (uint64 LDS sums of Q(near)), cost, n_iter, status
+// The state between launches lives in the outputs (medoids, labels, near) and in `work`: 8 control words, then the G keys.
+// Every kernel of the loop reads ctl[KM_DONE] first and returns when it is set.  Sums and comparisons are on integers, LDS
+// atomics are min / add on integers, there are no global atomics and no workgroup waits on another: nothing depends on the
+// order in which workgroups run.  Every loop is counted.
+#define AG_KMED_MAX_DIST 4096.0f
+enum { KM_DONE = 0, KM_STATUS = 1, KM_ITERS = 2, KM_CTL_WORDS = 8 };     // int32 words at the head of `work`
+static_assert(AGDIFF_KMEDOIDS_WORK_BYTES >= KM_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * 8, "agdiff_kmedoids: control words + one key per conformer");
+static_assert(AGDIFF_PRUNE_MAX_CONFS == 1 << 12 && AGDIFF_KMEDOIDS_MAX_DIST == 4096, "agdiff_kmedoids: 12 index bits under a sum of 4096 terms <= 2^40");
+
+__device__ __forceinline__ bool ag_kmed_valid(float x) { return x >= 0.0f && x <= AG_KMED_MAX_DIST; }
+
+// Q(x): rint(x * 2^28) for a valid x, 2^40 otherwise.  x * 2^28 < 2^41 is exact in fp64, and adding 2^52 rounds it to an
+// integer, half to even, in the one rounding of the fma; the integer is then the low 52 bits.
+__device__ __forceinline__ uint64_t ag_kmed_q(float x) {
+  const double s = __builtin_fma((double)x, 268435456.0, 4503599627370496.0);
+  const uint64_t q = (uint64_t)__double_as_longlong(s) & ((1ull << 52) - 1);
+  return ag_kmed_valid(x) ? q : (1ull << 40);
+}
+
+__device__ __forceinline__ uint64_t ag_shfl_xor_u64(uint64_t k, int o) {
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)k, o);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+__global__ void __launch_bounds__(1024) k_kmed_init(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init,
+                                                    int32_t* __restrict__ medoids, int32_t* __restrict__ labels, float* __restrict__ near,
+                                                    int32_t* __restrict__ size, double* __restrict__ within, double* __restrict__ cost,
+                                                    int32_t* __restrict__ n_iter, int32_t* __restrict__ status, int32_t* __restrict__ ctl) {
+  __shared__ int32_t s_seen[AGDIFF_PRUNE_MAX_CONFS];
+  const int t = threadIdx.x;
+  for (int j = t; j < G; j += 1024) s_seen[j] = 0;
+  __syncthreads();
+  const int s0 = init[0];
+  const bool s0_ok = (unsigned)s0 < (unsigned)G;    // (block-uniform)
+  int bad = s0_ok ? 0 : 1;
+  if (s0_ok) {
+    for (int r = t; r < K; r += 1024) {
+      const int s = init[r];
+      if ((unsigned)s >= (unsigned)G) { bad = 1; continue; }
+      if (atomicAdd(&s_seen[s], 1) != 0) bad = 1;                           // a duplicate: somebody counted this seed before
+      if (s != s0 && !ag_kmed_valid(dist[(size_t)s0 * (size_t)G + s])) bad = 1;   // an ineligible seed
+    }
+  }
+  bad = __syncthreads_or(bad);
+  if (!bad) {
+    for (int r = t; r < K; r += 1024) medoids[r] = init[r];
+    if (t < KM_CTL_WORDS) ctl[t] = 0;
+    return;
+  }
+  for (int r = t; r < K; r += 1024) { medoids[r] = -1; size[r] = 0; within[r] = 0.0; }
+  for (int j = t; j < G; j += 1024) { labels[j] = -1; near[j] = __builtin_nanf(""); }
+  if (t < KM_CTL_WORDS) ctl[t] = t == KM_DONE ? 1 : (t == KM_STATUS ? 2 : 0);
+  if (t == 0) { cost[0] = 0.0; n_iter[0] = 0; status[0] = 2; }
+}
+
+// final = 0: an assign of the loop, skipped once `done` is set.  final = 1: the assign after the last update, which runs only
+// after a status-1 stop (after a status-0 stop the labels already belong to the returned medoids).
+__global__ void __launch_bounds__(256) k_kmed_assign(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init,
+                                                     const int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                     float* __restrict__ near, const int32_t* __restrict__ ctl, int final) {
+  if (final ? ctl[KM_STATUS] != 1 : ctl[KM_DONE] != 0) return;
+  __shared__ uint64_t s_key[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + lane;
+  const bool in = j < G;
+  const int jc = in ? j : G - 1;                    // (a column past the end reads the last one and writes nothing)
+  uint64_t key = ~0ull;
+#pragma unroll 4
+  for (int r = wv; r < K; r += 4) {
+    const int m = medoids[r];                       // (wave-uniform)
+    const float x = dist[(size_t)m * (size_t)G + jc];
+    const uint64_t k = (m == jc ? 0ull : (ag_kmed_q(x) + 1) << 12) | (uint64_t)r;
+    key = k < key ? k : key;
+  }
+  s_key[wv][lane] = key;
+  __syncthreads();
+  if (wv != 0 || !in) return;
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const uint64_t k = s_key[w][lane];
+    key = k < key ? k : key;
+  }
+  const int s0 = init[0];
+  const bool eligible = j == s0 || ag_kmed_valid(dist[(size_t)s0 * (size_t)G + j]);
+  const int r = (int)(key & 4095);
+  const float x = dist[(size_t)medoids[r] * (size_t)G + j];
+  labels[j] = eligible ? r : -1;
+  near[j] = !eligible ? __builtin_nanf("") : ((key >> 12) == 0 || x == 0.0f ? 0.0f : x);     // (-0 is written as +0)
+}
+
+__global__ void __launch_bounds__(256) k_kmed_costs(const float* __restrict__ dist, int G, const int32_t* __restrict__ labels,
+                                                    uint64_t* __restrict__ keys, const int32_t* __restrict__ ctl) {
+  if (ctl[KM_DONE] != 0) return;
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);     // (wave-uniform)
+  if (i >= G) return;
+  const int c = labels[i];
+  if (c < 0) {
+    if (lane == 0) keys[i] = ~0ull;
+    return;
+  }
+  const float* __restrict__ row = dist + (size_t)i * (size_t)G;
+  uint64_t sum = 0;
+#pragma unroll 8
+  for (int j = lane; j < G; j += 64) {
+    const float x = row[j];
+    const int l = labels[j];
+    sum += (l == c && j != i) ? ag_kmed_q(x) : 0ull;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += ag_shfl_xor_u64(sum, o);
+  if (lane == 0) keys[i] = (sum << 12) | (uint64_t)i;
+}
+
+__global__ void __launch_bounds__(1024) k_kmed_choose(int G, int K, int max_iter, const int32_t* __restrict__ labels,
+                                                      const uint64_t* __restrict__ keys, int32_t* __restrict__ medoids,
+                                                      int32_t* __restrict__ ctl) {
+  if (ctl[KM_DONE] != 0) return;                    // (block-uniform: ctl is written only after the barriers below)
+  __shared__ unsigned long long s_best[AGDIFF_PRUNE_MAX_CONFS];
+  const int t = threadIdx.x;
+  for (int r = t; r < K; r += 1024) s_best[r] = ~0ull;
+  __syncthreads();
+  for (int j = t; j < G; j += 1024) {
+    const int l = labels[j];
+    if (l >= 0) atomicMin(&s_best[l], (unsigned long long)keys[j]);   // lowest cost, then lowest index
+  }
+  __syncthreads();
+  int changed = 0;
+  for (int r = t; r < K; r += 1024) {
+    const uint64_t best = s_best[r], mine = keys[medoids[r]];
+    if ((best >> 12) != (mine >> 12)) {             // the incumbent stays when its cost equals the minimum
+      medoids[r] = (int)(best & 4095);
+      changed = 1;
+    }
+  }
+  changed = __syncthreads_or(changed);
+  if (t == 0) {
+    const int n = ctl[KM_ITERS] + 1;
+    ctl[KM_ITERS] = n;
+    if (!changed) { ctl[KM_STATUS] = 0; ctl[KM_DONE] = 1; }
+    else if (n >= max_iter) { ctl[KM_STATUS] = 1; ctl[KM_DONE] = 1; }
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_kmed_finish(int G, int K, const int32_t* __restrict__ labels, const float* __restrict__ near,
+                                                      int32_t* __restrict__ size, double* __restrict__ within, double* __restrict__ cost,
+                                                      int32_t* __restrict__ n_iter, int32_t* __restrict__ status,
+                                                      const int32_t* __restrict__ ctl) {
+  if (ctl[KM_STATUS] == 2) return;                  // a bad seed: k_kmed_init wrote everything
+  __shared__ unsigned long long s_sum[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ int32_t s_size[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ unsigned long long s_part[16];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  for (int r = t; r < K; r += 1024) { s_sum[r] = 0; s_size[r] = 0; }
+  __syncthreads();
+  uint64_t total = 0;
+  for (int j = t; j < G; j += 1024) {
+    const int l = labels[j];
+    if (l >= 0) {
+      const uint64_t q = ag_kmed_q(near[j]);
+      atomicAdd(&s_sum[l], (unsigned long long)q);
+      atomicAdd(&s_size[l], 1);
+      total += q;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) total += ag_shfl_xor_u64(total, o);
+  if (lane == 0) s_part[wv] = total;
+  __syncthreads();
+  for (int r = t; r < K; r += 1024) {
+    size[r] = s_size[r];
+    within[r] = (double)s_sum[r] * (1.0 / 268435456.0);              // (<= 2^52: exact)
+  }
+  if (t == 0) {
+    uint64_t all = 0;
+    for (int w = 0; w < 16; ++w) all += s_part[w];
+    cost[0] = (double)all * (1.0 / 268435456.0);
+    n_iter[0] = ctl[KM_ITERS];
+    status[0] = ctl[KM_STATUS];
+  }
+}
+
 // eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
 // accumulated: returns the largest eigenvalue and its unit eigenvector q
 __device__ double ag_eigvec_max4(const double (&k)[10], double (&q)[4]) {
@@ -2296,6 +2490,45 @@ extern "C" int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32
   }
   k_maxmin_pick<<<dim3(1), dim3(AG_MAXMIN_THREADS), 0, (hipStream_t)stream>>>(dist, G, K, first, stop, picks, radius, owner, near, n_picked,
                                                                             cover);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t max_iter, int32_t* medoids,
+                               int32_t* labels, float* near, int32_t* size, double* within, double* cost, int32_t* n_iter,
+                               int32_t* status, uint64_t* work, void* stream) {
+  if (!dist || !init || !medoids || !labels || !near || !size || !within || !cost || !n_iter || !status || !work || G < 0)
+    return AGDIFF_ERR_ARG;
+  if (G > 0 && (K < 1 || K > G || max_iter < 1 || max_iter > AGDIFF_KMEDOIDS_MAX_ITER)) return AGDIFF_ERR_ARG;
+  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  hipStream_t st = (hipStream_t)stream;
+  if (G == 0) {                                     // no launch: n_iter = 0, status = 0 and cost = 0 (all bits clear) by memsets on the stream
+    const std::pair<void*, size_t> outs[] = {{n_iter, 4}, {status, 4}, {cost, 8}};
+    for (const auto& o : outs) {
+      const hipError_t e = hipMemsetAsync(o.first, 0, o.second, st);
+      if (e == hipSuccess) continue;
+      (void)hipGetLastError();
+      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
+    }
+    return AGDIFF_OK;
+  }
+  int32_t* ctl = (int32_t*)work;
+  uint64_t* keys = work + KM_CTL_WORDS * 4 / 8;
+  const dim3 cols((unsigned)((G + 63) / 64)), rows((unsigned)((G + 3) / 4));
+  k_kmed_init<<<dim3(1), dim3(1024), 0, st>>>(dist, G, K, init, medoids, labels, near, size, within, cost, n_iter, status, ctl);
+  AG_CHECK_LAUNCH();
+  for (int it = 0; it < max_iter; ++it) {           // every launch returns at once after the update that ended the walk
+    k_kmed_assign<<<cols, dim3(256), 0, st>>>(dist, G, K, init, medoids, labels, near, ctl, 0);
+    AG_CHECK_LAUNCH();
+    k_kmed_costs<<<rows, dim3(256), 0, st>>>(dist, G, labels, keys, ctl);
+    AG_CHECK_LAUNCH();
+    k_kmed_choose<<<dim3(1), dim3(1024), 0, st>>>(G, K, max_iter, labels, keys, medoids, ctl);
+    AG_CHECK_LAUNCH();
+  }
+  k_kmed_assign<<<cols, dim3(256), 0, st>>>(dist, G, K, init, medoids, labels, near, ctl, 1);
+  AG_CHECK_LAUNCH();
+  k_kmed_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, near, size, within, cost, n_iter, status, ctl);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

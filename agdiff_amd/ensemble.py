@@ -115,6 +115,65 @@ def _valid_mask(valid, G):
     return v
 
 
+def _usable_matrix(item, what, metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=None):
+    """What picks.pick_conformers and medoids.medoid_conformers do before their walk: the item's conformers, the `valid` mask,
+    the fixes (the caller's tensor is never written), the masking of conformers with a coordinate that is not finite, the
+    compaction to the usable ones on the device, and their float RMSD (metric="rmsd") or TFD matrix.
+        what    the caller's name, for the messages
+        check   check(G, mask, why): the caller's own checks of conformer indices against the item's G conformers and the bool
+                mask [G] (None: nothing masked); called once before any device work with why = "that valid masks out", and again,
+                with why = "with a coordinate that is not finite", when such conformers were masked
+    Returns a namespace: total (the item's conformers), G (the usable ones), mask (bool numpy [total] or None), sel (int64 tensor
+    [G], the usable conformers' indices, or None when all are), gen [G, n, 3], idx (the heavy atoms), out [G, G] (None when
+    G == 0, with gen the uncompacted conformers), hand, ez_state (as prune_conformers returns them, or None)."""
+    import types
+    import torch
+    if metric not in ("rmsd", "tfd"):
+        raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
+    if tfd_rings and metric != "tfd":
+        raise ValueError("tfd_rings goes with metric='tfd'")
+    gen = _lib.conformers(item["pos_gen"], num_atoms(item))
+    G = total = gen.shape[0]
+    if G == 0:
+        raise ValueError("%s: the item has no conformers" % what)
+    if G > MAX_CONFS:
+        raise _lib.AgdiffLimitError("%s: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (what, G, MAX_CONFS))
+    mask = None if valid is None else _valid_mask(valid, G)
+    if check is not None:
+        check(G, mask, "that valid masks out")
+    hand = None
+    if fix_handedness:
+        gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
+        hand = _fix_handedness(item, gen)
+    ez_state = None
+    if fix_double_bonds:
+        gen = gen.to(device).contiguous()
+        if not fix_handedness:
+            gen = gen.clone()                            # (the caller's tensor is never written)
+        ez_state = _fix_double_bonds(item, gen)
+    gen = gen.to(device).contiguous()
+    finite = torch.isfinite(gen).reshape(G, -1).all(dim=1).cpu().numpy()
+    if not finite.all():                                 # a coordinate that is not finite: masked before the matrix is made
+        mask = finite if mask is None else mask & finite
+        if check is not None:
+            check(G, mask, "with a coordinate that is not finite")
+    res = types.SimpleNamespace(total=total, G=G, mask=mask, sel=None, gen=gen, idx=None, out=None, hand=hand, ez_state=ez_state)
+    if mask is not None:                                 # compacted on the device; the kernels see the usable ones only
+        res.sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
+        res.G = int(res.sel.shape[0])
+        if res.G == 0:
+            return res
+        gen = gen[res.sel].contiguous()
+    if metric == "tfd":
+        from .torsions import _self_tfd
+        # (the keyword is passed only when set, as clusters.cluster_conformers does)
+        res.gen, res.out, _ = _self_tfd(dict(item, pos_gen=gen), device, **({"rings": True} if tfd_rings else {}))
+        res.idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
+    else:
+        res.gen, res.idx, res.out, _ = _self_rmsd(dict(item, pos_gen=gen), device)
+    return res
+
+
 def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=False, metric="rmsd", fix_double_bonds=False,
                      valid=None):
     """RDKit's pruneRmsThresh rule over the item's generated conformers, in their order: a conformer is kept iff its best RMSD

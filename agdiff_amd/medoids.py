@@ -1,0 +1,267 @@
+"""K representative conformers of a molecule's sampled ensemble, with their populations -- "the five families that were sampled,
+the structure in the middle of each and the share of the ensemble it stands for", for a docking run, a QM refinement or a report;
+with K = 1, the most central conformer.  Alternating k-medoids (Voronoi iteration) over the float RMSD or TFD matrix.
+
+Everything runs on the GPU (csrc/eval.hip), and there is no CPU fallback:
+    agdiff_rmsd_self / agdiff_tfd_matrix   the symmetry-aware float matrix
+    agdiff_maxmin_pick                     the seeds (init="maxmin")
+    agdiff_kmedoids                        the walk over that matrix: three grid-wide launches per iteration
+    agdiff_align_conformers                Kabsch superposition of the medoids
+
+The rule (include/agdiff_hip.h): from K seeds, every conformer goes to its nearest medoid (ties to the LOWEST rank), then in
+every cluster the member with the smallest sum of distances to the other members becomes the medoid (ties to the lowest index,
+but an incumbent whose sum equals the minimum stays), until an update changes nothing or `max_iter` updates were made.  All sums
+are made on a fixed-point image of the matrix (2^-28), so the result is exact and does not depend on any order.
+picks.pick_conformers returns the extremes of the ensemble and clusters.cluster_conformers takes a threshold and returns
+however many families it leaves; this takes the count and returns centres.
+
+What this is not: it is not PAM's swap phase -- a medoid only ever moves inside its own cluster -- there is no k-means++
+seeding and there are no silhouette scores.  The result is a local optimum that depends on the seeds; MaxMin seeds start from
+the outliers of the ensemble, and on random point clouds they can end at a slightly worse optimum than plain seeds
+(init="first").  Agreement with any other package's k-medoids is not claimed.
+
+    python -m agdiff_amd.medoids --samples out/samples_all.npz --testset test.npz --count K [--tfd] [--tfd-rings]
+                                 [--init maxmin|first] [--max-iter N] [--align] [--fix-handedness] [--fix-double-bonds]
+                                 [--drop-invalid] [--drop-bent] --out medoids.npz
+"""
+import numpy as np
+
+from . import _lib
+from .ensemble import _align, _usable_matrix
+from .molecule import sampled_items
+from .picks import maxmin_pick
+from .planarity import check_planarity
+from .validity import check_geometry
+
+MAX_ITER = _lib.DEFINES["AGDIFF_KMEDOIDS_MAX_ITER"]
+WORK_BYTES = _lib.DEFINES["AGDIFF_KMEDOIDS_WORK_BYTES"]
+
+
+def kmedoids(dist, G, init, max_iter=32):
+    """agdiff_kmedoids on a float32 matrix [G, G] on the GPU from the seeds `init` (int32 tensor [K] on the GPU, the medoids of
+    rank 0 .. K - 1): (medoids int32 [K], labels int32 [G], near float32 [G], size int32 [K], within float64 [K], cost float64
+    [1], n_iter int32 [1], status int32 [1]) -- the medoid of each rank, the rank of every conformer's cluster and the distance
+    to its medoid as the matrix stores it (-1 and NaN for a conformer that init[0]'s row marks as unusable), the members and the
+    summed distance of each cluster, the total, the number of updates made and 0 (converged) / 1 (stopped at max_iter) / 2 (a seed
+    out of range, twice, or unusable: nothing was computed).  More than AGDIFF_PRUNE_MAX_CONFS conformers: AgdiffLimitError."""
+    import torch
+    _lib.require_device_table(dist, "dist must be a contiguous float32 tensor [G, G] on the GPU")
+    if tuple(dist.shape) != (G, G):
+        raise ValueError("dist must be [%d, %d] (got %s)" % (G, G, tuple(dist.shape)))
+    if not (torch.is_tensor(init) and init.is_cuda and init.dtype == torch.int32 and init.dim() == 1 and init.is_contiguous()):
+        raise ValueError("init must be a contiguous int32 tensor [K] on the GPU")
+    if int(max_iter) != max_iter or not 1 <= max_iter <= MAX_ITER:
+        raise ValueError("max_iter must be a count in 1 .. %d (got %r)" % (MAX_ITER, max_iter))
+    dev, K = dist.device, int(init.shape[0])
+    medoids = torch.empty(K, dtype=torch.int32, device=dev)
+    labels = torch.empty(G, dtype=torch.int32, device=dev)
+    near = torch.empty(G, dtype=torch.float32, device=dev)
+    size = torch.empty(K, dtype=torch.int32, device=dev)
+    within = torch.empty(K, dtype=torch.float64, device=dev)
+    cost = torch.empty(1, dtype=torch.float64, device=dev)
+    n_iter = torch.empty(1, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    work = torch.empty(WORK_BYTES // 8, dtype=torch.int64, device=dev)
+    _lib.call("agdiff_kmedoids", dist, int(G), K, init, int(max_iter), medoids, labels, near, size, within, cost, n_iter, status, work)
+    return medoids, labels, near, size, within, cost, n_iter, status
+
+
+def _empty(total, gen, hand, ez_state):
+    """the result with no usable conformer: `total` conformers, all masked out"""
+    import torch
+    dev = gen.device
+    none = lambda dtype: torch.empty(0, dtype=dtype, device=dev)
+    res = {"medoids": none(torch.int32), "labels": torch.full((total,), -1, dtype=torch.int32, device=dev),
+           "near": torch.full((total,), float("nan"), dtype=torch.float32, device=dev), "count": none(torch.int32),
+           "population": none(torch.float32), "within": none(torch.float64), "cost": 0.0, "iters": 0, "converged": True,
+           "pos": gen[:0]}
+    if hand is not None:
+        res["hand"] = hand
+    if ez_state is not None:
+        res["ez_state"] = ez_state
+    return res
+
+
+def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=True, device="cuda", valid=None, fix_handedness=False,
+                      fix_double_bonds=False, tfd_rings=False):
+    """k-medoids among the item's generated conformers by their best RMSD (metric="tfd": their torsion fingerprint deviation,
+    agdiff_amd.torsions; the item must carry its bonds).  The item, `valid`, `fix_handedness`, `fix_double_bonds` and `tfd_rings`
+    are those of picks.pick_conformers, and the fixes run first.  A conformer with a coordinate that is not finite is left out
+    like one that `valid` masks.
+        k         the number of medoids (clamped to the number of usable conformers)
+        init      the seeds: "maxmin", the first k MaxMin picks from the first usable conformer (fewer picks: that many medoids);
+                  "first", the first k usable conformers; or a sequence of k distinct usable conformer indices in the item's own
+                  numbering, the medoids of rank 0 .. k - 1 (a masked, repeated or out-of-range one: ValueError)
+        max_iter  at most this many updates, 1 .. AGDIFF_KMEDOIDS_MAX_ITER
+    Returns a dict in the item's own conformer indices, tensors on `device`:
+        medoids     int32 [K]     the medoid of each rank; rank r descends from seed r
+        labels      int32 [G]     the rank of every conformer's cluster; -1 when masked
+        near        float32 [G]   the distance to its medoid as the matrix stores it, 0 for a medoid; NaN when masked
+        count       int32 [K]     the members of each cluster, the medoid included
+        population  float32 [K]   count / the number of usable conformers, one correctly rounded fp32 division
+        within      float64 [K]   each cluster's summed distance to its medoid (on the 2^-28 grid)
+        cost        float         their total: what the walk lowers
+        iters       int           the updates made, counting the one that changed nothing
+        converged   bool          False when max_iter updates were made and the last one still moved a medoid
+        pos         [K, n, 3]     the medoids; with align=True superposed on rank 0 over the heavy atoms (that one is returned as it
+                                  is, bit for bit)
+        hand, ez_state            as prune_conformers returns them, when the fixes ran
+    With no usable conformer the K-sized tensors are empty, `labels` is all -1 and `cost` is 0.  At most AGDIFF_PRUNE_MAX_CONFS
+    conformers.  Not PAM, no k-means++, a local optimum that depends on the seeds: see the module's docstring."""
+    import torch
+    if int(k) != k or k < 1:
+        raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
+    if int(max_iter) != max_iter or not 1 <= max_iter <= MAX_ITER:
+        raise ValueError("max_iter must be a count in 1 .. %d (got %r)" % (MAX_ITER, max_iter))
+    seeds = None
+    if not isinstance(init, str):
+        seeds = [s for s in np.asarray(init).reshape(-1).tolist()]
+        if len(seeds) != k or any(int(s) != s for s in seeds) or len(set(seeds)) != len(seeds):
+            raise ValueError("init must be 'maxmin', 'first' or %d distinct conformer indices (got %r)" % (k, init))
+        seeds = [int(s) for s in seeds]
+    elif init not in ("maxmin", "first"):
+        raise ValueError("init must be 'maxmin', 'first' or a sequence of conformer indices (got %r)" % (init,))
+
+    def check_seeds(G, mask, why):
+        for s in seeds or ():
+            if not 0 <= s < G:
+                raise ValueError("init: %d is not the index of a conformer, 0 .. %d" % (s, G - 1))
+            if mask is not None and not mask[s]:
+                raise ValueError("init: %d is a conformer %s" % (s, why))
+    m = _usable_matrix(item, "medoid_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_seeds)
+    if m.G == 0:
+        return _empty(m.total, m.gen, m.hand, m.ez_state)
+    G, out, dev = m.G, m.out, m.out.device
+    K = min(int(k), G)
+    if seeds is not None:                                # (K == k: the seeds are distinct usable conformers) in compacted numbering
+        first = torch.tensor(seeds if m.mask is None else [int(m.mask[:s].sum()) for s in seeds], dtype=torch.int32, device=dev)
+    elif init == "first":
+        first = torch.arange(K, dtype=torch.int32, device=dev)
+    else:
+        picks, _, _, _, n_picked, _ = maxmin_pick(out, G, K)
+        K = int(n_picked.item())
+        first = picks[:K].contiguous()
+    medoids, labels, near, size, within, cost, n_iter, status = kmedoids(out, G, first, max_iter=max_iter)
+    status = int(status.item())
+    if status == 2:
+        raise ValueError("init: a seed is as far from conformer %d as the matrix can say (not a number >= 0 and <= %d): the "
+                         "seeds must be usable together" % (seeds[0] if seeds else 0, _lib.DEFINES["AGDIFF_KMEDOIDS_MAX_DIST"]))
+    pos = m.gen[medoids.long()]
+    if align:
+        start_pos = pos[0].clone()
+        pos, _ = _align(pos.contiguous(), m.idx, start_pos)
+        pos[0] = start_pos
+    counts = size.cpu().numpy()                          # (the division on the host: one correctly rounded fp32 quotient each)
+    population = torch.from_numpy(counts.astype(np.float32) / np.float32(max(int(counts.sum()), 1))).to(dev)
+    res = {"medoids": medoids, "labels": labels, "near": near, "count": size,
+           "population": population, "within": within, "cost": float(cost.item()),
+           "iters": int(n_iter.item()), "converged": status == 0, "pos": pos}
+    if m.sel is not None:                                # back to the item's own conformer indices
+        lab = torch.full((m.total,), -1, dtype=torch.int32, device=dev)
+        lab[m.sel] = labels
+        nr = torch.full((m.total,), float("nan"), dtype=torch.float32, device=dev)
+        nr[m.sel] = near
+        res["medoids"], res["labels"], res["near"] = m.sel[medoids.long()].to(torch.int32), lab, nr
+    if m.hand is not None:
+        res["hand"] = m.hand
+    if m.ez_state is not None:
+        res["ez_state"] = m.ez_state
+    return res
+
+
+def _parser():
+    import argparse
+
+    class Parser(argparse.ArgumentParser):
+        def parse_args(self, *a, **kw):
+            args = super().parse_args(*a, **kw)
+            if args.count < 1:
+                self.error("--count must be at least 1")
+            if not 1 <= args.max_iter <= MAX_ITER:
+                self.error("--max-iter must be in 1 .. %d" % MAX_ITER)
+            if args.tfd_rings and not args.tfd:
+                self.error("--tfd-rings goes with --tfd")
+            return args
+    ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--samples", required=True)
+    ap.add_argument("--testset", required=True)
+    ap.add_argument("--count", type=int, required=True, help="the number of medoids per molecule")
+    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
+    ap.add_argument("--tfd-rings", action="store_true",
+                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+    ap.add_argument("--init", choices=("maxmin", "first"), default="maxmin",
+                    help="the seeds: the first K MaxMin picks (agdiff_amd.picks), or the first K conformers that are not left out")
+    ap.add_argument("--max-iter", type=int, default=32, help="at most this many updates (1 .. %d)" % MAX_ITER)
+    ap.add_argument("--align", action="store_true", help="superpose the medoids on the first of them")
+    ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
+    ap.add_argument("--fix-double-bonds", action="store_true",
+                    help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
+                         "in --testset: python -m agdiff_amd.ezbonds); also writes ez_state_<i> [G, D]")
+    ap.add_argument("--drop-invalid", action="store_true",
+                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out")
+    ap.add_argument("--drop-bent", action="store_true",
+                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda")
+    return ap
+
+
+def main(argv=None):
+    """python -m agdiff_amd.medoids --samples samples_all.npz --testset test.npz --count K [--tfd] [--init maxmin|first] [--align] --out medoids.npz
+    K representative conformers of a finished job's molecules (agdiff_amd.driver: `pos_gen_<i>`) with their populations:
+    k-medoids over the RMSD or TFD matrix.  The bonds come from the test set, so the molecules' symmetry is honoured.  Writes per
+    molecule `medoid_<i>` [K], `cluster_<i>` [G] (the rank of each conformer's cluster; -1 when left out), `dist_<i>` [G] (the
+    distance to its medoid; NaN when left out), `count_<i>` [K], `population_<i>` [K] (the share of the conformers that were
+    not left out), `within_<i>` float64 [K], `cost_<i>` float64, `iters_<i>` int32, `converged_<i>` int8, `pos_<i>` [K, n, 3]
+    (+ `name_<i>`).  --fix-handedness, --fix-double-bonds, --drop-invalid, --drop-bent: as in python -m agdiff_amd.picks, with the
+    same `hand_<i>`, `ez_state_<i>`, `valid_<i>` and `flat_<i>`.  Prints the conformers, the medoids, the molecules that did not
+    converge and the largest population of a medoid."""
+    args = _parser().parse_args(argv)
+    metric = "tfd" if args.tfd else "rmsd"
+    out, total, found, open_, top = {}, 0, 0, 0, 0.0
+    for mol, item in sampled_items(args.testset, args.samples):
+        i = mol["index"]
+        if args.fix_handedness:
+            if mol.get("stereo") is None:
+                raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
+            item["stereo"] = mol["stereo"]
+        if args.fix_double_bonds:
+            if mol.get("ez_quads") is None or mol.get("ez") is None:
+                raise ValueError("--fix-double-bonds: %s has no ez_quads_%d / ez_%d (python -m agdiff_amd.ezbonds adds them)"
+                                 % (args.testset, i, i))
+            item["ez_quads"], item["ez"] = mol["ez_quads"], mol["ez"]
+        valid = None
+        if args.drop_invalid:
+            valid = check_geometry(item, device=args.device)["valid"]
+            out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
+        if args.drop_bent:
+            flat = check_planarity(item, device=args.device)["flat"]
+            out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
+            valid = flat if valid is None else valid & flat
+        res = medoid_conformers(item, args.count, metric=metric, init=args.init, max_iter=args.max_iter, align=args.align,
+                                device=args.device, valid=valid, fix_handedness=args.fix_handedness,
+                                fix_double_bonds=args.fix_double_bonds, tfd_rings=args.tfd_rings)
+        for key, name in (("medoids", "medoid"), ("labels", "cluster"), ("near", "dist"), ("count", "count"),
+                          ("population", "population"), ("within", "within"), ("pos", "pos")):
+            out["%s_%d" % (name, i)] = res[key].cpu().numpy()
+        out["cost_%d" % i] = np.float64(res["cost"])
+        out["iters_%d" % i] = np.int32(res["iters"])
+        out["converged_%d" % i] = np.int8(res["converged"])
+        out["name_%d" % i] = np.str_(mol["name"])
+        if "hand" in res:
+            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
+        if "ez_state" in res:
+            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
+        total += int(res["labels"].shape[0])
+        found += int(res["medoids"].shape[0])
+        open_ += 0 if res["converged"] else 1
+        top = max([top] + res["population"].cpu().tolist())
+    np.savez_compressed(args.out, **out)
+    print("%d medoids of %d conformers by %s (%d per molecule, %s seeds, at most %d updates; %d molecules did not converge); "
+          "largest population of a medoid: %.3f" % (found, total, "TFD" if args.tfd else "RMSD", args.count, args.init, args.max_iter,
+                                                     open_, top))
+    return out
+
+
+if __name__ == "__main__":
+    main()

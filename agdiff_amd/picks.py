@@ -21,12 +21,9 @@ takes the count.  Agreement with rdkit's MaxMinPicker is not claimed: that one d
 import numpy as np
 
 from . import _lib
-from .ensemble import MAX_CONFS, _align, _self_rmsd, _valid_mask
-from .evaluation import selection_of
-from .ezbonds import fix_double_bonds as _fix_double_bonds
-from .molecule import check_threshold, num_atoms, sampled_items
+from .ensemble import _align, _usable_matrix
+from .molecule import check_threshold, sampled_items
 from .planarity import check_planarity
-from .stereo import fix_handedness as _fix_handedness
 from .validity import check_geometry
 
 
@@ -91,58 +88,24 @@ def pick_conformers(item, k=None, radius=None, metric="rmsd", first=None, align=
     With no usable conformer the K'-sized tensors are empty, `owner` is all -1 and `cover` is 0.  At most AGDIFF_PRUNE_MAX_CONFS
     conformers."""
     import torch
-    if metric not in ("rmsd", "tfd"):
-        raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
-    if tfd_rings and metric != "tfd":
-        raise ValueError("tfd_rings goes with metric='tfd'")
     if k is None and radius is None:
         raise ValueError("at least one of k and radius must be given")
     if k is not None and (int(k) != k or k < 1):
         raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
     stop = -1.0 if radius is None else check_threshold(radius, "RMSD")
-    gen = _lib.conformers(item["pos_gen"], num_atoms(item))
-    G = total = gen.shape[0]
-    if G == 0:
-        raise ValueError("no conformers to pick from")
-    if G > MAX_CONFS:
-        raise _lib.AgdiffLimitError("pick_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
-    mask = None if valid is None else _valid_mask(valid, G)
-    if first is not None:
+
+    def check_first(G, mask, why):
+        if first is None:
+            return
         if int(first) != first or not 0 <= first < G:
             raise ValueError("first must be the index of a conformer, 0 .. %d (got %r)" % (G - 1, first))
         if mask is not None and not mask[int(first)]:
-            raise ValueError("first = %d is a conformer that valid masks out" % first)
-    hand = None
-    if fix_handedness:
-        gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
-        hand = _fix_handedness(item, gen)
-    ez_state = None
-    if fix_double_bonds:
-        gen = gen.to(device).contiguous()
-        if not fix_handedness:
-            gen = gen.clone()                            # (the caller's tensor is never written)
-        ez_state = _fix_double_bonds(item, gen)
-    gen = gen.to(device).contiguous()
-    finite = torch.isfinite(gen).reshape(G, -1).all(dim=1).cpu().numpy()
-    if not finite.all():                                 # a coordinate that is not finite: masked before the matrix is made
-        mask = finite if mask is None else mask & finite
-        if first is not None and not mask[int(first)]:
-            raise ValueError("first = %d is a conformer with a coordinate that is not finite" % first)
-    sel = None
-    if mask is not None:                                 # compacted on the device; the kernels below see the usable ones only
-        sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
-        G = int(sel.shape[0])
-        if G == 0:
-            return _empty(total, gen, hand, ez_state)
-        gen = gen[sel].contiguous()
+            raise ValueError("first = %d is a conformer %s" % (first, why))
+    m = _usable_matrix(item, "pick_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_first)
+    total, G, mask, sel, gen, idx, out, hand, ez_state = m.total, m.G, m.mask, m.sel, m.gen, m.idx, m.out, m.hand, m.ez_state
+    if G == 0:
+        return _empty(total, gen, hand, ez_state)
     start = 0 if first is None else (int(first) if mask is None else int(mask[:int(first)].sum()))
-    if metric == "tfd":
-        from .torsions import _self_tfd
-        # (the keyword is passed only when set, as clusters.cluster_conformers does)
-        gen, out, _ = _self_tfd(dict(item, pos_gen=gen), device, **({"rings": True} if tfd_rings else {}))
-        idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
-    else:
-        gen, idx, out, _ = _self_rmsd(dict(item, pos_gen=gen), device)
     limit = G if k is None else min(int(k), G)
     picks, rad, owner, near, n_picked, cover = maxmin_pick(out, G, limit, stop=stop, first=start)
     n = int(n_picked.item())

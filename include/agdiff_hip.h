@@ -42,7 +42,10 @@ extern "C" {
 #define AGDIFF_MAX_CHUNK_TILES 8   /* most tiles one wave walks per chunk in the fused CFConv kernel (128 edges) */
 #define AGDIFF_RMSD_MAX_ATOMS 256  /* most (heavy) atoms per conformer in agdiff_rmsd_matrix / agdiff_rmsd_self */
 #define AGDIFF_PRUNE_MAX_CONFS 4096 /* most conformers of agdiff_leader_prune: one wave holds the kept set, 64 lanes x 64 bits */
-#define AGDIFF_TFD_MAX_COLUMNS 512 /* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
+#define AGDIFF_KMEDOIDS_MAX_DIST 4096 /* agdiff_kmedoids: a matrix entry above this (or not >= 0) counts as this far: 2^40 in fixed point */
+#define AGDIFF_KMEDOIDS_MAX_ITER 128 /* most updates agdiff_kmedoids may be asked for: it enqueues three launches for each */
+#define AGDIFF_KMEDOIDS_WORK_BYTES 131072 /* the scratch agdiff_kmedoids is handed: control words and one 64-bit key per conformer */
+#define AGDIFF_TFD_MAX_COLUMNS 512/* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_RING_MAX_ATOMS 32 /* most atoms of one ring of agdiff_ring_coords (the fewest: 4) */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
 #define AGDIFF_PLANAR_MAX_ATOMS 8 /* most atoms of one planar group of agdiff_planar_groups: a double bond with three neighbours at
@@ -845,6 +848,56 @@ int agdiff_butina_cluster(const uint64_t* bits, int32_t G, int32_t reorder, int3
  * Agreement with rdkit's MaxMinPicker is not claimed: that one draws its first pick at random, this one is deterministic. */
 int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32_t first, float stop, int32_t* picks, float* radius,
                        int32_t* owner, float* near, int32_t* n_picked, float* cover, void* stream);
+
+/* K representative conformers with their populations: alternating k-medoids (Voronoi iteration) from K given seeds over the
+ * same FLOAT matrix, dist [G][G] fp32, contiguous.  All sums and comparisons are made on a fixed-point image of the entries, so
+ * no result depends on a summation order and everything below is exact.
+ *   - validity: valid(x) = x >= 0.0f && x <= 4096.0f (AGDIFF_KMEDOIDS_MAX_DIST).  NaN, negative values, +-inf and anything above
+ *     the cap are not valid; -0.0f is valid and counts as 0.
+ *   - the quantiser: Q(x) = uint64(rint((double)x * 2^28)), rounding half to even, for a valid x (the product is exact in fp64);
+ *     Q(x) = 2^40 for an entry that is not valid: "as far as the cap".  A sum of at most 4096 such terms is <= 2^52, so
+ *     sum << 12 | index fits 64 bits and a total divided by 2^28 is exact in fp64.
+ *   - eligibility: conformer j is eligible iff j == init[0] or valid(dist[init[0]][j]): one row decides (agdiff_rmsd_self writes
+ *     +inf across the row and column of a conformer with a coordinate that is not finite).  An ineligible conformer takes no
+ *     further part.  Among eligible conformers an entry that is not valid counts as 2^40.
+ *   - seeds: init [K] holds the medoids of rank 0 .. K - 1.  The kernel checks them: a seed outside [0, G), a duplicate seed or an
+ *     ineligible seed gives status = 2 and nothing else is computed.
+ *   - assign: a medoid belongs to its own rank, with near 0.  Every other eligible j goes to the rank r with the smallest
+ *     Q(dist[medoid_r][j]), ties to the LOWEST rank.  The rows read are the medoids' rows: symmetry is not required and the
+ *     diagonal is never read.
+ *   - update: for every cluster r and every member i, cost_i = the sum of Q(dist[i][j]) over the members j != i, taken along
+ *     row i.  The new medoid is the member with the smallest cost, ties to the LOWEST index -- but if the incumbent medoid's
+ *     cost equals that minimum, THE INCUMBENT STAYS.  With this the total cost falls strictly at every update that changes
+ *     anything, and the walk cannot cycle.
+ *   - the loop: assign and update repeat until an update changes no medoid (status = 0) or max_iter updates have been made
+ *     (status = 1).  n_iter is the number of updates made, counting the one that changed nothing.  The returned labels are
+ *     always the assignment to the returned medoids: after a status = 1 stop one more assign runs.  Ranks never change:
+ *     medoids[r] descends from init[r].
+ * Outputs, every entry written:
+ *   medoids [K]   the medoid of each rank
+ *   labels [G]    the rank of each conformer's cluster; -1 for an ineligible conformer
+ *   near [G]      a copy of dist[medoid][j] as stored, -0.0f written as +0.0f; 0 for a medoid, NaN for an ineligible conformer
+ *   size [K]      the number of members of each cluster
+ *   within [K]    each cluster's sum of Q(near) / 2^28
+ *   cost [1]      the total over all clusters
+ *   n_iter [1]    the number of updates made
+ *   status [1]    0 converged, 1 stopped at max_iter, 2 a bad seed
+ * On status = 2: medoids all -1, labels all -1, near all NaN, size 0, within 0, cost 0 and n_iter 0.
+ * work: caller-provided scratch of AGDIFF_KMEDOIDS_WORK_BYTES, 8-byte aligned; its contents are ignored on entry and unspecified
+ * on return.  `dist` needs 4-byte alignment only, and any G, odd ones included.
+ * An iteration is three launches -- assign (columns across threads, a loop over the K medoid rows), member costs (one wave per
+ * candidate row), choose (per-cluster arg-min over the keys cost << 12 | index, the incumbent rule, the done flag) -- and the
+ * call enqueues them for max_iter iterations, plus the seed check, the final assign and the sums.  Every launch reads a
+ * device-side `done` flag first and returns at once when it is set.  No cooperative launch, no workgroup waits on another, no
+ * atomics on global memory; every loop is counted; deterministic bit for bit.
+ * A null pointer or G < 0: AGDIFF_ERR_ARG; for G > 0, K outside [1, G] or max_iter outside [1, AGDIFF_KMEDOIDS_MAX_ITER]:
+ * AGDIFF_ERR_ARG; `work` not 8-byte aligned: AGDIFF_ERR_ARG; G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT (the argument errors
+ * come first); G == 0: n_iter = 0, status = 0, cost = 0 and no launch.
+ * This is not PAM's swap phase: a local optimum that depends on the seeds.  Agreement with any other package's k-medoids is not
+ * claimed. */
+int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t max_iter,
+                    int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within,
+                    double* cost, int32_t* n_iter, int32_t* status, uint64_t* work, void* stream);
 
 /* Rigid superposition (rdkit AlignMolConformers: atoms keep their labels, identity mapping): for each conformer the proper
  * rotation R and translation that minimise the RMSD to `target` over the atoms `atom_idx` (Horn's quaternion, fp64), applied
