@@ -18,13 +18,8 @@ answers "which families are there", and its centroid is the member in the middle
 import numpy as np
 
 from . import _lib
-from .ensemble import MAX_CONFS, _align, _self_rmsd, _valid_mask
-from .evaluation import selection_of
-from .ezbonds import fix_double_bonds as _fix_double_bonds
-from .molecule import check_threshold, num_atoms, sampled_items
-from .planarity import check_planarity
-from .stereo import fix_handedness as _fix_handedness
-from .validity import check_geometry
+from .ensemble import _add_shared_flags, _attach, _checked_items, _chosen, _own, _scatter, _usable_matrix, _write_tail
+from .molecule import check_threshold, sampled_items
 
 
 def butina_cluster(bits, G, reorder=True):
@@ -37,23 +32,6 @@ def butina_cluster(bits, G, reorder=True):
     n_clusters = torch.empty(1, dtype=torch.int32, device=dev)
     _lib.call("agdiff_butina_cluster", bits, G, 1 if reorder else 0, leader, count, rank, n_clusters)
     return leader, count, rank, n_clusters
-
-
-def _empty(total, gen, distances, hand, ez_state):
-    """the result with no conformer to cluster: `total` conformers, all masked out"""
-    import torch
-    dev = gen.device
-    none = lambda dtype: torch.empty(0, dtype=dtype, device=dev)
-    res = {"centroids": none(torch.int32), "leader": torch.full((total,), -1, dtype=torch.int32, device=dev),
-           "cluster": torch.full((total,), -1, dtype=torch.int32, device=dev), "count": none(torch.int32),
-           "population": none(torch.float32), "pos": gen[:0]}
-    if distances:
-        res["dist"] = torch.full((total,), float("nan"), dtype=torch.float32, device=dev)
-    if hand is not None:
-        res["hand"] = hand
-    if ez_state is not None:
-        res["ez_state"] = ez_state
-    return res
 
 
 def cluster_conformers(item, threshold, metric="rmsd", reorder=True, align=True, device="cuda", valid=None, fix_handedness=False,
@@ -74,79 +52,31 @@ def cluster_conformers(item, threshold, metric="rmsd", reorder=True, align=True,
         hand, ez_state          as prune_conformers returns them, when the fixes ran
     With no valid conformer the K-sized tensors are empty and `leader` is all -1.  At most AGDIFF_PRUNE_MAX_CONFS conformers."""
     import torch
-    if metric not in ("rmsd", "tfd"):
-        raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
-    if tfd_rings and metric != "tfd":
-        raise ValueError("tfd_rings goes with metric='tfd'")
-    t = check_threshold(threshold, "RMSD")
-    gen = _lib.conformers(item["pos_gen"], num_atoms(item))
-    G = total = gen.shape[0]
-    if G == 0:
-        raise ValueError("no conformers to cluster")
-    if G > MAX_CONFS:
-        raise _lib.AgdiffLimitError("cluster_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
-    mask = None if valid is None else _valid_mask(valid, G)
-    hand = None
-    if fix_handedness:
-        gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
-        hand = _fix_handedness(item, gen)
-    ez_state = None
-    if fix_double_bonds:
-        gen = gen.to(device).contiguous()
-        if not fix_handedness:
-            gen = gen.clone()                            # (the caller's tensor is never written)
-        ez_state = _fix_double_bonds(item, gen)
-    sel = None
-    if mask is not None:                                 # compacted on the device; the kernels below see the valid ones only
-        gen = gen.to(device).contiguous()
-        sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
-        G = int(sel.shape[0])
-        if G == 0:
-            return _empty(total, gen, distances, hand, ez_state)
-        gen = gen[sel].contiguous()
-    if metric == "tfd":
-        from .torsions import _self_tfd
-        # (the keyword is passed only when set: without the switch this is, argument for argument, the call it was before)
-        gen, out, bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=t, want_out=distances,
-                                   **({"rings": True} if tfd_rings else {}))
-        idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
-    else:
-        gen, idx, out, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=distances)
-    leader, count, rank, _ = butina_cluster(bits, G, reorder=reorder)
+    m = _usable_matrix(item, "cluster_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings,
+                       threshold=threshold, want_out=distances, finite_only=False)
+    if m.G == 0:                                         # no conformer to cluster: all masked out
+        none = lambda dtype: torch.empty(0, dtype=dtype, device=m.gen.device)
+        res = {"centroids": none(torch.int32), "leader": _scatter(m, none(torch.int32), -1),
+               "cluster": _scatter(m, none(torch.int32), -1), "count": none(torch.int32), "population": none(torch.float32),
+               "pos": m.gen[:0]}
+        if distances:
+            res["dist"] = _scatter(m, none(torch.float32), float("nan"))
+        return _attach(m, res)
+    leader, count, rank, _ = butina_cluster(m.bits, m.G, reorder=reorder)
     cent = torch.nonzero(count, as_tuple=False).reshape(-1)
     cent = cent[torch.argsort(rank[cent])]               # creation order (the ranks of the centroids are 0 .. K - 1, each once)
-    pos = gen[cent]
-    if align and pos.shape[0] > 0:
-        first = pos[0].clone()
-        pos, _ = _align(pos, idx, first)
-        pos[0] = first
     size = count[cent]
-    res = {"centroids": cent.to(torch.int32), "leader": leader, "cluster": rank, "count": size,
-           "population": size.to(torch.float32) / float(G), "pos": pos}
+    res = {"centroids": _own(m, cent), "leader": _scatter(m, _own(m, leader), -1), "cluster": _scatter(m, rank, -1), "count": size,
+           "population": size.to(torch.float32) / float(m.G), "pos": _chosen(m, cent, align)}
     if distances:
-        res["dist"] = out[leader.long(), torch.arange(G, device=out.device)]
-    if sel is not None:                                  # back to the item's own conformer indices
-        lead = torch.full((total,), -1, dtype=torch.int32, device=leader.device)
-        lead[sel] = sel[leader.long()].to(torch.int32)
-        clus = torch.full((total,), -1, dtype=torch.int32, device=leader.device)
-        clus[sel] = rank
-        res["centroids"], res["leader"], res["cluster"] = sel[cent].to(torch.int32), lead, clus
-        if distances:
-            dist = torch.full((total,), float("nan"), dtype=torch.float32, device=leader.device)
-            dist[sel] = res["dist"]
-            res["dist"] = dist
-    if hand is not None:
-        res["hand"] = hand
-    if ez_state is not None:
-        res["ez_state"] = ez_state
-    return res
+        res["dist"] = _scatter(m, m.out[leader.long(), torch.arange(m.G, device=m.out.device)], float("nan"))
+    return _attach(m, res)
 
 
 def _parser():
     import argparse
     ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--samples", required=True)
-    ap.add_argument("--testset", required=True)
+    _add_shared_flags(ap)
     how = ap.add_mutually_exclusive_group(required=True)
     how.add_argument("--rms", type=float, default=None, help="RMSD threshold in Angstrom (heavy atoms)")
     how.add_argument("--tfd", type=float, default=None,
@@ -156,17 +86,6 @@ def _parser():
     ap.add_argument("--static", action="store_true",
                     help="count the neighbours once, over all conformers (ClusterData(reordering=False)); the default counts the "
                          "conformers still unclustered at every choice")
-    ap.add_argument("--align", action="store_true", help="superpose the centroids on the first of them")
-    ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
-    ap.add_argument("--fix-double-bonds", action="store_true",
-                    help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
-                         "in --testset: python -m agdiff_amd.ezbonds); also writes ez_state_<i> [G, D]")
-    ap.add_argument("--drop-invalid", action="store_true",
-                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the clustering")
-    ap.add_argument("--drop-bent", action="store_true",
-                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out of it")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--device", default="cuda")
     return ap
 
 
@@ -183,36 +102,15 @@ def main(argv=None):
     metric, threshold = ("rmsd", args.rms) if args.tfd is None else ("tfd", args.tfd)
     check_threshold(threshold, "RMSD")
     out, total, clusters, top = {}, 0, 0, []
-    for mol, item in sampled_items(args.testset, args.samples):
+    for mol, item, valid in _checked_items(sampled_items(args.testset, args.samples), args, out):
         i = mol["index"]
-        if args.fix_handedness:
-            if mol.get("stereo") is None:
-                raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
-            item["stereo"] = mol["stereo"]
-        if args.fix_double_bonds:
-            if mol.get("ez_quads") is None or mol.get("ez") is None:
-                raise ValueError("--fix-double-bonds: %s has no ez_quads_%d / ez_%d (python -m agdiff_amd.ezbonds adds them)"
-                                 % (args.testset, i, i))
-            item["ez_quads"], item["ez"] = mol["ez_quads"], mol["ez"]
-        valid = None
-        if args.drop_invalid:
-            valid = check_geometry(item, device=args.device)["valid"]
-            out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
-        if args.drop_bent:
-            flat = check_planarity(item, device=args.device)["flat"]
-            out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
-            valid = flat if valid is None else valid & flat
         res = cluster_conformers(item, threshold, metric=metric, reorder=not args.static, align=args.align, device=args.device,
                                  valid=valid, fix_handedness=args.fix_handedness, fix_double_bonds=args.fix_double_bonds,
                                  tfd_rings=args.tfd_rings)
         out["centroid_%d" % i] = res["centroids"].cpu().numpy()
         for key in ("cluster", "leader", "count", "population", "dist", "pos"):
             out["%s_%d" % (key, i)] = res[key].cpu().numpy()
-        out["name_%d" % i] = np.str_(mol["name"])
-        if "hand" in res:
-            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
-        if "ez_state" in res:
-            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
+        _write_tail(out, mol, res)
         total += int(res["leader"].shape[0])
         clusters += int(res["centroids"].shape[0])
         if res["population"].shape[0]:

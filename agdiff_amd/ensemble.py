@@ -115,23 +115,31 @@ def _valid_mask(valid, G):
     return v
 
 
-def _usable_matrix(item, what, metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=None):
-    """What picks.pick_conformers and medoids.medoid_conformers do before their walk: the item's conformers, the `valid` mask,
-    the fixes (the caller's tensor is never written), the masking of conformers with a coordinate that is not finite, the
-    compaction to the usable ones on the device, and their float RMSD (metric="rmsd") or TFD matrix.
-        what    the caller's name, for the messages
-        check   check(G, mask, why): the caller's own checks of conformer indices against the item's G conformers and the bool
-                mask [G] (None: nothing masked); called once before any device work with why = "that valid masks out", and again,
-                with why = "with a coordinate that is not finite", when such conformers were masked
+def _usable_matrix(item, what, metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=None, threshold=None,
+                   want_out=True, finite_only=True):
+    """What prune_conformers, clusters.cluster_conformers, picks.pick_conformers and medoids.medoid_conformers do before their
+    walk: the argument checks (all before any device work), the item's conformers, the `valid` mask, the fixes (the caller's tensor
+    is never written), the compaction to the usable conformers on the device, and their RMSD (metric="rmsd") or TFD matrix.
+        what         the caller's name, for the messages
+        check        check(G, mask, why): the caller's own checks of conformer indices against the item's G conformers and the
+                     bool mask [G] (None: nothing masked); called once before any device work with why = "that valid masks out",
+                     and again, with why = "with a coordinate that is not finite", when such conformers were masked
+        threshold    not None (the threshold walks): checked, and the matrix maker also packs `matrix <= threshold` into `bits`
+        want_out     the float matrix `out` is made
+        finite_only  a conformer with a coordinate that is not finite is masked like one that `valid` masks, which costs one
+                     synchronising read; False (the threshold walks): it reaches the matrix, +inf from everything, and nothing
+                     synchronises before the matrix launch
     Returns a namespace: total (the item's conformers), G (the usable ones), mask (bool numpy [total] or None), sel (int64 tensor
-    [G], the usable conformers' indices, or None when all are), gen [G, n, 3], idx (the heavy atoms), out [G, G] (None when
-    G == 0, with gen the uncompacted conformers), hand, ez_state (as prune_conformers returns them, or None)."""
+    [G], the usable conformers' indices, or None when all are), gen [G, n, 3], idx (the heavy atoms), out [G, G] and bits (int64
+    [G, pitch / 8]) or None as asked for (both None when G == 0, with gen the uncompacted conformers), hand, ez_state (as
+    prune_conformers returns them, or None).  _chosen, _own, _scatter and _attach turn a walk's answer into the caller's result."""
     import types
     import torch
     if metric not in ("rmsd", "tfd"):
         raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
     if tfd_rings and metric != "tfd":
         raise ValueError("tfd_rings goes with metric='tfd'")
+    thr = None if threshold is None else check_threshold(threshold, "RMSD")
     gen = _lib.conformers(item["pos_gen"], num_atoms(item))
     G = total = gen.shape[0]
     if G == 0:
@@ -152,12 +160,14 @@ def _usable_matrix(item, what, metric, device, valid, fix_handedness, fix_double
             gen = gen.clone()                            # (the caller's tensor is never written)
         ez_state = _fix_double_bonds(item, gen)
     gen = gen.to(device).contiguous()
-    finite = torch.isfinite(gen).reshape(G, -1).all(dim=1).cpu().numpy()
-    if not finite.all():                                 # a coordinate that is not finite: masked before the matrix is made
-        mask = finite if mask is None else mask & finite
-        if check is not None:
-            check(G, mask, "with a coordinate that is not finite")
-    res = types.SimpleNamespace(total=total, G=G, mask=mask, sel=None, gen=gen, idx=None, out=None, hand=hand, ez_state=ez_state)
+    if finite_only:                                      # a coordinate that is not finite: masked before the matrix is made
+        finite = torch.isfinite(gen).reshape(G, -1).all(dim=1).cpu().numpy()
+        if not finite.all():
+            mask = finite if mask is None else mask & finite
+            if check is not None:
+                check(G, mask, "with a coordinate that is not finite")
+    res = types.SimpleNamespace(total=total, G=G, mask=mask, sel=None, gen=gen, idx=None, out=None, bits=None, hand=hand,
+                                ez_state=ez_state)
     if mask is not None:                                 # compacted on the device; the kernels see the usable ones only
         res.sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
         res.G = int(res.sel.shape[0])
@@ -166,11 +176,49 @@ def _usable_matrix(item, what, metric, device, valid, fix_handedness, fix_double
         gen = gen[res.sel].contiguous()
     if metric == "tfd":
         from .torsions import _self_tfd
-        # (the keyword is passed only when set, as clusters.cluster_conformers does)
-        res.gen, res.out, _ = _self_tfd(dict(item, pos_gen=gen), device, **({"rings": True} if tfd_rings else {}))
+        # (the keyword is passed only when set: without the switch _self_tfd gets, argument for argument, the call it got before)
+        res.gen, res.out, res.bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=thr, want_out=want_out,
+                                               **({"rings": True} if tfd_rings else {}))
         res.idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
     else:
-        res.gen, res.idx, res.out, _ = _self_rmsd(dict(item, pos_gen=gen), device)
+        res.gen, res.idx, res.out, res.bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=thr, want_out=want_out)
+    return res
+
+
+def _chosen(m, chosen, align):
+    """The conformers `chosen` (indices among the usable ones of the namespace m, in the caller's order) [K, n, 3]; with `align`
+    superposed on the first of them over the heavy atoms, and that one put back bit for bit.  None chosen: nothing is launched."""
+    pos = m.gen[chosen.long()]
+    if align and pos.shape[0] > 0:
+        first = pos[0].clone()
+        pos, _ = _align(pos.contiguous(), m.idx, first)
+        pos[0] = first
+    return pos
+
+
+def _own(m, chosen):
+    """indices among the usable conformers as int32 indices into the item's own conformers"""
+    import torch
+    return (chosen if m.sel is None else m.sel[chosen.long()]).to(torch.int32)
+
+
+def _scatter(m, x, fill):
+    """a tensor with one entry per usable conformer as one with an entry per conformer of the item [total], `fill` (-1, NaN) for
+    the masked ones; x itself when nothing was masked"""
+    import torch
+    if m.sel is None:
+        return x
+    full = torch.full((m.total,), fill, dtype=x.dtype, device=x.device)
+    full[m.sel] = x
+    return full
+
+
+def _attach(m, res):
+    """res with `hand` and `ez_state` when the fixes ran"""
+    if m.hand is not None:
+        res["hand"] = m.hand
+    if m.ez_state is not None:
+        res["ez_state"] = m.ez_state
     return res
 
 
@@ -201,86 +249,24 @@ def prune_conformers(item, threshold, align=True, device="cuda", fix_handedness=
     the item's conformers, `leader` is -1 for an invalid one, and with no valid conformer `kept` is empty and nothing is aligned.
     At most AGDIFF_PRUNE_MAX_CONFS conformers."""
     import torch
-    if metric not in ("rmsd", "tfd"):
-        raise ValueError("metric must be 'rmsd' or 'tfd' (got %r)" % (metric,))
-    t = check_threshold(threshold, "RMSD")
-    gen = _lib.conformers(item["pos_gen"], num_atoms(item))
-    G = gen.shape[0]
-    if G == 0:
-        raise ValueError("no conformers to prune")
-    if G > MAX_CONFS:
-        raise _lib.AgdiffLimitError("prune_conformers: %d conformers, more than AGDIFF_PRUNE_MAX_CONFS = %d" % (G, MAX_CONFS))
-    mask = None if valid is None else _valid_mask(valid, G)
-    hand = None
-    if fix_handedness:
-        gen = gen.to(device).contiguous().clone()        # (the caller's tensor is never written)
-        hand = _fix_handedness(item, gen)
-    ez_state = None
-    if fix_double_bonds:
-        gen = gen.to(device).contiguous()
-        if not fix_handedness:
-            gen = gen.clone()                            # (the caller's tensor is never written)
-        ez_state = _fix_double_bonds(item, gen)
-    sel = None
-    if mask is not None:                                 # compacted on the device; the kernels below see the valid ones only
-        gen = gen.to(device).contiguous()
-        sel = torch.nonzero(torch.from_numpy(mask).to(gen.device), as_tuple=False).reshape(-1)
-        G = int(sel.shape[0])
-        if G == 0:
-            res = {"kept": torch.empty(0, dtype=torch.int32, device=gen.device),
-                   "leader": torch.full((mask.shape[0],), -1, dtype=torch.int32, device=gen.device),
-                   "count": torch.empty(0, dtype=torch.int32, device=gen.device), "pos": gen[:0]}
-            if hand is not None:
-                res["hand"] = hand
-            if ez_state is not None:
-                res["ez_state"] = ez_state
-            return res
-        gen = gen[sel].contiguous()
-    if metric == "tfd":
-        from .torsions import _self_tfd
-        gen, _, bits = _self_tfd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
-        idx = torch.from_numpy(selection_of({"atom_type": item["atom_type"]})[1]).to(device)
-    else:
-        gen, idx, _, bits = _self_rmsd(dict(item, pos_gen=gen), device, threshold=t, want_out=False)
-    keep, leader, count, _ = leader_prune(bits, G)
+    m = _usable_matrix(item, "prune_conformers", metric, device, valid, fix_handedness, fix_double_bonds, False,
+                       threshold=threshold, want_out=False, finite_only=False)
+    if m.G == 0:
+        none = torch.empty(0, dtype=torch.int32, device=m.gen.device)
+        return _attach(m, {"kept": none, "leader": _scatter(m, none, -1), "count": none.clone(), "pos": m.gen[:0]})
+    keep, leader, count, _ = leader_prune(m.bits, m.G)
     kept = torch.nonzero(keep, as_tuple=False).reshape(-1)
-    pos = gen[kept]
-    if align and pos.shape[0] > 0:
-        first = pos[0].clone()
-        pos, _ = _align(pos, idx, first)
-        pos[0] = first
-    res = {"kept": kept.to(torch.int32), "leader": leader, "count": count[kept], "pos": pos}
-    if sel is not None:                                  # back to the item's own conformer indices
-        full = torch.full((mask.shape[0],), -1, dtype=torch.int32, device=leader.device)
-        full[sel] = sel[leader.long()].to(torch.int32)
-        res["kept"], res["leader"] = sel[kept].to(torch.int32), full
-    if hand is not None:
-        res["hand"] = hand
-    if ez_state is not None:
-        res["ez_state"] = ez_state
-    return res
+    return _attach(m, {"kept": _own(m, kept), "leader": _scatter(m, _own(m, leader), -1), "count": count[kept],
+                       "pos": _chosen(m, kept, align)})
 
 
-def main(argv=None):
-    """python -m agdiff_amd.ensemble --samples samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
-    Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
-    symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
-    (+ `name_<i>`).  Exactly one of --prune-rms / --prune-tfd T (the torsion fingerprint deviation, in [0, 1]).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
-    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix.  --fix-double-bonds: then the double bonds of
-    the wrong E/Z parity are turned over (the test set must carry `ez_quads_<i>` / `ez_<i>`: python -m agdiff_amd.ezbonds); also
-    writes `ez_state_<i>` [G, D], each bond's state before the fix.  --drop-invalid: the conformers that fail
-    agdiff_amd.validity.check_geometry (table bounds, default clash ratio) take no part in the walk: `cluster_<i>` is -1 for them;
-    also writes `valid_<i>` int8 [G].  --drop-bent: the same for the conformers that fail agdiff_amd.planarity.check_planarity (an
-    aromatic ring or a double bond out of plane, default threshold); also writes `flat_<i>` int8 [G]."""
-    import argparse
-    ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def _add_shared_flags(ap):
+    """the flags that python -m agdiff_amd.ensemble, .clusters, .picks and .medoids share"""
     ap.add_argument("--samples", required=True)
     ap.add_argument("--testset", required=True)
-    how = ap.add_mutually_exclusive_group(required=True)
-    how.add_argument("--prune-rms", type=float, default=None, help="RMSD threshold in Angstrom (heavy atoms)")
-    how.add_argument("--prune-tfd", type=float, default=None,
-                     help="torsion fingerprint deviation threshold in [0, 1] (agdiff_amd.torsions) instead of an RMSD")
-    ap.add_argument("--align", action="store_true", help="superpose the kept conformers on the first of them")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--align", action="store_true", help="superpose the conformers that are written on the first of them")
     ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
     ap.add_argument("--fix-double-bonds", action="store_true",
                     help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
@@ -288,16 +274,19 @@ def main(argv=None):
                          "judge the conformers as sampled, before the flip, which can bring the two sides of a bond into contact: the "
                          "driver's order (flip, repair, check) is the one to use when that matters")
     ap.add_argument("--drop-invalid", action="store_true",
-                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the walk")
+                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out; also writes "
+                         "valid_<i> [G]")
     ap.add_argument("--drop-bent", action="store_true",
-                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out of the walk")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--device", default="cuda")
-    args = ap.parse_args(argv)
-    metric, threshold = ("rmsd", args.prune_rms) if args.prune_tfd is None else ("tfd", args.prune_tfd)
-    check_threshold(threshold, "RMSD")
-    out, total, left = {}, 0, 0
-    for mol, item in sampled_items(args.testset, args.samples):
+                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out; also "
+                         "writes flat_<i> [G]")
+
+
+def _checked_items(items, args, out):
+    """The per-molecule block of those four command lines over the (mol, item) pairs of a module's sampled_items: the test set's
+    `stereo` / `ez_quads` + `ez` go into the item when the fixes are asked for (a test set without them: ValueError), --drop-invalid
+    and --drop-bent judge the conformers and write `valid_<i>` / `flat_<i>` int8 [G] into `out`.  Yields (mol, item, valid), valid
+    the AND of the two masks or None."""
+    for mol, item in items:
         i = mol["index"]
         if args.fix_handedness:
             if mol.get("stereo") is None:
@@ -316,17 +305,49 @@ def main(argv=None):
             flat = check_planarity(item, device=args.device)["flat"]       # (mirroring keeps every plane too)
             out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
             valid = flat if valid is None else valid & flat
+        yield mol, item, valid
+
+
+def _write_tail(out, mol, res):
+    """`name_<i>` and, when the fixes ran, `hand_<i>` and `ez_state_<i>` int8 of a molecule's result, into `out`"""
+    i = mol["index"]
+    out["name_%d" % i] = np.str_(mol["name"])
+    for key in ("hand", "ez_state"):
+        if key in res:
+            out["%s_%d" % (key, i)] = res[key].cpu().numpy().astype(np.int8)
+
+
+def main(argv=None):
+    """python -m agdiff_amd.ensemble --samples samples_all.npz --testset test.npz --prune-rms 0.5 [--align] --out pruned.npz
+    Prunes a finished job's output (agdiff_amd.driver: `pos_gen_<i>`).  The bonds come from the test set, so the molecules'
+    symmetry is honoured.  Writes per molecule `pos_<i>` [K, n, 3], `kept_<i>` [K], `cluster_<i>` [G], `count_<i>` [K]
+    (+ `name_<i>`).  Exactly one of --prune-rms / --prune-tfd T (the torsion fingerprint deviation, in [0, 1]).  --fix-handedness: the mirror images are inverted before the matrix (the test set must carry `stereo_<i>`:
+    python -m agdiff_amd.stereo); also writes `hand_<i>` [G], the verdict before the fix.  --fix-double-bonds: then the double bonds of
+    the wrong E/Z parity are turned over (the test set must carry `ez_quads_<i>` / `ez_<i>`: python -m agdiff_amd.ezbonds); also
+    writes `ez_state_<i>` [G, D], each bond's state before the fix.  --drop-invalid: the conformers that fail
+    agdiff_amd.validity.check_geometry (table bounds, default clash ratio) take no part in the walk: `cluster_<i>` is -1 for them;
+    also writes `valid_<i>` int8 [G].  --drop-bent: the same for the conformers that fail agdiff_amd.planarity.check_planarity (an
+    aromatic ring or a double bond out of plane, default threshold); also writes `flat_<i>` int8 [G]."""
+    import argparse
+    ap = argparse.ArgumentParser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    _add_shared_flags(ap)
+    how = ap.add_mutually_exclusive_group(required=True)
+    how.add_argument("--prune-rms", type=float, default=None, help="RMSD threshold in Angstrom (heavy atoms)")
+    how.add_argument("--prune-tfd", type=float, default=None,
+                     help="torsion fingerprint deviation threshold in [0, 1] (agdiff_amd.torsions) instead of an RMSD")
+    args = ap.parse_args(argv)
+    metric, threshold = ("rmsd", args.prune_rms) if args.prune_tfd is None else ("tfd", args.prune_tfd)
+    check_threshold(threshold, "RMSD")
+    out, total, left = {}, 0, 0
+    for mol, item, valid in _checked_items(sampled_items(args.testset, args.samples), args, out):
+        i = mol["index"]
         res = prune_conformers(item, threshold, align=args.align, device=args.device, fix_handedness=args.fix_handedness,
                                metric=metric, valid=valid, fix_double_bonds=args.fix_double_bonds)
         out["pos_%d" % i] = res["pos"].cpu().numpy()
         out["kept_%d" % i] = res["kept"].cpu().numpy()
         out["cluster_%d" % i] = res["leader"].cpu().numpy()
         out["count_%d" % i] = res["count"].cpu().numpy()
-        out["name_%d" % i] = np.str_(mol["name"])
-        if "hand" in res:
-            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
-        if "ez_state" in res:
-            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
+        _write_tail(out, mol, res)
         total += int(res["leader"].shape[0])
         left += int(res["kept"].shape[0])
     np.savez_compressed(args.out, **out)

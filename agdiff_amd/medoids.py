@@ -27,11 +27,9 @@ the outliers of the ensemble, and on random point clouds they can end at a sligh
 import numpy as np
 
 from . import _lib
-from .ensemble import _align, _usable_matrix
+from .ensemble import _add_shared_flags, _attach, _checked_items, _chosen, _own, _scatter, _usable_matrix, _write_tail
 from .molecule import sampled_items
 from .picks import maxmin_pick
-from .planarity import check_planarity
-from .validity import check_geometry
 
 MAX_ITER = _lib.DEFINES["AGDIFF_KMEDOIDS_MAX_ITER"]
 WORK_BYTES = _lib.DEFINES["AGDIFF_KMEDOIDS_WORK_BYTES"]
@@ -66,28 +64,12 @@ def kmedoids(dist, G, init, max_iter=32):
     return medoids, labels, near, size, within, cost, n_iter, status
 
 
-def _empty(total, gen, hand, ez_state):
-    """the result with no usable conformer: `total` conformers, all masked out"""
-    import torch
-    dev = gen.device
-    none = lambda dtype: torch.empty(0, dtype=dtype, device=dev)
-    res = {"medoids": none(torch.int32), "labels": torch.full((total,), -1, dtype=torch.int32, device=dev),
-           "near": torch.full((total,), float("nan"), dtype=torch.float32, device=dev), "count": none(torch.int32),
-           "population": none(torch.float32), "within": none(torch.float64), "cost": 0.0, "iters": 0, "converged": True,
-           "pos": gen[:0]}
-    if hand is not None:
-        res["hand"] = hand
-    if ez_state is not None:
-        res["ez_state"] = ez_state
-    return res
-
-
 def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=True, device="cuda", valid=None, fix_handedness=False,
                       fix_double_bonds=False, tfd_rings=False):
     """k-medoids among the item's generated conformers by their best RMSD (metric="tfd": their torsion fingerprint deviation,
-    agdiff_amd.torsions; the item must carry its bonds).  The item, `valid`, `fix_handedness`, `fix_double_bonds` and `tfd_rings`
-    are those of picks.pick_conformers, and the fixes run first.  A conformer with a coordinate that is not finite is left out
-    like one that `valid` masks.
+    agdiff_amd.torsions; the item must carry its bonds).  The item, `valid`, `fix_handedness` and `fix_double_bonds` are those of
+    ensemble.prune_conformers, `tfd_rings` makes the rings terms of the TFD, and the fixes run first.  A conformer with a coordinate
+    that is not finite is left out like one that `valid` masks.
         k         the number of medoids (clamped to the number of usable conformers)
         init      the seeds: "maxmin", the first k MaxMin picks from the first usable conformer (fewer picks: that many medoids);
                   "first", the first k usable conformers; or a sequence of k distinct usable conformer indices in the item's own
@@ -129,8 +111,12 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
             if mask is not None and not mask[s]:
                 raise ValueError("init: %d is a conformer %s" % (s, why))
     m = _usable_matrix(item, "medoid_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_seeds)
-    if m.G == 0:
-        return _empty(m.total, m.gen, m.hand, m.ez_state)
+    if m.G == 0:                                         # no usable conformer: all masked out
+        none = lambda dtype: torch.empty(0, dtype=dtype, device=m.gen.device)
+        return _attach(m, {"medoids": none(torch.int32), "labels": _scatter(m, none(torch.int32), -1),
+                           "near": _scatter(m, none(torch.float32), float("nan")), "count": none(torch.int32),
+                           "population": none(torch.float32), "within": none(torch.float64), "cost": 0.0, "iters": 0,
+                           "converged": True, "pos": m.gen[:0]})
     G, out, dev = m.G, m.out, m.out.device
     K = min(int(k), G)
     if seeds is not None:                                # (K == k: the seeds are distinct usable conformers) in compacted numbering
@@ -146,27 +132,12 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
     if status == 2:
         raise ValueError("init: a seed is as far from conformer %d as the matrix can say (not a number >= 0 and <= %d): the "
                          "seeds must be usable together" % (seeds[0] if seeds else 0, _lib.DEFINES["AGDIFF_KMEDOIDS_MAX_DIST"]))
-    pos = m.gen[medoids.long()]
-    if align:
-        start_pos = pos[0].clone()
-        pos, _ = _align(pos.contiguous(), m.idx, start_pos)
-        pos[0] = start_pos
+    pos = _chosen(m, medoids, align)
     counts = size.cpu().numpy()                          # (the division on the host: one correctly rounded fp32 quotient each)
     population = torch.from_numpy(counts.astype(np.float32) / np.float32(max(int(counts.sum()), 1))).to(dev)
-    res = {"medoids": medoids, "labels": labels, "near": near, "count": size,
-           "population": population, "within": within, "cost": float(cost.item()),
-           "iters": int(n_iter.item()), "converged": status == 0, "pos": pos}
-    if m.sel is not None:                                # back to the item's own conformer indices
-        lab = torch.full((m.total,), -1, dtype=torch.int32, device=dev)
-        lab[m.sel] = labels
-        nr = torch.full((m.total,), float("nan"), dtype=torch.float32, device=dev)
-        nr[m.sel] = near
-        res["medoids"], res["labels"], res["near"] = m.sel[medoids.long()].to(torch.int32), lab, nr
-    if m.hand is not None:
-        res["hand"] = m.hand
-    if m.ez_state is not None:
-        res["ez_state"] = m.ez_state
-    return res
+    return _attach(m, {"medoids": _own(m, medoids), "labels": _scatter(m, labels, -1), "near": _scatter(m, near, float("nan")),
+                       "count": size, "population": population, "within": within, "cost": float(cost.item()),
+                       "iters": int(n_iter.item()), "converged": status == 0, "pos": pos})
 
 
 def _parser():
@@ -183,8 +154,7 @@ def _parser():
                 self.error("--tfd-rings goes with --tfd")
             return args
     ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--samples", required=True)
-    ap.add_argument("--testset", required=True)
+    _add_shared_flags(ap)
     ap.add_argument("--count", type=int, required=True, help="the number of medoids per molecule")
     ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
     ap.add_argument("--tfd-rings", action="store_true",
@@ -192,17 +162,6 @@ def _parser():
     ap.add_argument("--init", choices=("maxmin", "first"), default="maxmin",
                     help="the seeds: the first K MaxMin picks (agdiff_amd.picks), or the first K conformers that are not left out")
     ap.add_argument("--max-iter", type=int, default=32, help="at most this many updates (1 .. %d)" % MAX_ITER)
-    ap.add_argument("--align", action="store_true", help="superpose the medoids on the first of them")
-    ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
-    ap.add_argument("--fix-double-bonds", action="store_true",
-                    help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
-                         "in --testset: python -m agdiff_amd.ezbonds); also writes ez_state_<i> [G, D]")
-    ap.add_argument("--drop-invalid", action="store_true",
-                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out")
-    ap.add_argument("--drop-bent", action="store_true",
-                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--device", default="cuda")
     return ap
 
 
@@ -213,31 +172,14 @@ def main(argv=None):
     molecule `medoid_<i>` [K], `cluster_<i>` [G] (the rank of each conformer's cluster; -1 when left out), `dist_<i>` [G] (the
     distance to its medoid; NaN when left out), `count_<i>` [K], `population_<i>` [K] (the share of the conformers that were
     not left out), `within_<i>` float64 [K], `cost_<i>` float64, `iters_<i>` int32, `converged_<i>` int8, `pos_<i>` [K, n, 3]
-    (+ `name_<i>`).  --fix-handedness, --fix-double-bonds, --drop-invalid, --drop-bent: as in python -m agdiff_amd.picks, with the
+    (+ `name_<i>`).  --fix-handedness, --fix-double-bonds, --drop-invalid, --drop-bent: as in python -m agdiff_amd.ensemble, with the
     same `hand_<i>`, `ez_state_<i>`, `valid_<i>` and `flat_<i>`.  Prints the conformers, the medoids, the molecules that did not
     converge and the largest population of a medoid."""
     args = _parser().parse_args(argv)
     metric = "tfd" if args.tfd else "rmsd"
     out, total, found, open_, top = {}, 0, 0, 0, 0.0
-    for mol, item in sampled_items(args.testset, args.samples):
+    for mol, item, valid in _checked_items(sampled_items(args.testset, args.samples), args, out):
         i = mol["index"]
-        if args.fix_handedness:
-            if mol.get("stereo") is None:
-                raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
-            item["stereo"] = mol["stereo"]
-        if args.fix_double_bonds:
-            if mol.get("ez_quads") is None or mol.get("ez") is None:
-                raise ValueError("--fix-double-bonds: %s has no ez_quads_%d / ez_%d (python -m agdiff_amd.ezbonds adds them)"
-                                 % (args.testset, i, i))
-            item["ez_quads"], item["ez"] = mol["ez_quads"], mol["ez"]
-        valid = None
-        if args.drop_invalid:
-            valid = check_geometry(item, device=args.device)["valid"]
-            out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
-        if args.drop_bent:
-            flat = check_planarity(item, device=args.device)["flat"]
-            out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
-            valid = flat if valid is None else valid & flat
         res = medoid_conformers(item, args.count, metric=metric, init=args.init, max_iter=args.max_iter, align=args.align,
                                 device=args.device, valid=valid, fix_handedness=args.fix_handedness,
                                 fix_double_bonds=args.fix_double_bonds, tfd_rings=args.tfd_rings)
@@ -247,11 +189,7 @@ def main(argv=None):
         out["cost_%d" % i] = np.float64(res["cost"])
         out["iters_%d" % i] = np.int32(res["iters"])
         out["converged_%d" % i] = np.int8(res["converged"])
-        out["name_%d" % i] = np.str_(mol["name"])
-        if "hand" in res:
-            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
-        if "ez_state" in res:
-            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
+        _write_tail(out, mol, res)
         total += int(res["labels"].shape[0])
         found += int(res["medoids"].shape[0])
         open_ += 0 if res["converged"] else 1

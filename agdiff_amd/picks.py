@@ -21,10 +21,8 @@ takes the count.  Agreement with rdkit's MaxMinPicker is not claimed: that one d
 import numpy as np
 
 from . import _lib
-from .ensemble import _align, _usable_matrix
+from .ensemble import _add_shared_flags, _attach, _checked_items, _chosen, _own, _scatter, _usable_matrix, _write_tail
 from .molecule import check_threshold, sampled_items
-from .planarity import check_planarity
-from .validity import check_geometry
 
 
 def maxmin_pick(dist, G, k, stop=-1.0, first=0):
@@ -48,28 +46,12 @@ def maxmin_pick(dist, G, k, stop=-1.0, first=0):
     return picks, radius, owner, near, n_picked, cover
 
 
-def _empty(total, gen, hand, ez_state):
-    """the result with no conformer to pick from: `total` conformers, all masked out"""
-    import torch
-    dev = gen.device
-    none = lambda dtype: torch.empty(0, dtype=dtype, device=dev)
-    res = {"picks": none(torch.int32), "radius": none(torch.float32),
-           "owner": torch.full((total,), -1, dtype=torch.int32, device=dev),
-           "near": torch.full((total,), float("nan"), dtype=torch.float32, device=dev), "count": none(torch.int32),
-           "cover": 0.0, "pos": gen[:0]}
-    if hand is not None:
-        res["hand"] = hand
-    if ez_state is not None:
-        res["ez_state"] = ez_state
-    return res
-
-
 def pick_conformers(item, k=None, radius=None, metric="rmsd", first=None, align=True, device="cuda", valid=None, fix_handedness=False,
                     fix_double_bonds=False, tfd_rings=False):
     """MaxMin picking among the item's generated conformers by their best RMSD (metric="tfd": their torsion fingerprint deviation,
-    agdiff_amd.torsions; the item must carry its bonds).  The item, `valid`, `fix_handedness`, `fix_double_bonds` and `tfd_rings`
-    are those of clusters.cluster_conformers, and the fixes run first.  A conformer with a coordinate that is not finite is left
-    out like one that `valid` masks.
+    agdiff_amd.torsions; the item must carry its bonds).  The item, `valid`, `fix_handedness` and `fix_double_bonds` are those of
+    ensemble.prune_conformers, `tfd_rings` makes the rings terms of the TFD, and the fixes run first.  A conformer with a coordinate
+    that is not finite is left out like one that `valid` masks.
         k       at most this many picks (clamped to the number of usable conformers)
         radius  stop once every usable conformer is within `radius` of a pick: a conformer is picked only while the farthest one
                 is farther than that.  At least one of k and radius; radius alone picks until cover <= radius.
@@ -102,32 +84,20 @@ def pick_conformers(item, k=None, radius=None, metric="rmsd", first=None, align=
         if mask is not None and not mask[int(first)]:
             raise ValueError("first = %d is a conformer %s" % (first, why))
     m = _usable_matrix(item, "pick_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_first)
-    total, G, mask, sel, gen, idx, out, hand, ez_state = m.total, m.G, m.mask, m.sel, m.gen, m.idx, m.out, m.hand, m.ez_state
-    if G == 0:
-        return _empty(total, gen, hand, ez_state)
-    start = 0 if first is None else (int(first) if mask is None else int(mask[:int(first)].sum()))
-    limit = G if k is None else min(int(k), G)
-    picks, rad, owner, near, n_picked, cover = maxmin_pick(out, G, limit, stop=stop, first=start)
+    if m.G == 0:                                         # no conformer to pick from: all masked out
+        none = lambda dtype: torch.empty(0, dtype=dtype, device=m.gen.device)
+        return _attach(m, {"picks": none(torch.int32), "radius": none(torch.float32), "owner": _scatter(m, none(torch.int32), -1),
+                           "near": _scatter(m, none(torch.float32), float("nan")), "count": none(torch.int32), "cover": 0.0,
+                           "pos": m.gen[:0]})
+    start = 0 if first is None else (int(first) if m.mask is None else int(m.mask[:int(first)].sum()))
+    limit = m.G if k is None else min(int(k), m.G)
+    picks, rad, owner, near, n_picked, cover = maxmin_pick(m.out, m.G, limit, stop=stop, first=start)
     n = int(n_picked.item())
     picks, rad = picks[:n], rad[:n]
-    pos = gen[picks.long()]
-    if align:
-        start_pos = pos[0].clone()
-        pos, _ = _align(pos.contiguous(), idx, start_pos)
-        pos[0] = start_pos
+    pos = _chosen(m, picks, align)
     count = torch.bincount(owner[owner >= 0].long(), minlength=n).to(torch.int32)
-    res = {"picks": picks, "radius": rad, "owner": owner, "near": near, "count": count, "cover": float(cover.item()), "pos": pos}
-    if sel is not None:                                  # back to the item's own conformer indices
-        own = torch.full((total,), -1, dtype=torch.int32, device=owner.device)
-        own[sel] = owner
-        nr = torch.full((total,), float("nan"), dtype=torch.float32, device=owner.device)
-        nr[sel] = near
-        res["picks"], res["owner"], res["near"] = sel[picks.long()].to(torch.int32), own, nr
-    if hand is not None:
-        res["hand"] = hand
-    if ez_state is not None:
-        res["ez_state"] = ez_state
-    return res
+    return _attach(m, {"picks": _own(m, picks), "radius": rad, "owner": _scatter(m, owner, -1),
+                       "near": _scatter(m, near, float("nan")), "count": count, "cover": float(cover.item()), "pos": pos})
 
 
 def _parser():
@@ -142,8 +112,7 @@ def _parser():
                 self.error("--tfd-rings goes with --tfd")
             return args
     ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--samples", required=True)
-    ap.add_argument("--testset", required=True)
+    _add_shared_flags(ap)
     ap.add_argument("--count", type=int, default=None, help="pick at most this many conformers per molecule")
     ap.add_argument("--radius", type=float, default=None,
                     help="stop once every conformer is within this distance of a pick (Angstrom of heavy-atom RMSD; with --tfd a TFD "
@@ -152,17 +121,6 @@ def _parser():
     ap.add_argument("--tfd-rings", action="store_true",
                     help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
     ap.add_argument("--first", type=int, default=None, help="the conformer picked first (default: the first one that is not left out)")
-    ap.add_argument("--align", action="store_true", help="superpose the picks on the first of them")
-    ap.add_argument("--fix-handedness", action="store_true", help="invert the mirror-image conformers first (needs stereo_<i> in --testset)")
-    ap.add_argument("--fix-double-bonds", action="store_true",
-                    help="turn over the double bonds of the wrong E/Z parity first, after --fix-handedness (needs ez_quads_<i> and ez_<i> "
-                         "in --testset: python -m agdiff_amd.ezbonds); also writes ez_state_<i> [G, D]")
-    ap.add_argument("--drop-invalid", action="store_true",
-                    help="leave the conformers with a bond out of bounds or a steric clash (agdiff_amd.validity) out of the picking")
-    ap.add_argument("--drop-bent", action="store_true",
-                    help="leave the conformers with an aromatic ring or a double bond out of plane (agdiff_amd.planarity) out of it")
-    ap.add_argument("--out", required=True)
-    ap.add_argument("--device", default="cuda")
     return ap
 
 
@@ -173,32 +131,15 @@ def main(argv=None):
     `radius_<i>` [K'] (the distance at which each pick was taken; +inf for the first), `owner_<i>` [G] (the rank of the nearest
     pick; -1 when left out), `near_<i>` [G] (the distance to it; NaN when left out), `count_<i>` [K'], `cover_<i>` (the covering
     radius of the picks), `pos_<i>` [K', n, 3] (+ `name_<i>`).  At least one of --count / --radius.  --fix-handedness,
-    --fix-double-bonds, --drop-invalid, --drop-bent: as in python -m agdiff_amd.clusters, with the same `hand_<i>`, `ez_state_<i>`,
+    --fix-double-bonds, --drop-invalid, --drop-bent: as in python -m agdiff_amd.ensemble, with the same `hand_<i>`, `ez_state_<i>`,
     `valid_<i>` and `flat_<i>`.  Prints the conformers, the picks and the largest covering radius over the molecules."""
     args = _parser().parse_args(argv)
     metric = "tfd" if args.tfd else "rmsd"
     if args.radius is not None:
         check_threshold(args.radius, "RMSD")
     out, total, picked, covers = {}, 0, 0, []
-    for mol, item in sampled_items(args.testset, args.samples):
+    for mol, item, valid in _checked_items(sampled_items(args.testset, args.samples), args, out):
         i = mol["index"]
-        if args.fix_handedness:
-            if mol.get("stereo") is None:
-                raise ValueError("--fix-handedness: %s has no stereo_%d (python -m agdiff_amd.stereo adds it)" % (args.testset, i))
-            item["stereo"] = mol["stereo"]
-        if args.fix_double_bonds:
-            if mol.get("ez_quads") is None or mol.get("ez") is None:
-                raise ValueError("--fix-double-bonds: %s has no ez_quads_%d / ez_%d (python -m agdiff_amd.ezbonds adds them)"
-                                 % (args.testset, i, i))
-            item["ez_quads"], item["ez"] = mol["ez_quads"], mol["ez"]
-        valid = None
-        if args.drop_invalid:
-            valid = check_geometry(item, device=args.device)["valid"]
-            out["valid_%d" % i] = valid.cpu().numpy().astype(np.int8)
-        if args.drop_bent:
-            flat = check_planarity(item, device=args.device)["flat"]
-            out["flat_%d" % i] = flat.cpu().numpy().astype(np.int8)
-            valid = flat if valid is None else valid & flat
         res = pick_conformers(item, k=args.count, radius=args.radius, metric=metric, first=args.first, align=args.align,
                               device=args.device, valid=valid, fix_handedness=args.fix_handedness,
                               fix_double_bonds=args.fix_double_bonds, tfd_rings=args.tfd_rings)
@@ -206,11 +147,7 @@ def main(argv=None):
         for key in ("radius", "owner", "near", "count", "pos"):
             out["%s_%d" % (key, i)] = res[key].cpu().numpy()
         out["cover_%d" % i] = np.float32(res["cover"])
-        out["name_%d" % i] = np.str_(mol["name"])
-        if "hand" in res:
-            out["hand_%d" % i] = res["hand"].cpu().numpy().astype(np.int8)
-        if "ez_state" in res:
-            out["ez_state_%d" % i] = res["ez_state"].cpu().numpy().astype(np.int8)
+        _write_tail(out, mol, res)
         total += int(res["owner"].shape[0])
         picked += int(res["picks"].shape[0])
         covers.append(res["cover"])

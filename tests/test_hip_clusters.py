@@ -392,6 +392,42 @@ def test_tfd_clusters_are_the_planted_rotamer_families(reorder):
     assert np.abs(res["pos"].cpu().numpy() - want).max() <= ALIGN_ATOL
 
 
+@pytest.mark.parametrize("reorder", [False, True])
+def test_a_conformer_with_a_nan_is_a_singleton_and_changes_nobody_elses_cluster(reorder):
+    """cluster_conformers does not mask a conformer with a coordinate that is not finite: it reaches the matrix, where by the header's
+    rule it is +inf from everything (tests/test_hip_rmsd_kernels.py, section 5), so it is a cluster of its own, the last one, and the
+    others come out as they do from the item without it.  Two planted families (0.03 of noise, centres 1.5 apart, threshold 0.5),
+    conformer 3 broken in a heavy atom; with and without a `valid` mask that removes conformer 0, the first centroid.  The broken
+    conformer's own `dist` reads the matrix diagonal and is not looked at."""
+    from agdiff_amd.clusters import cluster_conformers
+    rng = np.random.default_rng(31)
+    n, G, bad, thr = 8, 6, 3, 0.5
+    at = np.array([6, 6, 7, 6, 8, 1, 1, 6])
+    label = np.array([0, 1, 0, 0, 1, 0])
+    centres = rng.normal(size=(2, n, 3)) * 1.5
+    gen = np.stack([_moved(rng, centres[c] + 0.03 * rng.normal(size=(n, 3))) for c in label]).astype(np.float32)
+    gen[bad, 2, 1] = np.nan
+    rest = np.delete(np.arange(G), bad)
+    masked = np.ones(G, dtype=bool)
+    masked[0] = False
+    for valid, cent, leader, cluster, count in ((None, [0, 1, 3], [0, 1, 0, 3, 1, 0], [0, 1, 0, 2, 1, 0], [3, 2, 1]),
+                                                (masked, [1, 2, 3], [-1, 1, 2, 3, 1, 2], [-1, 0, 1, 2, 0, 1], [2, 2, 1])):
+        res = cluster_conformers({"atom_type": at, "pos_gen": gen}, thr, reorder=reorder, valid=valid)
+        assert res["centroids"].cpu().tolist() == cent and res["leader"].cpu().tolist() == leader
+        assert res["cluster"].cpu().tolist() == cluster and res["count"].cpu().tolist() == count
+        ref = cluster_conformers({"atom_type": at, "pos_gen": gen[rest]}, thr, reorder=reorder, valid=None if valid is None else valid[rest])
+        own = lambda x: np.where(x < 0, -1, rest[np.maximum(x, 0)])         # the smaller item's indices in this one's
+        assert np.array_equal(own(ref["centroids"].cpu().numpy()), np.array(cent[:2]))
+        assert np.array_equal(own(ref["leader"].cpu().numpy()), np.array(leader)[rest])
+        assert np.array_equal(ref["cluster"].cpu().numpy(), np.array(cluster)[rest])
+        assert ref["count"].cpu().tolist() == count[:2]
+        got, want = res["dist"].cpu()[rest], ref["dist"].cpu()              # NaN where masked, else bit for bit
+        shown = torch.from_numpy(np.ones(G, dtype=bool) if valid is None else valid)[rest]
+        assert torch.equal(torch.isnan(got), ~shown) and torch.equal(torch.isnan(want), ~shown)
+        assert torch.equal(got[shown], want[shown]) and bool((got[shown] <= thr).all())
+        assert torch.equal(res["pos"][:2], ref["pos"])                      # superposed on the same first centroid
+
+
 # ------------------------------------------------------------------------------------------------ 8. the command line
 def seven_pattern_conformers(rng):
     """(atom_type, bonds as (i, j, type), gen fp32 [7, n, 3], threshold): seven conformers of a ten-atom chain whose adjacency under

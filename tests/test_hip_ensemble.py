@@ -402,3 +402,33 @@ def test_command_line_prunes_a_finished_job(tmp_path):
     z = np.load(str(tmp_path / "pruned.npz"))
     assert z["kept_0"].tolist() == [0, 1] and z["cluster_0"].tolist() == [0, 1, 0, 1, 0, 1, 0] and z["count_0"].tolist() == [4, 3]
     assert z["pos_0"].shape == (2, 15, 3) and np.array_equal(z["pos_0"][0], gen[0]) and np.array_equal(out["pos_0"], z["pos_0"])
+
+
+# ------------------------------------------------------------------------------------------------ 9. a conformer that is not a number
+def test_a_conformer_with_a_nan_is_kept_alone_and_changes_nobody_elses_leader():
+    """prune_conformers does not mask a conformer with a coordinate that is not finite: it reaches the matrix, where by the header's
+    rule it is +inf from everything (tests/test_hip_rmsd_kernels.py, section 5), so the walk keeps it as a leader of its own and
+    the others come out as they do from the item without it.  Two planted families (intra 0.03-noise, centres 1.5 apart, threshold
+    0.5), conformer 3 broken in a heavy atom; with and without a `valid` mask that removes conformer 0, the first leader."""
+    from agdiff_amd.ensemble import prune_conformers
+    rng = np.random.default_rng(31)
+    n, G, bad, thr = 8, 6, 3, 0.5
+    at = np.array([6, 6, 7, 6, 8, 1, 1, 6])
+    label = np.array([0, 1, 0, 0, 1, 0])
+    centres = rng.normal(size=(2, n, 3)) * 1.5
+    gen = np.stack([_moved(rng, centres[c] + 0.03 * rng.normal(size=(n, 3))) for c in label]).astype(np.float32)
+    gen[bad, 2, 1] = np.nan
+    rest = np.delete(np.arange(G), bad)
+    masked = np.ones(G, dtype=bool)
+    masked[0] = False
+    for valid, kept, leader, count in ((None, [0, 1, 3], [0, 1, 0, 3, 1, 0], [3, 2, 1]),
+                                       (masked, [1, 2, 3], [-1, 1, 2, 3, 1, 2], [2, 2, 1])):
+        res = prune_conformers(_item(at, gen), thr, valid=valid)
+        assert res["kept"].cpu().tolist() == kept and res["leader"].cpu().tolist() == leader and res["count"].cpu().tolist() == count
+        ref = prune_conformers(_item(at, gen[rest]), thr, valid=None if valid is None else valid[rest])
+        own = lambda x: np.where(x < 0, -1, rest[np.maximum(x, 0)])         # the smaller item's indices in this one's
+        finite = np.array(kept) != bad
+        assert np.array_equal(own(ref["kept"].cpu().numpy()), np.array(kept)[finite])
+        assert np.array_equal(own(ref["leader"].cpu().numpy()), np.array(leader)[rest])
+        assert np.array_equal(ref["count"].cpu().numpy(), np.array(count)[finite])
+        assert torch.equal(res["pos"][torch.from_numpy(finite).cuda()], ref["pos"])     # superposed on the same first conformer

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times of the conformer-ensemble kernels on one molecule (G conformers, n atoms, m heavy atoms, P atom mappings):
 agdiff_rmsd_self (matrix + threshold bits; upper-triangular tiles) against agdiff_rmsd_matrix(pos, pos) (every pair twice) on
-the same inputs, agdiff_leader_prune, and the wall time of ensemble.prune_conformers.  Device events around `--reps` launches
+the same inputs, agdiff_leader_prune, and the wall times of ensemble.prune_conformers and clusters.cluster_conformers.  Device events around `--reps` launches
 after a warm-up, the two matrix calls alternating round by round in this one process.
 
 --parent-lib PATH: the full-matrix call is ALSO taken from that build of libagdiff_hip.so (an older commit's, as AGDIFF_LIB
@@ -13,7 +13,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
-from agdiff_amd import _lib, ensemble
+from agdiff_amd import _lib, clusters, ensemble
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--G", type=int, default=1000)
@@ -139,6 +139,17 @@ for P in args.perms:
             walls.append((time.perf_counter() - t0) * 1e3)
         say("prune_conformers G = %d, P = %d, align=%s: wall median %.2f ms  min %.2f  max %.2f  (%d kept)"
             % (G, P, align, np.median(walls), min(walls), max(walls), int(res["kept"].shape[0])))
+        # clusters.cluster_conformers on the same item: the same prelude and matrix launch (plus the float matrix), Butina's walk
+        clusters.cluster_conformers(item, 0.5, align=align, device=dev)
+        torch.cuda.synchronize()
+        walls = []
+        for _ in range(args.rounds):
+            t0 = time.perf_counter()
+            res = clusters.cluster_conformers(item, 0.5, align=align, device=dev)
+            torch.cuda.synchronize()
+            walls.append((time.perf_counter() - t0) * 1e3)
+        say("cluster_conformers G = %d, P = %d, align=%s: wall median %.2f ms  min %.2f  max %.2f  (%d clusters)"
+            % (G, P, align, np.median(walls), min(walls), max(walls), int(res["centroids"].shape[0])))
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
