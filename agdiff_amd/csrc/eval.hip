@@ -836,6 +836,167 @@ __global__ void __launch_bounds__(1024) k_kmed_finish(int G, int K, const int32_
   }
 }
 
+// Silhouette coefficients of a given clustering over the same float matrix (the rule: include/agdiff_hip.h, agdiff_silhouette).
+// Three launches, the kernel boundary again the only grid-wide ordering:
+//   k_sil_init     one workgroup: checks the labels (-1 or a rank in [0, K)), counts the members of every rank with LDS integer
+//                  atomics and writes `size` and the control words; on a bad label it writes the status-2 fill and sets `done`
+//   k_sil_rows     row i is streamed once with coalesced 4-byte loads and Q of its entries is added into K uint64 bins in LDS, one
+//                  per rank (LDS 64-bit integer add, as k_kmed_finish); then the lanes stride over the bins, make the means
+//                  m_c = S_c / size[c] and min-reduce the pairs (m_c, c) under the total order "lowest mean, then lowest rank";
+//                  one lane writes a, b, s, other and T(i) = rint(s 2^40) into `work`.  Two shapes, chosen by K so that the bins
+//                  of a workgroup take at most 32 KB of LDS (SIL_BIN_BYTES):
+//                    K <= AG_SIL_WAVE_ROW_MAX_K (1024)   ROWS = 4: one row per WAVE, four rows and 4 K bins per workgroup
+//                    K >  AG_SIL_WAVE_ROW_MAX_K          ROWS = 1: one row per WORKGROUP of four waves, K bins (K <= 4096)
+//   k_sil_finish   one workgroup: per-rank and total sums of T (int64, as uint64 LDS adds), the divisions, status
+// The state between launches lives in `size` and in `work`: 8 control words, then T [G].  Sums are on integers; the only
+// floating-point values that cross lanes are the means of the (mean, rank) pairs, compared and never added; LDS atomics are adds
+// on integers, there are no global atomics and no workgroup waits on another.  Every loop is counted.
+#define AG_SIL_WAVE_ROW_MAX_K 1024
+enum { SIL_DONE = 0, SIL_STATUS = 1, SIL_CTL_WORDS = 8 };     // int32 words at the head of `work`
+enum { SIL_BIN_BYTES = 32768 };                               // the most LDS a workgroup's bins take, in either shape
+static_assert(AGDIFF_SILHOUETTE_WORK_BYTES >= SIL_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * 8, "agdiff_silhouette: control words + one T per conformer");
+static_assert(4 * AG_SIL_WAVE_ROW_MAX_K * 8 <= SIL_BIN_BYTES && AGDIFF_PRUNE_MAX_CONFS * 8 <= SIL_BIN_BYTES, "agdiff_silhouette: the bins of either shape fit their LDS");
+static_assert(AGDIFF_PRUNE_MAX_CONFS == 1 << 12 && AGDIFF_KMEDOIDS_MAX_DIST == 4096, "agdiff_silhouette: a row's sum of 4096 terms <= 2^40 and a sum of 4096 |T| <= 2^40 stay <= 2^52");
+
+__global__ void __launch_bounds__(1024) k_sil_init(int G, int K, const int32_t* __restrict__ labels, double* __restrict__ a,
+                                                   double* __restrict__ b, double* __restrict__ s, int32_t* __restrict__ other,
+                                                   int32_t* __restrict__ size, double* __restrict__ cluster_mean,
+                                                   double* __restrict__ mean, int32_t* __restrict__ status, int32_t* __restrict__ ctl) {
+  __shared__ int32_t s_size[AGDIFF_PRUNE_MAX_CONFS];
+  const int t = threadIdx.x;
+  for (int r = t; r < K; r += 1024) s_size[r] = 0;
+  __syncthreads();
+  int bad = 0;
+  for (int j = t; j < G; j += 1024) {
+    const int l = labels[j];
+    if (l == -1) continue;
+    if ((unsigned)l >= (unsigned)K) { bad = 1; continue; }
+    atomicAdd(&s_size[l], 1);
+  }
+  bad = __syncthreads_or(bad);
+  if (!bad) {
+    for (int r = t; r < K; r += 1024) size[r] = s_size[r];
+    if (t < SIL_CTL_WORDS) ctl[t] = 0;
+    return;
+  }
+  const double nan = __builtin_nan("");
+  for (int j = t; j < G; j += 1024) { a[j] = nan; b[j] = nan; s[j] = nan; other[j] = -1; }
+  for (int r = t; r < K; r += 1024) { size[r] = 0; cluster_mean[r] = nan; }
+  if (t < SIL_CTL_WORDS) ctl[t] = t == SIL_DONE ? 1 : (t == SIL_STATUS ? 2 : 0);
+  if (t == 0) { mean[0] = nan; status[0] = 2; }
+}
+
+// the smaller of two (mean, rank) pairs: lowest mean, then lowest rank.  The means are never NaN; "none" is (+inf, INT_MAX).
+__device__ __forceinline__ void ag_sil_min_pair(double& m, int& c, double om, int oc) {
+  const bool take = om < m || (om == m && oc < c);
+  m = take ? om : m;
+  c = take ? oc : c;
+}
+
+template <int ROWS>
+__global__ void __launch_bounds__(256) k_sil_rows(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ labels,
+                                                  const int32_t* __restrict__ size, double* __restrict__ a, double* __restrict__ b,
+                                                  double* __restrict__ s, int32_t* __restrict__ other, int64_t* __restrict__ T,
+                                                  const int32_t* __restrict__ ctl) {
+  static_assert(ROWS == 1 || ROWS == 4, "one row per workgroup or one per wave");
+  if (ctl[SIL_DONE] != 0) return;                   // (grid-uniform: a bad label, k_sil_init wrote everything)
+  extern __shared__ unsigned long long s_bins[];    // [ROWS][K]
+  __shared__ double s_pm[4];
+  __shared__ int s_pc[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int NT = ROWS == 4 ? 64 : 256;              // the threads that share a row
+  const int tid = ROWS == 4 ? lane : (int)threadIdx.x;
+  const int i = ROWS == 4 ? blockIdx.x * 4 + wv : (int)blockIdx.x;     // (wave-uniform; every wave reaches every barrier)
+  unsigned long long* __restrict__ bins = s_bins + (ROWS == 4 ? (size_t)wv * (size_t)K : 0);
+  const int own = i < G ? labels[i] : -1;
+  const bool member = own >= 0;
+  for (int c = tid; c < K; c += NT) bins[c] = 0ull;
+  __syncthreads();
+  if (member) {
+    const float* __restrict__ row = dist + (size_t)i * (size_t)G;
+#pragma unroll 4
+    for (int j = tid; j < G; j += NT) {
+      const int l = labels[j];
+      if (l >= 0 && j != i) atomicAdd(&bins[l], (unsigned long long)ag_kmed_q(row[j]));   // (a left-out column and the diagonal are not read)
+    }
+  }
+  __syncthreads();
+  double bm = __builtin_inf();
+  int bc = 0x7fffffff;
+  if (member) {
+    for (int c = tid; c < K; c += NT) {             // (ascending c: a later equal mean does not replace an earlier one)
+      const int n = size[c];
+      if (c == own || n == 0) continue;
+      ag_sil_min_pair(bm, bc, (double)bins[c] / (double)n, c);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ag_sil_min_pair(bm, bc, __shfl_xor(bm, o), __shfl_xor(bc, o));
+  if (ROWS == 1) {
+    if (lane == 0) { s_pm[wv] = bm; s_pc[wv] = bc; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 4; ++w) ag_sil_min_pair(bm, bc, s_pm[w], s_pc[w]);
+  }
+  if (tid != 0 || i >= G) return;
+  if (!member) {                                    // left out
+    a[i] = b[i] = s[i] = __builtin_nan("");
+    other[i] = -1;
+    T[i] = 0;
+    return;
+  }
+  const int n_own = size[own];
+  const bool none = bc == 0x7fffffff;
+  const double ma = n_own > 1 ? (double)bins[own] / (double)(n_own - 1) : 0.0;
+  const double mb = none ? 0.0 : bm;
+  const double top = ma > mb ? ma : mb;
+  const double si = (n_own == 1 || none || top == 0.0) ? 0.0 : (mb - ma) / top;
+  a[i] = ma * (1.0 / 268435456.0);
+  b[i] = none ? __builtin_nan("") : mb * (1.0 / 268435456.0);
+  s[i] = si;
+  other[i] = none ? -1 : bc;
+  T[i] = (int64_t)__builtin_rint(si * 1099511627776.0);      // (|s| <= 1: the product is exact and the integer <= 2^40)
+}
+
+__global__ void __launch_bounds__(1024) k_sil_finish(int G, int K, const int32_t* __restrict__ labels, const int64_t* __restrict__ T,
+                                                     const int32_t* __restrict__ size, double* __restrict__ cluster_mean,
+                                                     double* __restrict__ mean, int32_t* __restrict__ status,
+                                                     const int32_t* __restrict__ ctl) {
+  if (ctl[SIL_STATUS] == 2) return;                 // a bad label: k_sil_init wrote everything
+  __shared__ unsigned long long s_sum[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ unsigned long long s_part[16];
+  __shared__ int s_cnt[16];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  for (int r = t; r < K; r += 1024) s_sum[r] = 0ull;
+  __syncthreads();
+  uint64_t total = 0;                               // (int64 sums in two's complement: the adds wrap the same way)
+  int members = 0;
+  for (int j = t; j < G; j += 1024) {
+    const int l = labels[j];
+    if (l >= 0) {
+      const uint64_t v = (uint64_t)T[j];
+      atomicAdd(&s_sum[l], (unsigned long long)v);
+      total += v;
+      ++members;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { total += ag_shfl_xor_u64(total, o); members += __shfl_xor(members, o); }
+  if (lane == 0) { s_part[wv] = total; s_cnt[wv] = members; }
+  __syncthreads();
+  for (int r = t; r < K; r += 1024) {
+    const int n = size[r];
+    cluster_mean[r] = n > 0 ? ((double)(int64_t)s_sum[r] / (double)n) * (1.0 / 1099511627776.0) : __builtin_nan("");
+  }
+  if (t == 0) {
+    uint64_t all = 0;
+    int n = 0;
+    for (int w = 0; w < 16; ++w) { all += s_part[w]; n += s_cnt[w]; }
+    mean[0] = n > 0 ? ((double)(int64_t)all / (double)n) * (1.0 / 1099511627776.0) : __builtin_nan("");
+    status[0] = 0;
+  }
+}
+
 // eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
 // accumulated: returns the largest eigenvalue and its unit eigenvector q
 __device__ double ag_eigvec_max4(const double (&k)[10], double (&q)[4]) {
@@ -2529,6 +2690,39 @@ extern "C" int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const in
   k_kmed_assign<<<cols, dim3(256), 0, st>>>(dist, G, K, init, medoids, labels, near, ctl, 1);
   AG_CHECK_LAUNCH();
   k_kmed_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, near, size, within, cost, n_iter, status, ctl);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_silhouette(const float* dist, int32_t G, int32_t K, const int32_t* labels, double* a, double* b, double* s,
+                                 int32_t* other, int32_t* size, double* cluster_mean, double* mean, int32_t* status, uint64_t* work,
+                                 void* stream) {
+  if (!dist || !labels || !a || !b || !s || !other || !size || !cluster_mean || !mean || !status || !work || G < 0)
+    return AGDIFF_ERR_ARG;
+  if (K < 1 || K > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_ARG;
+  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  hipStream_t st = (hipStream_t)stream;
+  if (G == 0) {                                     // no launch: status = 0 and size = 0 (all bits clear), mean and cluster_mean NaN (all bits set), by memsets on the stream
+    const struct { void* p; int v; size_t n; } outs[] = {{status, 0, 4}, {size, 0, (size_t)K * 4}, {mean, 0xff, 8}, {cluster_mean, 0xff, (size_t)K * 8}};
+    for (const auto& o : outs) {
+      const hipError_t e = hipMemsetAsync(o.p, o.v, o.n, st);
+      if (e == hipSuccess) continue;
+      (void)hipGetLastError();
+      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
+    }
+    return AGDIFF_OK;
+  }
+  int32_t* ctl = (int32_t*)work;
+  int64_t* T = (int64_t*)(work + SIL_CTL_WORDS * 4 / 8);
+  k_sil_init<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, a, b, s, other, size, cluster_mean, mean, status, ctl);
+  AG_CHECK_LAUNCH();
+  if (K <= AG_SIL_WAVE_ROW_MAX_K)                   // one row per wave, 4 K bins per workgroup (<= 32 KB)
+    k_sil_rows<4><<<dim3((unsigned)((G + 3) / 4)), dim3(256), (size_t)4 * K * 8, st>>>(dist, G, K, labels, size, a, b, s, other, T, ctl);
+  else                                              // one row per workgroup, K bins (<= 32 KB)
+    k_sil_rows<1><<<dim3((unsigned)G), dim3(256), (size_t)K * 8, st>>>(dist, G, K, labels, size, a, b, s, other, T, ctl);
+  AG_CHECK_LAUNCH();
+  k_sil_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, T, size, cluster_mean, mean, status, ctl);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

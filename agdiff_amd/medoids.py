@@ -15,10 +15,11 @@ are made on a fixed-point image of the matrix (2^-28), so the result is exact an
 picks.pick_conformers returns the extremes of the ensemble and clusters.cluster_conformers takes a threshold and returns
 however many families it leaves; this takes the count and returns centres.
 
-What this is not: it is not PAM's swap phase -- a medoid only ever moves inside its own cluster -- there is no k-means++
-seeding and there are no silhouette scores.  The result is a local optimum that depends on the seeds; MaxMin seeds start from
-the outliers of the ensemble, and on random point clouds they can end at a slightly worse optimum than plain seeds
-(init="first").  Agreement with any other package's k-medoids is not claimed.
+What this is not: it is not PAM's swap phase -- a medoid only ever moves inside its own cluster -- and there is no k-means++
+seeding.  The result is a local optimum that depends on the seeds; MaxMin seeds start from the outliers of the ensemble, and on
+random point clouds they can end at a slightly worse optimum than plain seeds (init="first").  Agreement with any other
+package's k-medoids is not claimed.  Whether K families are there at all is agdiff_amd.silhouette's question: it scores this
+module's `labels` and sweeps K.
 
     python -m agdiff_amd.medoids --samples out/samples_all.npz --testset test.npz --count K [--tfd] [--tfd-rings]
                                  [--init maxmin|first] [--max-iter N] [--align] [--fix-handedness] [--fix-double-bonds]
@@ -90,7 +91,6 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
         hand, ez_state            as prune_conformers returns them, when the fixes ran
     With no usable conformer the K-sized tensors are empty, `labels` is all -1 and `cost` is 0.  At most AGDIFF_PRUNE_MAX_CONFS
     conformers.  Not PAM, no k-means++, a local optimum that depends on the seeds: see the module's docstring."""
-    import torch
     if int(k) != k or k < 1:
         raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
     if int(max_iter) != max_iter or not 1 <= max_iter <= MAX_ITER:
@@ -111,6 +111,13 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
             if mask is not None and not mask[s]:
                 raise ValueError("init: %d is a conformer %s" % (s, why))
     m = _usable_matrix(item, "medoid_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_seeds)
+    return _from_matrix(m, k, init, seeds, max_iter, align)
+
+
+def _from_matrix(m, k, init, seeds, max_iter, align):
+    """medoid_conformers after its matrix: the seeds, the walk and the result, from the namespace m of ensemble._usable_matrix.
+    `seeds`: the checked explicit seeds in the item's own numbering, or None when `init` is "maxmin" or "first"."""
+    import torch
     if m.G == 0:                                         # no usable conformer: all masked out
         none = lambda dtype: torch.empty(0, dtype=dtype, device=m.gen.device)
         return _attach(m, {"medoids": none(torch.int32), "labels": _scatter(m, none(torch.int32), -1),
@@ -127,7 +134,14 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
         picks, _, _, _, n_picked, _ = maxmin_pick(out, G, K)
         K = int(n_picked.item())
         first = picks[:K].contiguous()
-    medoids, labels, near, size, within, cost, n_iter, status = kmedoids(out, G, first, max_iter=max_iter)
+    return _result(m, kmedoids(out, G, first, max_iter=max_iter), seeds, align)
+
+
+def _result(m, walked, seeds, align):
+    """what kmedoids returned for the usable conformers of m as medoid_conformers' dict, in the item's own numbering"""
+    import torch
+    medoids, labels, near, size, within, cost, n_iter, status = walked
+    dev = m.out.device
     status = int(status.item())
     if status == 2:
         raise ValueError("init: a seed is as far from conformer %d as the matrix can say (not a number >= 0 and <= %d): the "

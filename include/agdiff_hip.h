@@ -45,6 +45,7 @@ extern "C" {
 #define AGDIFF_KMEDOIDS_MAX_DIST 4096 /* agdiff_kmedoids: a matrix entry above this (or not >= 0) counts as this far: 2^40 in fixed point */
 #define AGDIFF_KMEDOIDS_MAX_ITER 128 /* most updates agdiff_kmedoids may be asked for: it enqueues three launches for each */
 #define AGDIFF_KMEDOIDS_WORK_BYTES 131072 /* the scratch agdiff_kmedoids is handed: control words and one 64-bit key per conformer */
+#define AGDIFF_SILHOUETTE_WORK_BYTES 65536 /* the scratch agdiff_silhouette is handed: control words and one 64-bit integer per conformer */
 #define AGDIFF_TFD_MAX_COLUMNS 512/* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_RING_MAX_ATOMS 32 /* most atoms of one ring of agdiff_ring_coords (the fewest: 4) */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
@@ -898,6 +899,53 @@ int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32_t first, f
 int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t max_iter,
                     int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within,
                     double* cost, int32_t* n_iter, int32_t* status, uint64_t* work, void* stream);
+
+/* How good is a clustering, and how many families are there: the silhouette coefficient (Rousseeuw 1987) of every conformer of
+ * a GIVEN clustering over the same FLOAT matrix, dist [G][G] fp32, contiguous, made exact the way agdiff_kmedoids is: all sums
+ * are made on the fixed-point image of the entries, so no result depends on a summation order and everything below is exact.
+ *   - validity and the quantiser are agdiff_kmedoids': valid(x) = x >= 0.0f && x <= 4096.0f; Q(x) = uint64(rint((double)x * 2^28)),
+ *     rounding half to even, for a valid x and Q(x) = 2^40 for an entry that is not valid; -0.0f counts as 0.
+ *   - labels [G]: labels[j] == -1 means conformer j is LEFT OUT: it takes no part and is never read as a column.
+ *     0 <= labels[j] < K means j is a member of rank labels[j].  Any other value gives status = 2 and nothing else is computed.
+ *     The check is made on the device: the host never reads `labels`.
+ *   - sizes: size[c] is the number of members of rank c.  A rank with no member is allowed (K may exceed the ranks used, and K
+ *     may exceed G); an EMPTY RANK IS NEVER anybody's other cluster.
+ *   - sums: for a member i and a rank c, S_c(i) = the sum of Q(dist[i][j]) over the members j != i of rank c, taken along ROW i.
+ *     Symmetry is not required and the diagonal is never read.  The sums are uint64 sums of integers, <= 4096 * 2^40 = 2^52.
+ *   - means, in fp64 and in units of 2^-28, each ONE correctly rounded division of two exactly converted integers:
+ *       ma  = (double)S_own / (double)(size_own - 1), and 0 when size_own == 1
+ *       m_c = (double)S_c / (double)size[c]
+ *   - mb is the smallest m_c over the non-empty ranks c != own and other[i] is that rank, ties to the LOWEST rank.  With no
+ *     such rank other[i] = -1 and b[i] = NaN.
+ *   - the coefficient: s(i) = 0 when size_own == 1, when there is no other non-empty rank, or when max(ma, mb) == 0; otherwise
+ *     s(i) = (mb - ma) / max(ma, mb): one fp64 subtraction and one fp64 division.
+ *   - a[i] = ma * 2^-28 and b[i] = mb * 2^-28, exact scalings.  A left-out conformer gets a, b and s NaN and other -1.
+ *   - aggregates: T(i) = (int64)rint(s(i) * 2^40) (the product is exact); cluster_mean[c] = ((double)(the sum of T(i) over the
+ *     members of c) / (double)size[c]) * 2^-40, NaN for an empty rank; mean[0] is the same quantity over all members, NaN when
+ *     there are none.  The sums of T are integer sums, <= 2^52 in magnitude.
+ * Outputs, every entry written in every case:
+ *   a [G], b [G], s [G]   fp64: the mean distance to the own cluster's other members, to the nearest other cluster, the coefficient
+ *   other [G]             the rank of that nearest other cluster, -1 for none
+ *   size [K]              the members of each rank
+ *   cluster_mean [K]      the mean coefficient of each rank's members
+ *   mean [1]              the mean coefficient of all members
+ *   status [1]            0, or 2 for a bad label
+ * On status = 2: a, b, s, cluster_mean and mean NaN, other all -1 and size 0.
+ * work: caller-provided scratch of AGDIFF_SILHOUETTE_WORK_BYTES, 8-byte aligned; its contents are ignored on entry and unspecified
+ * on return.  `dist` needs 4-byte alignment only, and any G, odd ones included.
+ * Three launches: the label check and the sizes (one workgroup), the rows (row i is streamed once into K uint64 bins in LDS; one
+ * row per wave for K <= 1024, one row per workgroup above, so that a workgroup's bins take at most 32 KB), the aggregates (one
+ * workgroup).  What crosses lanes is an integer or a (mean, rank) pair compared under a total order.  No cooperative launch, no
+ * workgroup waits on another, no atomics on global memory; every loop is counted; deterministic bit for bit.
+ * A null pointer or G < 0: AGDIFF_ERR_ARG; K outside [1, AGDIFF_PRUNE_MAX_CONFS]: AGDIFF_ERR_ARG; `work` not 8-byte aligned:
+ * AGDIFF_ERR_ARG; G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT (the argument errors come first); G == 0: status = 0, size 0,
+ * cluster_mean and mean NaN, and no launch.
+ * This is the full silhouette, O(G^2): not the simplified (medoid-based) one, and neither a gap statistic nor Davies-Bouldin.
+ * Agreement with scikit-learn's silhouette_samples is by definition only, not bit for bit. */
+int agdiff_silhouette(const float* dist, int32_t G, int32_t K, const int32_t* labels,
+                      double* a, double* b, double* s, int32_t* other,
+                      int32_t* size, double* cluster_mean, double* mean, int32_t* status,
+                      uint64_t* work, void* stream);
 
 /* Rigid superposition (rdkit AlignMolConformers: atoms keep their labels, identity mapping): for each conformer the proper
  * rotation R and translation that minimise the RMSD to `target` over the atoms `atom_idx` (Horn's quaternion, fp64), applied
