@@ -678,15 +678,30 @@ __device__ __forceinline__ uint64_t ag_shfl_xor_u64(uint64_t k, int o) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-__global__ void __launch_bounds__(1024) k_kmed_init(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init,
-                                                    int32_t* __restrict__ medoids, int32_t* __restrict__ labels, float* __restrict__ near,
-                                                    int32_t* __restrict__ size, double* __restrict__ within, double* __restrict__ cost,
-                                                    int32_t* __restrict__ n_iter, int32_t* __restrict__ status, int32_t* __restrict__ ctl) {
+// the status-2 fill of agdiff_kmedoids, agdiff_pam_build and agdiff_pam_swap, by one workgroup of 1024 threads: every output is
+// written and `done` is set, so nothing after it does anything
+__device__ __forceinline__ void ag_kmed_fill_bad(int G, int K, int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                 float* __restrict__ near, int32_t* __restrict__ size, double* __restrict__ within,
+                                                 double* __restrict__ cost, int32_t* __restrict__ n_iter, int32_t* __restrict__ status,
+                                                 int32_t* __restrict__ ctl) {
+  const int t = threadIdx.x;
+  for (int r = t; r < K; r += 1024) { medoids[r] = -1; size[r] = 0; within[r] = 0.0; }
+  for (int j = t; j < G; j += 1024) { labels[j] = -1; near[j] = __builtin_nanf(""); }
+  if (t < KM_CTL_WORDS) ctl[t] = t == KM_DONE ? 1 : (t == KM_STATUS ? 2 : 0);
+  if (t == 0) { cost[0] = 0.0; n_iter[0] = 0; status[0] = 2; }
+}
+
+// the seed check of agdiff_kmedoids (s0 = init[0], status0 = 0) and of agdiff_pam_swap (s0 = its anchor, status0 = 1: "a negative
+// exchange may be left" until a choose says otherwise), by one workgroup of 1024 threads: s0's row decides who is eligible
+__device__ __forceinline__ void ag_kmed_check_seeds(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init, int s0,
+                                                    int status0, int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                    float* __restrict__ near, int32_t* __restrict__ size, double* __restrict__ within,
+                                                    double* __restrict__ cost, int32_t* __restrict__ n_iter, int32_t* __restrict__ status,
+                                                    int32_t* __restrict__ ctl) {
   __shared__ int32_t s_seen[AGDIFF_PRUNE_MAX_CONFS];
   const int t = threadIdx.x;
   for (int j = t; j < G; j += 1024) s_seen[j] = 0;
   __syncthreads();
-  const int s0 = init[0];
   const bool s0_ok = (unsigned)s0 < (unsigned)G;    // (block-uniform)
   int bad = s0_ok ? 0 : 1;
   if (s0_ok) {
@@ -700,13 +715,17 @@ __global__ void __launch_bounds__(1024) k_kmed_init(const float* __restrict__ di
   bad = __syncthreads_or(bad);
   if (!bad) {
     for (int r = t; r < K; r += 1024) medoids[r] = init[r];
-    if (t < KM_CTL_WORDS) ctl[t] = 0;
+    if (t < KM_CTL_WORDS) ctl[t] = t == KM_STATUS ? status0 : 0;
     return;
   }
-  for (int r = t; r < K; r += 1024) { medoids[r] = -1; size[r] = 0; within[r] = 0.0; }
-  for (int j = t; j < G; j += 1024) { labels[j] = -1; near[j] = __builtin_nanf(""); }
-  if (t < KM_CTL_WORDS) ctl[t] = t == KM_DONE ? 1 : (t == KM_STATUS ? 2 : 0);
-  if (t == 0) { cost[0] = 0.0; n_iter[0] = 0; status[0] = 2; }
+  ag_kmed_fill_bad(G, K, medoids, labels, near, size, within, cost, n_iter, status, ctl);
+}
+
+__global__ void __launch_bounds__(1024) k_kmed_init(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init,
+                                                    int32_t* __restrict__ medoids, int32_t* __restrict__ labels, float* __restrict__ near,
+                                                    int32_t* __restrict__ size, double* __restrict__ within, double* __restrict__ cost,
+                                                    int32_t* __restrict__ n_iter, int32_t* __restrict__ status, int32_t* __restrict__ ctl) {
+  ag_kmed_check_seeds(dist, G, K, init, init[0], 0, medoids, labels, near, size, within, cost, n_iter, status, ctl);
 }
 
 // final = 0: an assign of the loop, skipped once `done` is set.  final = 1: the assign after the last update, which runs only
@@ -995,6 +1014,243 @@ __global__ void __launch_bounds__(1024) k_sil_finish(int G, int K, const int32_t
     mean[0] = n > 0 ? ((double)(int64_t)all / (double)n) * (1.0 / 1099511627776.0) : __builtin_nan("");
     status[0] = 0;
   }
+}
+
+// PAM (BUILD + SWAP) over the same float matrix (the rule: include/agdiff_hip.h, agdiff_pam_build / agdiff_pam_swap).  Again a
+// sequence of launches with the kernel boundary as the only grid-wide ordering:
+//   k_pam_swap_init   one workgroup: agdiff_kmedoids' seed check under the explicit anchor (ag_kmed_check_seeds)
+//   k_pam_build_init  one workgroup: the anchor, the eligible count against K, tag and dn = 2^40 ("no medoid yet": with it rank 0
+//                     is the same arg-max of the gain as every later rank)
+//   k_pam_state       k_kmed_assign's shape (64 columns per workgroup, its 4 waves over the ranks), keeping the best key AND the
+//                     second-best Q + 1: writes labels and near, and into `work` dn, ds (all ones: none) and
+//                     tag = -1 (ineligible) or n << 1 | is-a-medoid
+//   k_pam_rows        k_sil_rows' shape: candidate row c is streamed once with coalesced 4-byte loads; gain(c) is summed in
+//                     registers and reduced by shuffles; with BINS the terms of corr(c, r) go into K uint64 bins in LDS (one row
+//                     per wave up to K = 1024, one per workgroup above: <= 32 KB), then the lanes stride over the bins and
+//                     min-reduce the pairs (delta, rank).  One record per row: recD = delta (BUILD: -gain), recR = the rank;
+//                     INT64_MAX for a row that is no candidate.
+//   k_pam_choose      one workgroup over the G records (ag_pam_best: lowest recD, then lowest index): a negative delta is applied
+//                     and counted, anything else ends the walk with status 0
+//   k_pam_build_pick  one workgroup: the same arg-min, then medoids[p], tag and dn = min(dn, Q(row c)) along the picked row
+//   k_kmed_finish     size, within, cost, n_swaps, status: as it is, from the same control words
+// `work`: 8 control words (KM_DONE, KM_STATUS, KM_ITERS = the swaps made), then dn, ds, recD (64-bit each), tag, recR (32-bit
+// each), one per conformer.  Every kernel of a loop reads ctl[KM_DONE] first and returns when it is set.  Sums are on integers
+// (<= 2^52, differences in int64), LDS atomics are adds on integers, there are no global atomics and no workgroup waits on
+// another.  Every loop is counted.
+#define AG_PAM_NONE 0x7fffffffffffffffll
+static_assert(AGDIFF_PAM_WORK_BYTES >= KM_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * (3 * 8 + 2 * 4), "agdiff_pam_*: control words + dn, ds, recD, tag, recR per conformer");
+static_assert(AGDIFF_PAM_MAX_SWAPS <= 4095, "agdiff_pam_swap: the launches of one call");
+
+__global__ void __launch_bounds__(1024) k_pam_swap_init(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init,
+                                                        int anchor, int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                        float* __restrict__ near, int32_t* __restrict__ size, double* __restrict__ within,
+                                                        double* __restrict__ cost, int32_t* __restrict__ n_swaps,
+                                                        int32_t* __restrict__ status, int32_t* __restrict__ ctl) {
+  ag_kmed_check_seeds(dist, G, K, init, anchor, 1, medoids, labels, near, size, within, cost, n_swaps, status, ctl);
+}
+
+__global__ void __launch_bounds__(1024) k_pam_build_init(const float* __restrict__ dist, int G, int K, int anchor,
+                                                         int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                         float* __restrict__ near, int32_t* __restrict__ size, double* __restrict__ within,
+                                                         double* __restrict__ cost, int32_t* __restrict__ n_swaps,
+                                                         int32_t* __restrict__ status, int32_t* __restrict__ ctl,
+                                                         uint64_t* __restrict__ dn, int32_t* __restrict__ tag) {
+  __shared__ int s_n;
+  const int t = threadIdx.x;
+  if (t == 0) s_n = 0;
+  __syncthreads();
+  const bool ok = (unsigned)anchor < (unsigned)G;   // (block-uniform)
+  if (ok) {
+    int n = 0;
+    for (int j = t; j < G; j += 1024) {
+      const bool e = j == anchor || ag_kmed_valid(dist[(size_t)anchor * (size_t)G + j]);
+      tag[j] = e ? 0 : -1;
+      dn[j] = 1ull << 40;
+      n += e ? 1 : 0;
+    }
+    atomicAdd(&s_n, n);
+  }
+  __syncthreads();
+  if (ok && s_n >= K) {
+    if (t < KM_CTL_WORDS) ctl[t] = 0;
+    return;
+  }
+  ag_kmed_fill_bad(G, K, medoids, labels, near, size, within, cost, n_swaps, status, ctl);
+}
+
+// k joins the running (best key, second-best Q + 1) of one column; ~0 is "none" in both places.  Keys differ in their rank bits.
+__device__ __forceinline__ void ag_pam_push(uint64_t& k1, uint64_t& s2, uint64_t k) {
+  const bool lower = k < k1;
+  const uint64_t loser = lower ? k1 : k;
+  k1 = lower ? k : k1;
+  const uint64_t ls = loser == ~0ull ? ~0ull : loser >> 12;
+  s2 = ls < s2 ? ls : s2;
+}
+
+// final = 0: a state of the loop (or BUILD's one), skipped once `done` is set.  final = 1: the state after the last swap, which
+// runs only after a status-1 stop (after a status-0 stop the labels already belong to the returned medoids).
+__global__ void __launch_bounds__(256) k_pam_state(const float* __restrict__ dist, int G, int K, int anchor,
+                                                   const int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                   float* __restrict__ near, const int32_t* __restrict__ ctl, uint64_t* __restrict__ dn,
+                                                   uint64_t* __restrict__ ds, int32_t* __restrict__ tag, int final) {
+  if (final ? ctl[KM_STATUS] != 1 : ctl[KM_DONE] != 0) return;
+  __shared__ uint64_t s_key[4][64], s_sec[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + lane;
+  const bool in = j < G;
+  const int jc = in ? j : G - 1;                    // (a column past the end reads the last one and writes nothing)
+  uint64_t key = ~0ull, sec = ~0ull;
+#pragma unroll 4
+  for (int r = wv; r < K; r += 4) {
+    const int m = medoids[r];                       // (wave-uniform)
+    const float x = dist[(size_t)m * (size_t)G + jc];
+    ag_pam_push(key, sec, (m == jc ? 0ull : (ag_kmed_q(x) + 1) << 12) | (uint64_t)r);
+  }
+  s_key[wv][lane] = key;
+  s_sec[wv][lane] = sec;
+  __syncthreads();
+  if (wv != 0 || !in) return;
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const uint64_t s = s_sec[w][lane];
+    ag_pam_push(key, sec, s_key[w][lane]);
+    sec = s < sec ? s : sec;
+  }
+  const bool eligible = j == anchor || ag_kmed_valid(dist[(size_t)anchor * (size_t)G + j]);
+  const int r = (int)(key & 4095);
+  const int m = medoids[r];
+  const float x = dist[(size_t)m * (size_t)G + j];
+  labels[j] = eligible ? r : -1;
+  near[j] = !eligible ? __builtin_nanf("") : ((key >> 12) == 0 || x == 0.0f ? 0.0f : x);     // (-0 is written as +0)
+  tag[j] = eligible ? (r << 1) | (m == j ? 1 : 0) : -1;
+  dn[j] = (key >> 12) == 0 ? 0ull : (key >> 12) - 1;
+  ds[j] = sec == ~0ull ? ~0ull : sec - 1;           // (K == 1: no other rank, min(ds, x) = x)
+}
+
+// the smaller of two (delta, index) pairs: lowest delta, then lowest index (a rank in k_pam_rows, a conformer in ag_pam_best)
+__device__ __forceinline__ void ag_pam_min_pair(int64_t& d, int& c, int64_t od, int oc) {
+  const bool take = od < d || (od == d && oc < c);
+  d = take ? od : d;
+  c = take ? oc : c;
+}
+
+template <int ROWS, bool BINS>
+__global__ void __launch_bounds__(256) k_pam_rows(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ tag,
+                                                  const uint64_t* __restrict__ dn, const uint64_t* __restrict__ ds,
+                                                  int64_t* __restrict__ recD, int32_t* __restrict__ recR, const int32_t* __restrict__ ctl) {
+  static_assert(ROWS == 4 || (ROWS == 1 && BINS), "one row per wave, or with bins one per workgroup");
+  if (ctl[KM_DONE] != 0) return;                    // (grid-uniform)
+  extern __shared__ unsigned long long s_bins[];    // [ROWS][K] with BINS
+  __shared__ unsigned long long s_pg[4];
+  __shared__ long long s_pd[4];
+  __shared__ int s_pr[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int NT = ROWS == 4 ? 64 : 256;              // the threads that share a row
+  const int tid = ROWS == 4 ? lane : (int)threadIdx.x;
+  const int i = ROWS == 4 ? blockIdx.x * 4 + wv : (int)blockIdx.x;     // (wave-uniform; every wave reaches every barrier)
+  unsigned long long* __restrict__ bins = s_bins + (ROWS == 4 ? (size_t)wv * (size_t)K : 0);
+  const int own = i < G ? tag[i] : -1;
+  const bool cand = own >= 0 && (own & 1) == 0;     // eligible and not a medoid
+  if (BINS) {
+    for (int c = tid; c < K; c += NT) bins[c] = 0ull;
+    __syncthreads();
+  }
+  uint64_t gain = 0;
+  if (cand) {
+    const float* __restrict__ row = dist + (size_t)i * (size_t)G;
+#pragma unroll 4
+    for (int j = tid; j < G; j += NT) {
+      const int tg = tag[j];
+      if (tg < 0) continue;                         // (a left-out column takes no part)
+      const uint64_t x = j == i ? 0ull : ag_kmed_q(row[j]);            // (the diagonal counts as 0)
+      const uint64_t d1 = dn[j], m1 = x < d1 ? x : d1;
+      gain += d1 - m1;
+      if (BINS) {
+        const uint64_t d2 = ds[j], term = (x < d2 ? x : d2) - m1;      // (>= 0: ds >= dn)
+        if (term != 0) atomicAdd(&bins[tg >> 1], (unsigned long long)term);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) gain += ag_shfl_xor_u64(gain, o);
+  int64_t bd = AG_PAM_NONE;
+  int br = 0x7fffffff;
+  if (BINS) {
+    if (ROWS == 1 && lane == 0) s_pg[wv] = gain;
+    __syncthreads();
+    if (ROWS == 1) gain = s_pg[0] + s_pg[1] + s_pg[2] + s_pg[3];
+    if (cand)
+      for (int c = tid; c < K; c += NT) ag_pam_min_pair(bd, br, (int64_t)bins[c] - (int64_t)gain, c);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ag_pam_min_pair(bd, br, (int64_t)ag_shfl_xor_u64((uint64_t)bd, o), __shfl_xor(br, o));
+    if (ROWS == 1) {
+      if (lane == 0) { s_pd[wv] = bd; s_pr[wv] = br; }
+      __syncthreads();
+#pragma unroll
+      for (int w = 0; w < 4; ++w) ag_pam_min_pair(bd, br, (int64_t)s_pd[w], s_pr[w]);
+    }
+  } else if (cand) {
+    bd = -(int64_t)gain;                            // BUILD: the largest gain is the lowest record
+    br = 0;
+  }
+  if (tid != 0 || i >= G) return;
+  recD[i] = bd;
+  recR[i] = cand ? br : 0;
+}
+
+// the arg-min of the G records by one workgroup of 1024 threads: lowest recD, then lowest index; (AG_PAM_NONE, INT_MAX) when
+// no row is a candidate.  Block-uniform on return.
+__device__ __forceinline__ void ag_pam_best(int G, const int64_t* __restrict__ recD, int64_t& bd, int& bj) {
+  __shared__ long long s_d[16];
+  __shared__ int s_j[16];
+  const int t = threadIdx.x;
+  bd = AG_PAM_NONE;
+  bj = 0x7fffffff;
+  for (int j = t; j < G; j += 1024) ag_pam_min_pair(bd, bj, recD[j], j);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ag_pam_min_pair(bd, bj, (int64_t)ag_shfl_xor_u64((uint64_t)bd, o), __shfl_xor(bj, o));
+  if ((t & 63) == 0) { s_d[t >> 6] = bd; s_j[t >> 6] = bj; }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 16; ++w) ag_pam_min_pair(bd, bj, (int64_t)s_d[w], s_j[w]);
+}
+
+__global__ void __launch_bounds__(1024) k_pam_choose(int G, int max_swaps, const int64_t* __restrict__ recD,
+                                                     const int32_t* __restrict__ recR, int32_t* __restrict__ medoids,
+                                                     int32_t* __restrict__ ctl) {
+  if (ctl[KM_DONE] != 0) return;                    // (block-uniform: ctl is written only after the barrier of ag_pam_best)
+  int64_t bd;
+  int bj;
+  ag_pam_best(G, recD, bd, bj);
+  if (threadIdx.x != 0) return;
+  if (bd < 0) {                                     // the exchange lowers the cost: rank recR[bj] moves to conformer bj
+    medoids[recR[bj]] = bj;
+    const int n = ctl[KM_ITERS] + 1;
+    ctl[KM_ITERS] = n;
+    if (n >= max_swaps) ctl[KM_DONE] = 1;           // (status stays 1: whether a negative exchange is left was not looked at)
+  } else {
+    ctl[KM_STATUS] = 0;
+    ctl[KM_DONE] = 1;
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_pam_build_pick(const float* __restrict__ dist, int G, int p, const int64_t* __restrict__ recD,
+                                                         int32_t* __restrict__ medoids, uint64_t* __restrict__ dn,
+                                                         int32_t* __restrict__ tag, const int32_t* __restrict__ ctl) {
+  if (ctl[KM_DONE] != 0) return;
+  int64_t bd;
+  int bj;
+  ag_pam_best(G, recD, bd, bj);
+  if (bd == AG_PAM_NONE) return;                    // (never: K <= the eligible count; block-uniform)
+  const int t = threadIdx.x;
+  const float* __restrict__ row = dist + (size_t)bj * (size_t)G;
+  for (int o = t; o < G; o += 1024) {
+    if (tag[o] < 0) continue;
+    const uint64_t x = o == bj ? 0ull : ag_kmed_q(row[o]), d = dn[o];
+    dn[o] = x < d ? x : d;
+    if (o == bj) tag[o] = 1;
+  }
+  if (t == 0) medoids[p] = bj;
 }
 
 // eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
@@ -2690,6 +2946,94 @@ extern "C" int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const in
   k_kmed_assign<<<cols, dim3(256), 0, st>>>(dist, G, K, init, medoids, labels, near, ctl, 1);
   AG_CHECK_LAUNCH();
   k_kmed_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, near, size, within, cost, n_iter, status, ctl);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+// the argument checks, the G == 0 memsets and the carving of `work` that agdiff_pam_build and agdiff_pam_swap share; returns
+// AGDIFF_OK with *launch = false when there is nothing to launch
+struct ag_pam_work { int32_t* ctl; uint64_t *dn, *ds; int64_t* recD; int32_t *tag, *recR; };
+static int ag_pam_prepare(const float* dist, int32_t G, int32_t K, bool rest_ok, int32_t* medoids, int32_t* labels, float* near,
+                          int32_t* size, double* within, double* cost, int32_t* n_swaps, int32_t* status, uint64_t* work,
+                          hipStream_t st, ag_pam_work* w, bool* launch) {
+  *launch = false;
+  if (!dist || !medoids || !labels || !near || !size || !within || !cost || !n_swaps || !status || !work || G < 0) return AGDIFF_ERR_ARG;
+  if (G > 0 && (K < 1 || K > G || !rest_ok)) return AGDIFF_ERR_ARG;
+  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) {                                     // no launch: n_swaps = 0, status = 0 and cost = 0 (all bits clear) by memsets on the stream
+    const std::pair<void*, size_t> outs[] = {{n_swaps, 4}, {status, 4}, {cost, 8}};
+    for (const auto& o : outs) {
+      const hipError_t e = hipMemsetAsync(o.first, 0, o.second, st);
+      if (e == hipSuccess) continue;
+      (void)hipGetLastError();
+      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
+    }
+    return AGDIFF_OK;
+  }
+  w->ctl = (int32_t*)work;
+  w->dn = work + KM_CTL_WORDS * 4 / 8;
+  w->ds = w->dn + AGDIFF_PRUNE_MAX_CONFS;
+  w->recD = (int64_t*)(w->ds + AGDIFF_PRUNE_MAX_CONFS);
+  w->tag = (int32_t*)(w->recD + AGDIFF_PRUNE_MAX_CONFS);
+  w->recR = w->tag + AGDIFF_PRUNE_MAX_CONFS;
+  *launch = true;
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_pam_build(const float* dist, int32_t G, int32_t K, int32_t anchor, int32_t* medoids, int32_t* labels, float* near,
+                                int32_t* size, double* within, double* cost, int32_t* n_swaps, int32_t* status, uint64_t* work,
+                                void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  ag_pam_work w;
+  bool launch;
+  const int rc = ag_pam_prepare(dist, G, K, true, medoids, labels, near, size, within, cost, n_swaps, status, work, st, &w, &launch);
+  if (!launch) return rc;
+  const dim3 cols((unsigned)((G + 63) / 64)), rows((unsigned)((G + 3) / 4));
+  k_pam_build_init<<<dim3(1), dim3(1024), 0, st>>>(dist, G, K, anchor, medoids, labels, near, size, within, cost, n_swaps, status, w.ctl,
+                                                   w.dn, w.tag);
+  AG_CHECK_LAUNCH();
+  for (int p = 0; p < K; ++p) {                     // one pass over the candidates' rows and one pick per rank
+    k_pam_rows<4, false><<<rows, dim3(256), 0, st>>>(dist, G, K, w.tag, w.dn, w.ds, w.recD, w.recR, w.ctl);
+    AG_CHECK_LAUNCH();
+    k_pam_build_pick<<<dim3(1), dim3(1024), 0, st>>>(dist, G, p, w.recD, medoids, w.dn, w.tag, w.ctl);
+    AG_CHECK_LAUNCH();
+  }
+  k_pam_state<<<cols, dim3(256), 0, st>>>(dist, G, K, anchor, medoids, labels, near, w.ctl, w.dn, w.ds, w.tag, 0);
+  AG_CHECK_LAUNCH();
+  k_kmed_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, near, size, within, cost, n_swaps, status, w.ctl);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_pam_swap(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t anchor, int32_t max_swaps,
+                               int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within, double* cost,
+                               int32_t* n_swaps, int32_t* status, uint64_t* work, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  ag_pam_work w;
+  bool launch;
+  if (!init) return AGDIFF_ERR_ARG;
+  const int rc = ag_pam_prepare(dist, G, K, max_swaps >= 0 && max_swaps <= AGDIFF_PAM_MAX_SWAPS, medoids, labels, near, size, within,
+                                cost, n_swaps, status, work, st, &w, &launch);
+  if (!launch) return rc;
+  const dim3 cols((unsigned)((G + 63) / 64)), rows((unsigned)((G + 3) / 4));
+  k_pam_swap_init<<<dim3(1), dim3(1024), 0, st>>>(dist, G, K, init, anchor, medoids, labels, near, size, within, cost, n_swaps, status,
+                                                  w.ctl);
+  AG_CHECK_LAUNCH();
+  for (int it = 0; it < max_swaps; ++it) {          // every launch returns at once after the choose that ended the walk
+    k_pam_state<<<cols, dim3(256), 0, st>>>(dist, G, K, anchor, medoids, labels, near, w.ctl, w.dn, w.ds, w.tag, 0);
+    AG_CHECK_LAUNCH();
+    if (K <= AG_SIL_WAVE_ROW_MAX_K)                 // one row per wave, 4 K bins per workgroup (<= 32 KB)
+      k_pam_rows<4, true><<<rows, dim3(256), (size_t)4 * K * 8, st>>>(dist, G, K, w.tag, w.dn, w.ds, w.recD, w.recR, w.ctl);
+    else                                            // one row per workgroup, K bins (<= 32 KB)
+      k_pam_rows<1, true><<<dim3((unsigned)G), dim3(256), (size_t)K * 8, st>>>(dist, G, K, w.tag, w.dn, w.ds, w.recD, w.recR, w.ctl);
+    AG_CHECK_LAUNCH();
+    k_pam_choose<<<dim3(1), dim3(1024), 0, st>>>(G, max_swaps, w.recD, w.recR, medoids, w.ctl);
+    AG_CHECK_LAUNCH();
+  }
+  k_pam_state<<<cols, dim3(256), 0, st>>>(dist, G, K, anchor, medoids, labels, near, w.ctl, w.dn, w.ds, w.tag, 1);
+  AG_CHECK_LAUNCH();
+  k_kmed_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, near, size, within, cost, n_swaps, status, w.ctl);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

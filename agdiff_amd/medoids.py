@@ -15,7 +15,8 @@ are made on a fixed-point image of the matrix (2^-28), so the result is exact an
 picks.pick_conformers returns the extremes of the ensemble and clusters.cluster_conformers takes a threshold and returns
 however many families it leaves; this takes the count and returns centres.
 
-What this is not: it is not PAM's swap phase -- a medoid only ever moves inside its own cluster -- and there is no k-means++
+What this is not: it is not PAM's swap phase -- a medoid only ever moves inside its own cluster; PAM (BUILD + SWAP) is
+agdiff_amd.pam, which needs no seeds and can polish this module's result -- and there is no k-means++
 seeding.  The result is a local optimum that depends on the seeds; MaxMin seeds start from the outliers of the ensemble, and on
 random point clouds they can end at a slightly worse optimum than plain seeds (init="first").  Agreement with any other
 package's k-medoids is not claimed.  Whether K families are there at all is agdiff_amd.silhouette's question: it scores this
@@ -90,7 +91,8 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
                                   is, bit for bit)
         hand, ez_state            as prune_conformers returns them, when the fixes ran
     With no usable conformer the K-sized tensors are empty, `labels` is all -1 and `cost` is 0.  At most AGDIFF_PRUNE_MAX_CONFS
-    conformers.  Not PAM, no k-means++, a local optimum that depends on the seeds: see the module's docstring."""
+    conformers.  Not PAM (that is agdiff_amd.pam), no k-means++, a local optimum that depends on the seeds: see the module's
+    docstring."""
     if int(k) != k or k < 1:
         raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
     if int(max_iter) != max_iter or not 1 <= max_iter <= MAX_ITER:

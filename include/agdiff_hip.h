@@ -46,6 +46,8 @@ extern "C" {
 #define AGDIFF_KMEDOIDS_MAX_ITER 128 /* most updates agdiff_kmedoids may be asked for: it enqueues three launches for each */
 #define AGDIFF_KMEDOIDS_WORK_BYTES 131072 /* the scratch agdiff_kmedoids is handed: control words and one 64-bit key per conformer */
 #define AGDIFF_SILHOUETTE_WORK_BYTES 65536 /* the scratch agdiff_silhouette is handed: control words and one 64-bit integer per conformer */
+#define AGDIFF_PAM_MAX_SWAPS 256 /* most swaps one agdiff_pam_swap call may be asked for: it enqueues three launches for each */
+#define AGDIFF_PAM_WORK_BYTES 135168 /* the scratch agdiff_pam_build / agdiff_pam_swap are handed: control words, three 64-bit and two 32-bit words per conformer */
 #define AGDIFF_TFD_MAX_COLUMNS 512/* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_RING_MAX_ATOMS 32 /* most atoms of one ring of agdiff_ring_coords (the fewest: 4) */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
@@ -894,11 +896,65 @@ int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32_t first, f
  * A null pointer or G < 0: AGDIFF_ERR_ARG; for G > 0, K outside [1, G] or max_iter outside [1, AGDIFF_KMEDOIDS_MAX_ITER]:
  * AGDIFF_ERR_ARG; `work` not 8-byte aligned: AGDIFF_ERR_ARG; G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT (the argument errors
  * come first); G == 0: n_iter = 0, status = 0, cost = 0 and no launch.
- * This is not PAM's swap phase: a local optimum that depends on the seeds.  Agreement with any other package's k-medoids is not
- * claimed. */
+ * This is not PAM's swap phase: a local optimum that depends on the seeds (PAM is agdiff_pam_build + agdiff_pam_swap, below).
+ * Agreement with any other package's k-medoids is not claimed. */
 int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t max_iter,
                     int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within,
                     double* cost, int32_t* n_iter, int32_t* status, uint64_t* work, void* stream);
+
+/* Seed-independent representatives: PAM (Kaufman & Rousseeuw), a greedy BUILD that needs no seeds and a steepest-descent SWAP
+ * that tries every (medoid, non-medoid) exchange, so that a medoid can leave its cluster altogether.  Same FLOAT matrix, dist
+ * [G][G] fp32, contiguous; valid(x), Q(x) and the cap are agdiff_kmedoids'.  All arithmetic is on integers: Q values, sums <= 2^52,
+ * signed differences in int64.  The diagonal is never read and counts as 0.  Symmetry is not required: "the distance from medoid
+ * or candidate c to o" is always dist[c][o], along row c.
+ *   - eligibility: both calls take an explicit `anchor`.  Conformer j is eligible iff j == anchor or valid(dist[anchor][j]).  An
+ *     ineligible conformer takes no part and is never a candidate.  Among eligible conformers an entry that is not valid counts
+ *     as 2^40.
+ *   - the state of a medoid set, for each eligible o: n(o) is the nearest medoid's rank, ties to the LOWEST rank, and a medoid
+ *     belongs to its own rank with distance 0 even if a lower-rank medoid is at Q = 0 (agdiff_kmedoids' assign); dn(o) is that Q;
+ *     ds(o) is the smallest Q over the ranks other than n(o), infinite for K = 1: min(ds, x) = x.
+ * agdiff_pam_build makes K medoids in rank order from nothing:
+ *   - rank 0 is the eligible c with the smallest sum over the eligible o != c of Q(dist[c][o]), ties to the lowest index;
+ *   - each further rank is the eligible non-medoid c with the largest gain(c) = dn(c) + the sum over the eligible non-medoids
+ *     o != c of max(dn(o) - Q(dist[c][o]), 0), ties to the lowest index; a gain of 0 still picks;
+ *   - after each pick dn(o) = min(dn(o), Q(dist[c][o])).  (With dn = 2^40 before the first pick, rank 0 is the same rule.)
+ *   - K above the number of eligible conformers or `anchor` outside [0, G): status = 2.  Otherwise status = 0 and n_swaps = 0.
+ * agdiff_pam_swap is steepest descent from the K seeds init [K] (checked as agdiff_kmedoids checks them, eligibility under
+ * `anchor`: a seed or an anchor outside [0, G), a duplicate or an ineligible seed gives status = 2).  One iteration computes for
+ * every candidate c (eligible, not a medoid), with x(o) = Q(dist[c][o]) and x(c) = 0:
+ *     gain(c)     = the sum over all eligible o of dn(o) - min(dn(o), x(o))
+ *     corr(c, r)  = the sum over the o with n(o) == r of min(ds(o), x(o)) - min(dn(o), x(o))
+ *     delta(c, r) = corr(c, r) - gain(c)
+ *   delta(c, r) is exactly the change of the total cost when c replaces the medoid of rank r and everyone is reassigned.  The
+ *   iteration takes the smallest delta, ties to the lowest candidate index, then to the lowest rank.  If it is < 0 (strictly),
+ *   medoids[r] = c -- the rank is kept, so medoids[r] descends from init[r] by exchanges --, n_swaps is incremented and the state
+ *   is recomputed; otherwise the walk stops with status = 0.  With no candidate (K == the number of eligible conformers): status
+ *   0 with 0 swaps.  After max_swaps swaps, with a negative delta possibly left and not looked for: status = 1 (so max_swaps = 0
+ *   returns the seeds' assignment with status 1).  The cost falls strictly with every swap, so the walk cannot cycle.  The rule
+ *   is memoryless: calling again with the returned medoids as init and the same anchor continues the same walk bit for bit.
+ * Outputs of both, agdiff_kmedoids', every entry written in every case: medoids [K], labels [G], near [G], size [K], within
+ * [K], cost [1]; n_swaps [1] in n_iter's place; status [1].  labels and near are always the assignment to the returned medoids.
+ * On status = 2 the fill is agdiff_kmedoids'.
+ * work: caller-provided scratch of AGDIFF_PAM_WORK_BYTES, 8-byte aligned; its contents are ignored on entry and unspecified on
+ * return.  `dist` needs 4-byte alignment only, and any G, odd ones included.
+ * A swap iteration is three launches -- the state (agdiff_kmedoids' assign keeping the second-best too), the candidates (row c
+ * is streamed once: the gain in registers, corr in K uint64 bins in LDS, one row per wave for K <= 1024 and one per workgroup
+ * above, as agdiff_silhouette; then the arg-min over the bins, one record per candidate), the choose (one workgroup: the arg-min
+ * of the records, applied or not) -- and the call enqueues them for max_swaps iterations, plus the seed check, the final state
+ * and the sums.  BUILD is the candidates' launch without bins and a pick per rank: 2 K + 3 launches.  Every launch of a loop reads
+ * a device-side `done` flag first and returns at once when it is set.  No cooperative launch, no workgroup waits on another, no
+ * atomics on global memory; every loop is counted; deterministic bit for bit.
+ * A null pointer or G < 0: AGDIFF_ERR_ARG; for G > 0, K outside [1, G] or max_swaps outside [0, AGDIFF_PAM_MAX_SWAPS]:
+ * AGDIFF_ERR_ARG; `work` not 8-byte aligned: AGDIFF_ERR_ARG; G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT (the argument errors
+ * come first); G == 0: n_swaps = 0, status = 0, cost = 0 and no launch.
+ * Not built: FasterPAM's eager variant (several swaps per pass), CLARA / CLARANS sampling, k-means++ / LAB seeding.  Agreement
+ * with any other package's PAM is by the definition only. */
+int agdiff_pam_build(const float* dist, int32_t G, int32_t K, int32_t anchor,
+                     int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within,
+                     double* cost, int32_t* n_swaps, int32_t* status, uint64_t* work, void* stream);
+int agdiff_pam_swap(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t anchor, int32_t max_swaps,
+                    int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within,
+                    double* cost, int32_t* n_swaps, int32_t* status, uint64_t* work, void* stream);
 
 /* How good is a clustering, and how many families are there: the silhouette coefficient (Rousseeuw 1987) of every conformer of
  * a GIVEN clustering over the same FLOAT matrix, dist [G][G] fp32, contiguous, made exact the way agdiff_kmedoids is: all sums
