@@ -646,9 +646,7 @@ __global__ void __launch_bounds__(AG_MAXMIN_THREADS) k_maxmin_pick(const float* 
 // iteration is parallel inside, so it is a SEQUENCE OF LAUNCHES, and the kernel boundary is the only grid-wide ordering there is:
 //   k_kmed_init     one workgroup: checks the seeds (range, duplicates by LDS counters, eligibility), sets up the control words;
 //                   on a bad seed it writes the status-2 fill and sets `done`, so nothing after it does anything
-//   k_kmed_assign   64 columns per workgroup, its 4 waves take the ranks r = w, w + 4, ... of the K medoid rows (coalesced 4-byte
-//                   loads, unrolled); the keys (Q + 1) << 12 | r -- 0 << 12 | r for the medoid's own column -- are min-reduced
-//                   through LDS: lowest Q, then lowest rank.  Writes labels and near.
+//   k_kmed_assign   the column pass (ag_kmed_columns<false>, below) under the anchor init[0]: writes labels and near
 //   k_kmed_costs    one wave per candidate row i: sum of Q(dist[i][j]) over the members j != i of i's cluster, uint64 partials
 //                   reduced by shuffles; writes the key cost << 12 | i (all ones for an ineligible row)
 //   k_kmed_choose   one workgroup (G keys, nothing to stream): per-cluster arg-min by LDS atomic min on the keys, the incumbent
@@ -671,11 +669,6 @@ __device__ __forceinline__ uint64_t ag_kmed_q(float x) {
   const double s = __builtin_fma((double)x, 268435456.0, 4503599627370496.0);
   const uint64_t q = (uint64_t)__double_as_longlong(s) & ((1ull << 52) - 1);
   return ag_kmed_valid(x) ? q : (1ull << 40);
-}
-
-__device__ __forceinline__ uint64_t ag_shfl_xor_u64(uint64_t k, int o) {
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)k, o);
-  return ((uint64_t)hi << 32) | lo;
 }
 
 // the status-2 fill of agdiff_kmedoids, agdiff_pam_build and agdiff_pam_swap, by one workgroup of 1024 threads: every output is
@@ -728,39 +721,70 @@ __global__ void __launch_bounds__(1024) k_kmed_init(const float* __restrict__ di
   ag_kmed_check_seeds(dist, G, K, init, init[0], 0, medoids, labels, near, size, within, cost, n_iter, status, ctl);
 }
 
+// k joins the running (best key, second-best Q + 1) of one column; ~0 is "none" in both places.  Keys differ in their rank bits.
+__device__ __forceinline__ void ag_kmed_push(uint64_t& k1, uint64_t& s2, uint64_t k) {
+  const bool lower = k < k1;
+  const uint64_t loser = lower ? k1 : k;
+  k1 = lower ? k : k1;
+  const uint64_t ls = loser == ~0ull ? ~0ull : loser >> 12;
+  s2 = ls < s2 ? ls : s2;
+}
+
+// THE COLUMN PASS, the body of k_kmed_assign (SECOND = false) and k_pam_state (SECOND = true), by a workgroup of 256 threads: 64
+// columns, its 4 waves take the ranks r = w, w + 4, ... of the K medoid rows (coalesced 4-byte loads, unrolled); the keys
+// (Q + 1) << 12 | r -- 0 << 12 | r for the medoid's own column -- are min-reduced through LDS: lowest Q, then lowest rank.  Row
+// `anchor` decides who is eligible.  Writes labels and near; with SECOND the second-best Q + 1 is kept beside the best key, and
+// dn, ds (all ones: none) and tag = -1 (ineligible) or n << 1 | is-a-medoid are written too.  Without it `sec` is never stored,
+// so nothing of it is left in the code.
+template <bool SECOND>
+__device__ __forceinline__ void ag_kmed_columns(const float* __restrict__ dist, int G, int K, int anchor,
+                                                const int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                float* __restrict__ near, uint64_t* __restrict__ dn, uint64_t* __restrict__ ds,
+                                                int32_t* __restrict__ tag) {
+  __shared__ uint64_t s_key[SECOND ? 2 : 1][4][64];     // the best keys, then the seconds
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + lane;
+  const bool in = j < G;
+  const int jc = in ? j : G - 1;                    // (a column past the end reads the last one and writes nothing)
+  uint64_t key = ~0ull, sec = ~0ull;
+#pragma unroll 4
+  for (int r = wv; r < K; r += 4) {
+    const int m = medoids[r];                       // (wave-uniform)
+    const float x = dist[(size_t)m * (size_t)G + jc];
+    ag_kmed_push(key, sec, (m == jc ? 0ull : (ag_kmed_q(x) + 1) << 12) | (uint64_t)r);
+  }
+  s_key[0][wv][lane] = key;
+  if (SECOND) s_key[1][wv][lane] = sec;
+  __syncthreads();
+  if (wv != 0 || !in) return;
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    ag_kmed_push(key, sec, s_key[0][w][lane]);
+    if (SECOND) {
+      const uint64_t s = s_key[1][w][lane];
+      sec = s < sec ? s : sec;
+    }
+  }
+  const bool eligible = j == anchor || ag_kmed_valid(dist[(size_t)anchor * (size_t)G + j]);
+  const int r = (int)(key & 4095);
+  const int m = medoids[r];
+  const float x = dist[(size_t)m * (size_t)G + j];
+  labels[j] = eligible ? r : -1;
+  near[j] = !eligible ? __builtin_nanf("") : ((key >> 12) == 0 || x == 0.0f ? 0.0f : x);     // (-0 is written as +0)
+  if (SECOND) {
+    tag[j] = eligible ? (r << 1) | (m == j ? 1 : 0) : -1;
+    dn[j] = (key >> 12) == 0 ? 0ull : (key >> 12) - 1;
+    ds[j] = sec == ~0ull ? ~0ull : sec - 1;         // (K == 1: no other rank, min(ds, x) = x)
+  }
+}
+
 // final = 0: an assign of the loop, skipped once `done` is set.  final = 1: the assign after the last update, which runs only
 // after a status-1 stop (after a status-0 stop the labels already belong to the returned medoids).
 __global__ void __launch_bounds__(256) k_kmed_assign(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ init,
                                                      const int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
                                                      float* __restrict__ near, const int32_t* __restrict__ ctl, int final) {
   if (final ? ctl[KM_STATUS] != 1 : ctl[KM_DONE] != 0) return;
-  __shared__ uint64_t s_key[4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + lane;
-  const bool in = j < G;
-  const int jc = in ? j : G - 1;                    // (a column past the end reads the last one and writes nothing)
-  uint64_t key = ~0ull;
-#pragma unroll 4
-  for (int r = wv; r < K; r += 4) {
-    const int m = medoids[r];                       // (wave-uniform)
-    const float x = dist[(size_t)m * (size_t)G + jc];
-    const uint64_t k = (m == jc ? 0ull : (ag_kmed_q(x) + 1) << 12) | (uint64_t)r;
-    key = k < key ? k : key;
-  }
-  s_key[wv][lane] = key;
-  __syncthreads();
-  if (wv != 0 || !in) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const uint64_t k = s_key[w][lane];
-    key = k < key ? k : key;
-  }
-  const int s0 = init[0];
-  const bool eligible = j == s0 || ag_kmed_valid(dist[(size_t)s0 * (size_t)G + j]);
-  const int r = (int)(key & 4095);
-  const float x = dist[(size_t)medoids[r] * (size_t)G + j];
-  labels[j] = eligible ? r : -1;
-  near[j] = !eligible ? __builtin_nanf("") : ((key >> 12) == 0 || x == 0.0f ? 0.0f : x);     // (-0 is written as +0)
+  ag_kmed_columns<false>(dist, G, K, init[0], medoids, labels, near, nullptr, nullptr, nullptr);
 }
 
 __global__ void __launch_bounds__(256) k_kmed_costs(const float* __restrict__ dist, int G, const int32_t* __restrict__ labels,
@@ -782,8 +806,7 @@ __global__ void __launch_bounds__(256) k_kmed_costs(const float* __restrict__ di
     const int l = labels[j];
     sum += (l == c && j != i) ? ag_kmed_q(x) : 0ull;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += ag_shfl_xor_u64(sum, o);
+  ag_wave_sum(sum);
   if (lane == 0) keys[i] = (sum << 12) | (uint64_t)i;
 }
 
@@ -838,8 +861,7 @@ __global__ void __launch_bounds__(1024) k_kmed_finish(int G, int K, const int32_
       total += q;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) total += ag_shfl_xor_u64(total, o);
+  ag_wave_sum(total);
   if (lane == 0) s_part[wv] = total;
   __syncthreads();
   for (int r = t; r < K; r += 1024) {
@@ -855,26 +877,75 @@ __global__ void __launch_bounds__(1024) k_kmed_finish(int G, int K, const int32_
   }
 }
 
+// THE ROW PASS, the scaffold of k_sil_rows and k_pam_rows, by a workgroup of 256 threads: row i of the matrix is streamed once with
+// coalesced 4-byte loads and integer terms of its entries are added into K uint64 bins in LDS, one per rank (LDS 64-bit integer
+// add, as k_kmed_finish); then the row's threads stride over the bins and min-reduce (value, rank) pairs under the total order
+// "lowest value, then lowest rank".  What is added and what the pairs hold is the kernel's own; who shares a row, where its bins
+// are, their zeroing and the reduction are here.  Two shapes, chosen by K (ag_row_pass_launch, below) so that the bins of a
+// workgroup take at most 32 KB of LDS (AG_ROW_BIN_BYTES):
+//   K <= AG_ROW_WAVE_MAX_K (1024)   ROWS = 4: one row per WAVE, four rows and 4 K bins per workgroup
+//   K >  AG_ROW_WAVE_MAX_K          ROWS = 1: one row per WORKGROUP of four waves, K bins (K <= 4096)
+#define AG_ROW_WAVE_MAX_K 1024
+enum { AG_ROW_BIN_BYTES = 32768 };                // the most LDS a workgroup's bins take, in either shape
+static_assert(4 * AG_ROW_WAVE_MAX_K * 8 <= AG_ROW_BIN_BYTES && AGDIFF_PRUNE_MAX_CONFS * 8 <= AG_ROW_BIN_BYTES, "the row pass: the bins of either shape fit their LDS");
+
+// the smaller of two (value, index) pairs: lowest value, then lowest index.  The values are never NaN.
+template <typename V>
+__device__ __forceinline__ void ag_min_pair(V& v, int& c, V ov, int oc) {
+  const bool take = ov < v || (ov == v && oc < c);
+  v = take ? ov : v;
+  c = take ? oc : c;
+}
+
+// the smallest pair of the WAVES waves of the workgroup, in every thread: a wave xor-butterfly, then (WAVES > 1) the waves'
+// partials through LDS, which every wave of the workgroup has to reach.  The slots are the helper's own and nothing orders
+// their reads before a later write: one call per instantiation and kernel, or a barrier between two.
+template <int WAVES, typename V>
+__device__ __forceinline__ void ag_min_pair_over(V& v, int& c) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ag_min_pair(v, c, __shfl_xor(v, o), __shfl_xor(c, o));
+  if constexpr (WAVES > 1) {
+    __shared__ V s_v[WAVES];
+    __shared__ int s_c[WAVES];
+    if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = v; s_c[threadIdx.x >> 6] = c; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) ag_min_pair(v, c, s_v[w], s_c[w]);
+  }
+}
+
+template <int ROWS>
+struct ag_row_pass {
+  static_assert(ROWS == 1 || ROWS == 4, "one row per workgroup or one per wave");
+  static constexpr int NT = ROWS == 4 ? 64 : 256;   // the threads that share a row
+  int tid;                                          // this thread among them
+  int i;                                            // the row (wave-uniform; may be >= G: every wave reaches every barrier)
+  unsigned long long* bins;                         // the row's K bins, of s_bins [ROWS][K]
+  __device__ __forceinline__ ag_row_pass(unsigned long long* s_bins, int K) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    tid = ROWS == 4 ? lane : (int)threadIdx.x;
+    i = ROWS == 4 ? blockIdx.x * 4 + wv : (int)blockIdx.x;
+    bins = s_bins + (ROWS == 4 ? (size_t)wv * (size_t)K : 0);
+  }
+  __device__ __forceinline__ void zero_bins(int K) const {
+    for (int c = tid; c < K; c += NT) bins[c] = 0ull;
+    __syncthreads();
+  }
+  template <typename V>
+  __device__ __forceinline__ void min_pair(V& v, int& c) const { ag_min_pair_over<ROWS == 4 ? 1 : 4>(v, c); }
+};
+
 // Silhouette coefficients of a given clustering over the same float matrix (the rule: include/agdiff_hip.h, agdiff_silhouette).
 // Three launches, the kernel boundary again the only grid-wide ordering:
 //   k_sil_init     one workgroup: checks the labels (-1 or a rank in [0, K)), counts the members of every rank with LDS integer
 //                  atomics and writes `size` and the control words; on a bad label it writes the status-2 fill and sets `done`
-//   k_sil_rows     row i is streamed once with coalesced 4-byte loads and Q of its entries is added into K uint64 bins in LDS, one
-//                  per rank (LDS 64-bit integer add, as k_kmed_finish); then the lanes stride over the bins, make the means
-//                  m_c = S_c / size[c] and min-reduce the pairs (m_c, c) under the total order "lowest mean, then lowest rank";
-//                  one lane writes a, b, s, other and T(i) = rint(s 2^40) into `work`.  Two shapes, chosen by K so that the bins
-//                  of a workgroup take at most 32 KB of LDS (SIL_BIN_BYTES):
-//                    K <= AG_SIL_WAVE_ROW_MAX_K (1024)   ROWS = 4: one row per WAVE, four rows and 4 K bins per workgroup
-//                    K >  AG_SIL_WAVE_ROW_MAX_K          ROWS = 1: one row per WORKGROUP of four waves, K bins (K <= 4096)
+//   k_sil_rows     the row pass: Q of row i's entries goes into the bin of the entry's rank; the pairs are (m_c, c), the means
+//                  m_c = S_c / size[c]; one lane writes a, b, s, other and T(i) = rint(s 2^40) into `work`
 //   k_sil_finish   one workgroup: per-rank and total sums of T (int64, as uint64 LDS adds), the divisions, status
-// The state between launches lives in `size` and in `work`: 8 control words, then T [G].  Sums are on integers; the only
-// floating-point values that cross lanes are the means of the (mean, rank) pairs, compared and never added; LDS atomics are adds
-// on integers, there are no global atomics and no workgroup waits on another.  Every loop is counted.
-#define AG_SIL_WAVE_ROW_MAX_K 1024
-enum { SIL_DONE = 0, SIL_STATUS = 1, SIL_CTL_WORDS = 8 };     // int32 words at the head of `work`
-enum { SIL_BIN_BYTES = 32768 };                               // the most LDS a workgroup's bins take, in either shape
-static_assert(AGDIFF_SILHOUETTE_WORK_BYTES >= SIL_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * 8, "agdiff_silhouette: control words + one T per conformer");
-static_assert(4 * AG_SIL_WAVE_ROW_MAX_K * 8 <= SIL_BIN_BYTES && AGDIFF_PRUNE_MAX_CONFS * 8 <= SIL_BIN_BYTES, "agdiff_silhouette: the bins of either shape fit their LDS");
+// The state between launches lives in `size` and in `work`: the 8 control words (KM_DONE, KM_STATUS), then T [G].  Sums are on
+// integers; the only floating-point values that cross lanes are the means of the (mean, rank) pairs, compared and never added;
+// LDS atomics are adds on integers, there are no global atomics and no workgroup waits on another.  Every loop is counted.
+static_assert(AGDIFF_SILHOUETTE_WORK_BYTES >= KM_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * 8, "agdiff_silhouette: control words + one T per conformer");
 static_assert(AGDIFF_PRUNE_MAX_CONFS == 1 << 12 && AGDIFF_KMEDOIDS_MAX_DIST == 4096, "agdiff_silhouette: a row's sum of 4096 terms <= 2^40 and a sum of 4096 |T| <= 2^40 stay <= 2^52");
 
 __global__ void __launch_bounds__(1024) k_sil_init(int G, int K, const int32_t* __restrict__ labels, double* __restrict__ a,
@@ -895,42 +966,30 @@ __global__ void __launch_bounds__(1024) k_sil_init(int G, int K, const int32_t* 
   bad = __syncthreads_or(bad);
   if (!bad) {
     for (int r = t; r < K; r += 1024) size[r] = s_size[r];
-    if (t < SIL_CTL_WORDS) ctl[t] = 0;
+    if (t < KM_CTL_WORDS) ctl[t] = 0;
     return;
   }
   const double nan = __builtin_nan("");
   for (int j = t; j < G; j += 1024) { a[j] = nan; b[j] = nan; s[j] = nan; other[j] = -1; }
   for (int r = t; r < K; r += 1024) { size[r] = 0; cluster_mean[r] = nan; }
-  if (t < SIL_CTL_WORDS) ctl[t] = t == SIL_DONE ? 1 : (t == SIL_STATUS ? 2 : 0);
+  if (t < KM_CTL_WORDS) ctl[t] = t == KM_DONE ? 1 : (t == KM_STATUS ? 2 : 0);
   if (t == 0) { mean[0] = nan; status[0] = 2; }
 }
 
-// the smaller of two (mean, rank) pairs: lowest mean, then lowest rank.  The means are never NaN; "none" is (+inf, INT_MAX).
-__device__ __forceinline__ void ag_sil_min_pair(double& m, int& c, double om, int oc) {
-  const bool take = om < m || (om == m && oc < c);
-  m = take ? om : m;
-  c = take ? oc : c;
-}
-
+// the pairs are (mean, rank); "none" is (+inf, INT_MAX)
 template <int ROWS>
 __global__ void __launch_bounds__(256) k_sil_rows(const float* __restrict__ dist, int G, int K, const int32_t* __restrict__ labels,
                                                   const int32_t* __restrict__ size, double* __restrict__ a, double* __restrict__ b,
                                                   double* __restrict__ s, int32_t* __restrict__ other, int64_t* __restrict__ T,
                                                   const int32_t* __restrict__ ctl) {
-  static_assert(ROWS == 1 || ROWS == 4, "one row per workgroup or one per wave");
-  if (ctl[SIL_DONE] != 0) return;                   // (grid-uniform: a bad label, k_sil_init wrote everything)
+  if (ctl[KM_DONE] != 0) return;                    // (grid-uniform: a bad label, k_sil_init wrote everything)
   extern __shared__ unsigned long long s_bins[];    // [ROWS][K]
-  __shared__ double s_pm[4];
-  __shared__ int s_pc[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int NT = ROWS == 4 ? 64 : 256;              // the threads that share a row
-  const int tid = ROWS == 4 ? lane : (int)threadIdx.x;
-  const int i = ROWS == 4 ? blockIdx.x * 4 + wv : (int)blockIdx.x;     // (wave-uniform; every wave reaches every barrier)
-  unsigned long long* __restrict__ bins = s_bins + (ROWS == 4 ? (size_t)wv * (size_t)K : 0);
+  const ag_row_pass<ROWS> rp(s_bins, K);
+  const int NT = rp.NT, tid = rp.tid, i = rp.i;
+  unsigned long long* __restrict__ bins = rp.bins;
   const int own = i < G ? labels[i] : -1;
   const bool member = own >= 0;
-  for (int c = tid; c < K; c += NT) bins[c] = 0ull;
-  __syncthreads();
+  rp.zero_bins(K);
   if (member) {
     const float* __restrict__ row = dist + (size_t)i * (size_t)G;
 #pragma unroll 4
@@ -946,17 +1005,10 @@ __global__ void __launch_bounds__(256) k_sil_rows(const float* __restrict__ dist
     for (int c = tid; c < K; c += NT) {             // (ascending c: a later equal mean does not replace an earlier one)
       const int n = size[c];
       if (c == own || n == 0) continue;
-      ag_sil_min_pair(bm, bc, (double)bins[c] / (double)n, c);
+      ag_min_pair(bm, bc, (double)bins[c] / (double)n, c);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ag_sil_min_pair(bm, bc, __shfl_xor(bm, o), __shfl_xor(bc, o));
-  if (ROWS == 1) {
-    if (lane == 0) { s_pm[wv] = bm; s_pc[wv] = bc; }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < 4; ++w) ag_sil_min_pair(bm, bc, s_pm[w], s_pc[w]);
-  }
+  rp.min_pair(bm, bc);
   if (tid != 0 || i >= G) return;
   if (!member) {                                    // left out
     a[i] = b[i] = s[i] = __builtin_nan("");
@@ -981,7 +1033,7 @@ __global__ void __launch_bounds__(1024) k_sil_finish(int G, int K, const int32_t
                                                      const int32_t* __restrict__ size, double* __restrict__ cluster_mean,
                                                      double* __restrict__ mean, int32_t* __restrict__ status,
                                                      const int32_t* __restrict__ ctl) {
-  if (ctl[SIL_STATUS] == 2) return;                 // a bad label: k_sil_init wrote everything
+  if (ctl[KM_STATUS] == 2) return;                  // a bad label: k_sil_init wrote everything
   __shared__ unsigned long long s_sum[AGDIFF_PRUNE_MAX_CONFS];
   __shared__ unsigned long long s_part[16];
   __shared__ int s_cnt[16];
@@ -999,8 +1051,7 @@ __global__ void __launch_bounds__(1024) k_sil_finish(int G, int K, const int32_t
       ++members;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { total += ag_shfl_xor_u64(total, o); members += __shfl_xor(members, o); }
+  ag_wave_sum(total, members);
   if (lane == 0) { s_part[wv] = total; s_cnt[wv] = members; }
   __syncthreads();
   for (int r = t; r < K; r += 1024) {
@@ -1021,16 +1072,13 @@ __global__ void __launch_bounds__(1024) k_sil_finish(int G, int K, const int32_t
 //   k_pam_swap_init   one workgroup: agdiff_kmedoids' seed check under the explicit anchor (ag_kmed_check_seeds)
 //   k_pam_build_init  one workgroup: the anchor, the eligible count against K, tag and dn = 2^40 ("no medoid yet": with it rank 0
 //                     is the same arg-max of the gain as every later rank)
-//   k_pam_state       k_kmed_assign's shape (64 columns per workgroup, its 4 waves over the ranks), keeping the best key AND the
-//                     second-best Q + 1: writes labels and near, and into `work` dn, ds (all ones: none) and
-//                     tag = -1 (ineligible) or n << 1 | is-a-medoid
-//   k_pam_rows        k_sil_rows' shape: candidate row c is streamed once with coalesced 4-byte loads; gain(c) is summed in
-//                     registers and reduced by shuffles; with BINS the terms of corr(c, r) go into K uint64 bins in LDS (one row
-//                     per wave up to K = 1024, one per workgroup above: <= 32 KB), then the lanes stride over the bins and
-//                     min-reduce the pairs (delta, rank).  One record per row: recD = delta (BUILD: -gain), recR = the rank;
-//                     INT64_MAX for a row that is no candidate.
-//   k_pam_choose      one workgroup over the G records (ag_pam_best: lowest recD, then lowest index): a negative delta is applied
-//                     and counted, anything else ends the walk with status 0
+//   k_pam_state       the column pass keeping the second best (ag_kmed_columns<true>): labels and near, and into `work` dn, ds
+//                     and tag
+//   k_pam_rows        the row pass over candidate row c: gain(c) is summed in registers and reduced by shuffles; with BINS the
+//                     terms of corr(c, r) go into the bin of rank r and the pairs are (delta, rank).  One record per row:
+//                     recD = delta (BUILD, without bins: -gain), recR = the rank; INT64_MAX for a row that is no candidate.
+//   k_pam_choose      one workgroup over the G records (ag_pam_best: lowest recD, then lowest index, by the row pass's
+//                     ag_min_pair_over): a negative delta is applied and counted, anything else ends the walk with status 0
 //   k_pam_build_pick  one workgroup: the same arg-min, then medoids[p], tag and dn = min(dn, Q(row c)) along the picked row
 //   k_kmed_finish     size, within, cost, n_swaps, status: as it is, from the same control words
 // `work`: 8 control words (KM_DONE, KM_STATUS, KM_ITERS = the swaps made), then dn, ds, recD (64-bit each), tag, recR (32-bit
@@ -1078,15 +1126,6 @@ __global__ void __launch_bounds__(1024) k_pam_build_init(const float* __restrict
   ag_kmed_fill_bad(G, K, medoids, labels, near, size, within, cost, n_swaps, status, ctl);
 }
 
-// k joins the running (best key, second-best Q + 1) of one column; ~0 is "none" in both places.  Keys differ in their rank bits.
-__device__ __forceinline__ void ag_pam_push(uint64_t& k1, uint64_t& s2, uint64_t k) {
-  const bool lower = k < k1;
-  const uint64_t loser = lower ? k1 : k;
-  k1 = lower ? k : k1;
-  const uint64_t ls = loser == ~0ull ? ~0ull : loser >> 12;
-  s2 = ls < s2 ? ls : s2;
-}
-
 // final = 0: a state of the loop (or BUILD's one), skipped once `done` is set.  final = 1: the state after the last swap, which
 // runs only after a status-1 stop (after a status-0 stop the labels already belong to the returned medoids).
 __global__ void __launch_bounds__(256) k_pam_state(const float* __restrict__ dist, int G, int K, int anchor,
@@ -1094,44 +1133,7 @@ __global__ void __launch_bounds__(256) k_pam_state(const float* __restrict__ dis
                                                    float* __restrict__ near, const int32_t* __restrict__ ctl, uint64_t* __restrict__ dn,
                                                    uint64_t* __restrict__ ds, int32_t* __restrict__ tag, int final) {
   if (final ? ctl[KM_STATUS] != 1 : ctl[KM_DONE] != 0) return;
-  __shared__ uint64_t s_key[4][64], s_sec[4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int j = blockIdx.x * 64 + lane;
-  const bool in = j < G;
-  const int jc = in ? j : G - 1;                    // (a column past the end reads the last one and writes nothing)
-  uint64_t key = ~0ull, sec = ~0ull;
-#pragma unroll 4
-  for (int r = wv; r < K; r += 4) {
-    const int m = medoids[r];                       // (wave-uniform)
-    const float x = dist[(size_t)m * (size_t)G + jc];
-    ag_pam_push(key, sec, (m == jc ? 0ull : (ag_kmed_q(x) + 1) << 12) | (uint64_t)r);
-  }
-  s_key[wv][lane] = key;
-  s_sec[wv][lane] = sec;
-  __syncthreads();
-  if (wv != 0 || !in) return;
-#pragma unroll
-  for (int w = 1; w < 4; ++w) {
-    const uint64_t s = s_sec[w][lane];
-    ag_pam_push(key, sec, s_key[w][lane]);
-    sec = s < sec ? s : sec;
-  }
-  const bool eligible = j == anchor || ag_kmed_valid(dist[(size_t)anchor * (size_t)G + j]);
-  const int r = (int)(key & 4095);
-  const int m = medoids[r];
-  const float x = dist[(size_t)m * (size_t)G + j];
-  labels[j] = eligible ? r : -1;
-  near[j] = !eligible ? __builtin_nanf("") : ((key >> 12) == 0 || x == 0.0f ? 0.0f : x);     // (-0 is written as +0)
-  tag[j] = eligible ? (r << 1) | (m == j ? 1 : 0) : -1;
-  dn[j] = (key >> 12) == 0 ? 0ull : (key >> 12) - 1;
-  ds[j] = sec == ~0ull ? ~0ull : sec - 1;           // (K == 1: no other rank, min(ds, x) = x)
-}
-
-// the smaller of two (delta, index) pairs: lowest delta, then lowest index (a rank in k_pam_rows, a conformer in ag_pam_best)
-__device__ __forceinline__ void ag_pam_min_pair(int64_t& d, int& c, int64_t od, int oc) {
-  const bool take = od < d || (od == d && oc < c);
-  d = take ? od : d;
-  c = take ? oc : c;
+  ag_kmed_columns<true>(dist, G, K, anchor, medoids, labels, near, dn, ds, tag);
 }
 
 template <int ROWS, bool BINS>
@@ -1142,19 +1144,12 @@ __global__ void __launch_bounds__(256) k_pam_rows(const float* __restrict__ dist
   if (ctl[KM_DONE] != 0) return;                    // (grid-uniform)
   extern __shared__ unsigned long long s_bins[];    // [ROWS][K] with BINS
   __shared__ unsigned long long s_pg[4];
-  __shared__ long long s_pd[4];
-  __shared__ int s_pr[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int NT = ROWS == 4 ? 64 : 256;              // the threads that share a row
-  const int tid = ROWS == 4 ? lane : (int)threadIdx.x;
-  const int i = ROWS == 4 ? blockIdx.x * 4 + wv : (int)blockIdx.x;     // (wave-uniform; every wave reaches every barrier)
-  unsigned long long* __restrict__ bins = s_bins + (ROWS == 4 ? (size_t)wv * (size_t)K : 0);
+  const ag_row_pass<ROWS> rp(s_bins, K);
+  const int NT = rp.NT, tid = rp.tid, i = rp.i;
+  unsigned long long* __restrict__ bins = rp.bins;
   const int own = i < G ? tag[i] : -1;
   const bool cand = own >= 0 && (own & 1) == 0;     // eligible and not a medoid
-  if (BINS) {
-    for (int c = tid; c < K; c += NT) bins[c] = 0ull;
-    __syncthreads();
-  }
+  if (BINS) rp.zero_bins(K);
   uint64_t gain = 0;
   if (cand) {
     const float* __restrict__ row = dist + (size_t)i * (size_t)G;
@@ -1171,24 +1166,16 @@ __global__ void __launch_bounds__(256) k_pam_rows(const float* __restrict__ dist
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) gain += ag_shfl_xor_u64(gain, o);
+  ag_wave_sum(gain);
   int64_t bd = AG_PAM_NONE;
   int br = 0x7fffffff;
   if (BINS) {
-    if (ROWS == 1 && lane == 0) s_pg[wv] = gain;
+    if (ROWS == 1 && (threadIdx.x & 63) == 0) s_pg[threadIdx.x >> 6] = gain;
     __syncthreads();
     if (ROWS == 1) gain = s_pg[0] + s_pg[1] + s_pg[2] + s_pg[3];
     if (cand)
-      for (int c = tid; c < K; c += NT) ag_pam_min_pair(bd, br, (int64_t)bins[c] - (int64_t)gain, c);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ag_pam_min_pair(bd, br, (int64_t)ag_shfl_xor_u64((uint64_t)bd, o), __shfl_xor(br, o));
-    if (ROWS == 1) {
-      if (lane == 0) { s_pd[wv] = bd; s_pr[wv] = br; }
-      __syncthreads();
-#pragma unroll
-      for (int w = 0; w < 4; ++w) ag_pam_min_pair(bd, br, (int64_t)s_pd[w], s_pr[w]);
-    }
+      for (int c = tid; c < K; c += NT) ag_min_pair(bd, br, (int64_t)bins[c] - (int64_t)gain, c);
+    rp.min_pair(bd, br);
   } else if (cand) {
     bd = -(int64_t)gain;                            // BUILD: the largest gain is the lowest record
     br = 0;
@@ -1201,18 +1188,10 @@ __global__ void __launch_bounds__(256) k_pam_rows(const float* __restrict__ dist
 // the arg-min of the G records by one workgroup of 1024 threads: lowest recD, then lowest index; (AG_PAM_NONE, INT_MAX) when
 // no row is a candidate.  Block-uniform on return.
 __device__ __forceinline__ void ag_pam_best(int G, const int64_t* __restrict__ recD, int64_t& bd, int& bj) {
-  __shared__ long long s_d[16];
-  __shared__ int s_j[16];
-  const int t = threadIdx.x;
   bd = AG_PAM_NONE;
   bj = 0x7fffffff;
-  for (int j = t; j < G; j += 1024) ag_pam_min_pair(bd, bj, recD[j], j);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ag_pam_min_pair(bd, bj, (int64_t)ag_shfl_xor_u64((uint64_t)bd, o), __shfl_xor(bj, o));
-  if ((t & 63) == 0) { s_d[t >> 6] = bd; s_j[t >> 6] = bj; }
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < 16; ++w) ag_pam_min_pair(bd, bj, (int64_t)s_d[w], s_j[w]);
+  for (int j = threadIdx.x; j < G; j += 1024) ag_min_pair(bd, bj, recD[j], j);
+  ag_min_pair_over<16>(bd, bj);
 }
 
 __global__ void __launch_bounds__(1024) k_pam_choose(int G, int max_swaps, const int64_t* __restrict__ recD,
@@ -2802,6 +2781,27 @@ __global__ void __launch_bounds__(AG_MMD_SINGLE_THREADS) k_mmd_single(const floa
 // bytes per row of a threshold bit-matrix of `columns` columns: 16-bit pieces, rounded up to 8 bytes
 static int ag_bits_pitch(int columns) { return ((columns + 15) / 16 * 2 + 7) / 8 * 8; }
 
+// The G == 0 answer of a walk, which launches nothing: every listed output set byte-wise (0: all bits clear; 0xff: NaNs) by
+// memsets on the stream.  Without a device there is nothing to write to, and that is no error.
+struct ag_fill { void* p; int byte; size_t bytes; };
+static int ag_fill_outputs(std::initializer_list<ag_fill> outs, hipStream_t st) {
+  for (const ag_fill& o : outs) {
+    const hipError_t e = hipMemsetAsync(o.p, o.byte, o.bytes, st);
+    if (e == hipSuccess) continue;
+    (void)hipGetLastError();
+    return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;
+  }
+  return AGDIFF_OK;
+}
+
+// the launch shape of a row pass with K bins per row (ag_row_pass<4> or <1>): one row per wave while the 4 K bins of a workgroup
+// fit AG_ROW_BIN_BYTES, one row per workgroup above
+struct ag_row_launch { bool wave_rows; dim3 grid; size_t lds; };
+static ag_row_launch ag_row_pass_launch(int G, int K) {
+  if (K <= AG_ROW_WAVE_MAX_K) return {true, dim3((unsigned)((G + 3) / 4)), (size_t)4 * K * 8};
+  return {false, dim3((unsigned)G), (size_t)K * 8};
+}
+
 // agdiff_rmsd_matrix (out_mirror unused) and agdiff_rmsd_matrix_hands: the shared argument checks, both centring launches and
 // the matrix kernel
 template <bool kMirror>
@@ -2879,12 +2879,7 @@ extern "C" int agdiff_butina_cluster(const uint64_t* bits, int32_t G, int32_t re
   if (!bits || !leader || !count || !rank || !n_clusters || G < 0 || (reorder != 0 && reorder != 1) || ((uintptr_t)bits & 7))
     return AGDIFF_ERR_ARG;
   if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
-  if (G == 0) {                                     // no launch: n_clusters = 0 by a memset on the stream
-    const hipError_t e = hipMemsetAsync(n_clusters, 0, sizeof(int32_t), (hipStream_t)stream);
-    if (e == hipSuccess) return AGDIFF_OK;
-    (void)hipGetLastError();
-    return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;      // (without a device there is no n_clusters to write)
-  }
+  if (G == 0) return ag_fill_outputs({{n_clusters, 0, 4}}, (hipStream_t)stream);      // no launch: n_clusters = 0
   const int words = ag_bits_pitch(G) / 8;                 // 64-bit words per row
   k_butina_cluster<<<dim3(1), dim3(AG_BUTINA_THREADS), 0, (hipStream_t)stream>>>(bits, G, words, reorder, leader, count, rank, n_clusters);
   AG_CHECK_LAUNCH();
@@ -2896,40 +2891,38 @@ extern "C" int agdiff_maxmin_pick(const float* dist, int32_t G, int32_t K, int32
   if (!dist || !picks || !radius || !owner || !near || !n_picked || !cover || G < 0) return AGDIFF_ERR_ARG;
   if (G > 0 && (K < 1 || K > G || first < 0 || first >= G || stop != stop)) return AGDIFF_ERR_ARG;
   if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
-  if (G == 0) {                                     // no launch: n_picked = 0 and cover = 0 (all bits clear) by memsets on the stream
-    for (void* p : {(void*)n_picked, (void*)cover}) {
-      const hipError_t e = hipMemsetAsync(p, 0, 4, (hipStream_t)stream);
-      if (e == hipSuccess) continue;
-      (void)hipGetLastError();
-      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
-    }
-    return AGDIFF_OK;
-  }
+  if (G == 0) return ag_fill_outputs({{n_picked, 0, 4}, {cover, 0, 4}}, (hipStream_t)stream);      // no launch: n_picked = 0, cover = 0
   k_maxmin_pick<<<dim3(1), dim3(AG_MAXMIN_THREADS), 0, (hipStream_t)stream>>>(dist, G, K, first, stop, picks, radius, owner, near, n_picked,
                                                                             cover);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }
 
+// the argument checks and the G == 0 answer that agdiff_kmedoids, agdiff_pam_build and agdiff_pam_swap share (`rest_ok`: the
+// caller's own conditions, which count with K's when G > 0; n_steps: n_iter or n_swaps); returns AGDIFF_OK with *launch = false
+// when there is nothing to launch
+static int ag_kmed_prepare(const float* dist, int32_t G, int32_t K, bool rest_ok, int32_t* medoids, int32_t* labels, float* near,
+                           int32_t* size, double* within, double* cost, int32_t* n_steps, int32_t* status, uint64_t* work,
+                           hipStream_t st, bool* launch) {
+  *launch = false;
+  if (!dist || !medoids || !labels || !near || !size || !within || !cost || !n_steps || !status || !work || G < 0) return AGDIFF_ERR_ARG;
+  if (G > 0 && (K < 1 || K > G || !rest_ok)) return AGDIFF_ERR_ARG;
+  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  if (G == 0) return ag_fill_outputs({{n_steps, 0, 4}, {status, 0, 4}, {cost, 0, 8}}, st);      // n_steps = 0, status = 0, cost = 0
+  *launch = true;
+  return AGDIFF_OK;
+}
+
 extern "C" int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const int32_t* init, int32_t max_iter, int32_t* medoids,
                                int32_t* labels, float* near, int32_t* size, double* within, double* cost, int32_t* n_iter,
                                int32_t* status, uint64_t* work, void* stream) {
-  if (!dist || !init || !medoids || !labels || !near || !size || !within || !cost || !n_iter || !status || !work || G < 0)
-    return AGDIFF_ERR_ARG;
-  if (G > 0 && (K < 1 || K > G || max_iter < 1 || max_iter > AGDIFF_KMEDOIDS_MAX_ITER)) return AGDIFF_ERR_ARG;
-  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
-  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
   hipStream_t st = (hipStream_t)stream;
-  if (G == 0) {                                     // no launch: n_iter = 0, status = 0 and cost = 0 (all bits clear) by memsets on the stream
-    const std::pair<void*, size_t> outs[] = {{n_iter, 4}, {status, 4}, {cost, 8}};
-    for (const auto& o : outs) {
-      const hipError_t e = hipMemsetAsync(o.first, 0, o.second, st);
-      if (e == hipSuccess) continue;
-      (void)hipGetLastError();
-      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
-    }
-    return AGDIFF_OK;
-  }
+  bool launch;
+  if (!init) return AGDIFF_ERR_ARG;
+  const int rc = ag_kmed_prepare(dist, G, K, max_iter >= 1 && max_iter <= AGDIFF_KMEDOIDS_MAX_ITER, medoids, labels, near, size, within,
+                                 cost, n_iter, status, work, st, &launch);
+  if (!launch) return rc;
   int32_t* ctl = (int32_t*)work;
   uint64_t* keys = work + KM_CTL_WORDS * 4 / 8;
   const dim3 cols((unsigned)((G + 63) / 64)), rows((unsigned)((G + 3) / 4));
@@ -2950,45 +2943,23 @@ extern "C" int agdiff_kmedoids(const float* dist, int32_t G, int32_t K, const in
   return AGDIFF_OK;
 }
 
-// the argument checks, the G == 0 memsets and the carving of `work` that agdiff_pam_build and agdiff_pam_swap share; returns
-// AGDIFF_OK with *launch = false when there is nothing to launch
-struct ag_pam_work { int32_t* ctl; uint64_t *dn, *ds; int64_t* recD; int32_t *tag, *recR; };
-static int ag_pam_prepare(const float* dist, int32_t G, int32_t K, bool rest_ok, int32_t* medoids, int32_t* labels, float* near,
-                          int32_t* size, double* within, double* cost, int32_t* n_swaps, int32_t* status, uint64_t* work,
-                          hipStream_t st, ag_pam_work* w, bool* launch) {
-  *launch = false;
-  if (!dist || !medoids || !labels || !near || !size || !within || !cost || !n_swaps || !status || !work || G < 0) return AGDIFF_ERR_ARG;
-  if (G > 0 && (K < 1 || K > G || !rest_ok)) return AGDIFF_ERR_ARG;
-  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
-  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
-  if (G == 0) {                                     // no launch: n_swaps = 0, status = 0 and cost = 0 (all bits clear) by memsets on the stream
-    const std::pair<void*, size_t> outs[] = {{n_swaps, 4}, {status, 4}, {cost, 8}};
-    for (const auto& o : outs) {
-      const hipError_t e = hipMemsetAsync(o.first, 0, o.second, st);
-      if (e == hipSuccess) continue;
-      (void)hipGetLastError();
-      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
-    }
-    return AGDIFF_OK;
-  }
-  w->ctl = (int32_t*)work;
-  w->dn = work + KM_CTL_WORDS * 4 / 8;
-  w->ds = w->dn + AGDIFF_PRUNE_MAX_CONFS;
-  w->recD = (int64_t*)(w->ds + AGDIFF_PRUNE_MAX_CONFS);
-  w->tag = (int32_t*)(w->recD + AGDIFF_PRUNE_MAX_CONFS);
-  w->recR = w->tag + AGDIFF_PRUNE_MAX_CONFS;
-  *launch = true;
-  return AGDIFF_OK;
-}
+// agdiff_pam_build's and agdiff_pam_swap's carving of `work`
+struct ag_pam_work {
+  int32_t* ctl; uint64_t *dn, *ds; int64_t* recD; int32_t *tag, *recR;
+  explicit ag_pam_work(uint64_t* work)
+      : ctl((int32_t*)work), dn(work + KM_CTL_WORDS * 4 / 8), ds(dn + AGDIFF_PRUNE_MAX_CONFS),
+        recD((int64_t*)(ds + AGDIFF_PRUNE_MAX_CONFS)), tag((int32_t*)(recD + AGDIFF_PRUNE_MAX_CONFS)),
+        recR(tag + AGDIFF_PRUNE_MAX_CONFS) {}
+};
 
 extern "C" int agdiff_pam_build(const float* dist, int32_t G, int32_t K, int32_t anchor, int32_t* medoids, int32_t* labels, float* near,
                                 int32_t* size, double* within, double* cost, int32_t* n_swaps, int32_t* status, uint64_t* work,
                                 void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  ag_pam_work w;
   bool launch;
-  const int rc = ag_pam_prepare(dist, G, K, true, medoids, labels, near, size, within, cost, n_swaps, status, work, st, &w, &launch);
+  const int rc = ag_kmed_prepare(dist, G, K, true, medoids, labels, near, size, within, cost, n_swaps, status, work, st, &launch);
   if (!launch) return rc;
+  const ag_pam_work w(work);
   const dim3 cols((unsigned)((G + 63) / 64)), rows((unsigned)((G + 3) / 4));
   k_pam_build_init<<<dim3(1), dim3(1024), 0, st>>>(dist, G, K, anchor, medoids, labels, near, size, within, cost, n_swaps, status, w.ctl,
                                                    w.dn, w.tag);
@@ -3010,23 +2981,22 @@ extern "C" int agdiff_pam_swap(const float* dist, int32_t G, int32_t K, const in
                                int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within, double* cost,
                                int32_t* n_swaps, int32_t* status, uint64_t* work, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  ag_pam_work w;
   bool launch;
   if (!init) return AGDIFF_ERR_ARG;
-  const int rc = ag_pam_prepare(dist, G, K, max_swaps >= 0 && max_swaps <= AGDIFF_PAM_MAX_SWAPS, medoids, labels, near, size, within,
-                                cost, n_swaps, status, work, st, &w, &launch);
+  const int rc = ag_kmed_prepare(dist, G, K, max_swaps >= 0 && max_swaps <= AGDIFF_PAM_MAX_SWAPS, medoids, labels, near, size, within,
+                                 cost, n_swaps, status, work, st, &launch);
   if (!launch) return rc;
-  const dim3 cols((unsigned)((G + 63) / 64)), rows((unsigned)((G + 3) / 4));
+  const ag_pam_work w(work);
+  const dim3 cols((unsigned)((G + 63) / 64));
+  const ag_row_launch rows = ag_row_pass_launch(G, K);
+  const auto k_rows = rows.wave_rows ? k_pam_rows<4, true> : k_pam_rows<1, true>;
   k_pam_swap_init<<<dim3(1), dim3(1024), 0, st>>>(dist, G, K, init, anchor, medoids, labels, near, size, within, cost, n_swaps, status,
                                                   w.ctl);
   AG_CHECK_LAUNCH();
   for (int it = 0; it < max_swaps; ++it) {          // every launch returns at once after the choose that ended the walk
     k_pam_state<<<cols, dim3(256), 0, st>>>(dist, G, K, anchor, medoids, labels, near, w.ctl, w.dn, w.ds, w.tag, 0);
     AG_CHECK_LAUNCH();
-    if (K <= AG_SIL_WAVE_ROW_MAX_K)                 // one row per wave, 4 K bins per workgroup (<= 32 KB)
-      k_pam_rows<4, true><<<rows, dim3(256), (size_t)4 * K * 8, st>>>(dist, G, K, w.tag, w.dn, w.ds, w.recD, w.recR, w.ctl);
-    else                                            // one row per workgroup, K bins (<= 32 KB)
-      k_pam_rows<1, true><<<dim3((unsigned)G), dim3(256), (size_t)K * 8, st>>>(dist, G, K, w.tag, w.dn, w.ds, w.recD, w.recR, w.ctl);
+    k_rows<<<rows.grid, dim3(256), rows.lds, st>>>(dist, G, K, w.tag, w.dn, w.ds, w.recD, w.recR, w.ctl);
     AG_CHECK_LAUNCH();
     k_pam_choose<<<dim3(1), dim3(1024), 0, st>>>(G, max_swaps, w.recD, w.recR, medoids, w.ctl);
     AG_CHECK_LAUNCH();
@@ -3047,24 +3017,15 @@ extern "C" int agdiff_silhouette(const float* dist, int32_t G, int32_t K, const 
   if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
   if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
   hipStream_t st = (hipStream_t)stream;
-  if (G == 0) {                                     // no launch: status = 0 and size = 0 (all bits clear), mean and cluster_mean NaN (all bits set), by memsets on the stream
-    const struct { void* p; int v; size_t n; } outs[] = {{status, 0, 4}, {size, 0, (size_t)K * 4}, {mean, 0xff, 8}, {cluster_mean, 0xff, (size_t)K * 8}};
-    for (const auto& o : outs) {
-      const hipError_t e = hipMemsetAsync(o.p, o.v, o.n, st);
-      if (e == hipSuccess) continue;
-      (void)hipGetLastError();
-      return e == hipErrorNoDevice ? AGDIFF_OK : AGDIFF_ERR_LAUNCH;    // (without a device there is nothing to write to)
-    }
-    return AGDIFF_OK;
-  }
+  if (G == 0)                                       // no launch: status = 0 and size = 0, mean and cluster_mean NaN
+    return ag_fill_outputs({{status, 0, 4}, {size, 0, (size_t)K * 4}, {mean, 0xff, 8}, {cluster_mean, 0xff, (size_t)K * 8}}, st);
   int32_t* ctl = (int32_t*)work;
-  int64_t* T = (int64_t*)(work + SIL_CTL_WORDS * 4 / 8);
+  int64_t* T = (int64_t*)(work + KM_CTL_WORDS * 4 / 8);
   k_sil_init<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, a, b, s, other, size, cluster_mean, mean, status, ctl);
   AG_CHECK_LAUNCH();
-  if (K <= AG_SIL_WAVE_ROW_MAX_K)                   // one row per wave, 4 K bins per workgroup (<= 32 KB)
-    k_sil_rows<4><<<dim3((unsigned)((G + 3) / 4)), dim3(256), (size_t)4 * K * 8, st>>>(dist, G, K, labels, size, a, b, s, other, T, ctl);
-  else                                              // one row per workgroup, K bins (<= 32 KB)
-    k_sil_rows<1><<<dim3((unsigned)G), dim3(256), (size_t)K * 8, st>>>(dist, G, K, labels, size, a, b, s, other, T, ctl);
+  const ag_row_launch rows = ag_row_pass_launch(G, K);
+  const auto k_rows = rows.wave_rows ? k_sil_rows<4> : k_sil_rows<1>;
+  k_rows<<<rows.grid, dim3(256), rows.lds, st>>>(dist, G, K, labels, size, a, b, s, other, T, ctl);
   AG_CHECK_LAUNCH();
   k_sil_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, T, size, cluster_mean, mean, status, ctl);
   AG_CHECK_LAUNCH();

@@ -281,6 +281,19 @@ def _add_shared_flags(ap):
                          "writes flat_<i> [G]")
 
 
+def _add_tfd_flags(ap):
+    """--tfd and --tfd-rings of python -m agdiff_amd.picks, .medoids, .pam and .silhouette (.clusters' --tfd takes a threshold)"""
+    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
+    ap.add_argument("--tfd-rings", action="store_true",
+                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+
+
+def _check_tfd_flags(ap, args):
+    """the parser's check of those two flags once they are parsed"""
+    if args.tfd_rings and not args.tfd:
+        ap.error("--tfd-rings goes with --tfd")
+
+
 def _checked_items(items, args, out):
     """The per-molecule block of those four command lines over the (mol, item) pairs of a module's sampled_items: the test set's
     `stereo` / `ez_quads` + `ez` go into the item when the fixes are asked for (a test set without them: ValueError), --drop-invalid

@@ -29,12 +29,37 @@ module's `labels` and sweeps K.
 import numpy as np
 
 from . import _lib
-from .ensemble import _add_shared_flags, _attach, _checked_items, _chosen, _own, _scatter, _usable_matrix, _write_tail
+from .ensemble import (_add_shared_flags, _add_tfd_flags, _attach, _check_tfd_flags, _checked_items, _chosen, _own, _scatter,
+                       _usable_matrix, _write_tail)
 from .molecule import sampled_items
 from .picks import maxmin_pick
 
 MAX_ITER = _lib.DEFINES["AGDIFF_KMEDOIDS_MAX_ITER"]
 WORK_BYTES = _lib.DEFINES["AGDIFF_KMEDOIDS_WORK_BYTES"]
+
+
+def _check_dist(dist, G):
+    """the float matrix of every walk: a contiguous float32 tensor [G, G] on the GPU, or ValueError"""
+    _lib.require_device_table(dist, "dist must be a contiguous float32 tensor [G, G] on the GPU")
+    if tuple(dist.shape) != (G, G):
+        raise ValueError("dist must be [%d, %d] (got %s)" % (G, G, tuple(dist.shape)))
+
+
+def _check_init(init, at_least=0):
+    """the seeds of kmedoids and pam.pam_swap: a contiguous int32 tensor [K] on the GPU, K >= at_least, or ValueError"""
+    import torch
+    if not (torch.is_tensor(init) and init.is_cuda and init.dtype == torch.int32 and init.dim() == 1 and init.is_contiguous()
+            and init.shape[0] >= at_least):
+        raise ValueError("init must be a contiguous int32 tensor [K] on the GPU" + (", K >= %d" % at_least if at_least else ""))
+
+
+def _outputs(dist, G, K, work_bytes):
+    """what agdiff_kmedoids, agdiff_pam_build and agdiff_pam_swap write, on dist's device: medoids, labels, near, size, within,
+    cost, n_iter / n_swaps, status, and their `work`"""
+    import torch
+    new = lambda n, dtype: torch.empty(n, dtype=dtype, device=dist.device)
+    return (new(K, torch.int32), new(G, torch.int32), new(G, torch.float32), new(K, torch.int32), new(K, torch.float64),
+            new(1, torch.float64), new(1, torch.int32), new(1, torch.int32), new(work_bytes // 8, torch.int64))
 
 
 def kmedoids(dist, G, init, max_iter=32):
@@ -44,26 +69,52 @@ def kmedoids(dist, G, init, max_iter=32):
     to its medoid as the matrix stores it (-1 and NaN for a conformer that init[0]'s row marks as unusable), the members and the
     summed distance of each cluster, the total, the number of updates made and 0 (converged) / 1 (stopped at max_iter) / 2 (a seed
     out of range, twice, or unusable: nothing was computed).  More than AGDIFF_PRUNE_MAX_CONFS conformers: AgdiffLimitError."""
-    import torch
-    _lib.require_device_table(dist, "dist must be a contiguous float32 tensor [G, G] on the GPU")
-    if tuple(dist.shape) != (G, G):
-        raise ValueError("dist must be [%d, %d] (got %s)" % (G, G, tuple(dist.shape)))
-    if not (torch.is_tensor(init) and init.is_cuda and init.dtype == torch.int32 and init.dim() == 1 and init.is_contiguous()):
-        raise ValueError("init must be a contiguous int32 tensor [K] on the GPU")
+    _check_dist(dist, G)
+    _check_init(init)
     if int(max_iter) != max_iter or not 1 <= max_iter <= MAX_ITER:
         raise ValueError("max_iter must be a count in 1 .. %d (got %r)" % (MAX_ITER, max_iter))
-    dev, K = dist.device, int(init.shape[0])
-    medoids = torch.empty(K, dtype=torch.int32, device=dev)
-    labels = torch.empty(G, dtype=torch.int32, device=dev)
-    near = torch.empty(G, dtype=torch.float32, device=dev)
-    size = torch.empty(K, dtype=torch.int32, device=dev)
-    within = torch.empty(K, dtype=torch.float64, device=dev)
-    cost = torch.empty(1, dtype=torch.float64, device=dev)
-    n_iter = torch.empty(1, dtype=torch.int32, device=dev)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    work = torch.empty(WORK_BYTES // 8, dtype=torch.int64, device=dev)
-    _lib.call("agdiff_kmedoids", dist, int(G), K, init, int(max_iter), medoids, labels, near, size, within, cost, n_iter, status, work)
-    return medoids, labels, near, size, within, cost, n_iter, status
+    K = int(init.shape[0])
+    outs = _outputs(dist, G, K, WORK_BYTES)
+    _lib.call("agdiff_kmedoids", dist, int(G), K, init, int(max_iter), *outs)
+    return outs[:8]
+
+
+def _explicit_seeds(init, k, names):
+    """`init` of medoid_conformers and pam.pam_conformers, one of `names` or k distinct conformer indices (anything else:
+    ValueError): (seeds, check) -- the indices as a list of ints, None for a name, and the check(G, mask, why) of theirs that
+    ensemble._usable_matrix makes against the item's conformers"""
+    listed = ", ".join(map(repr, names))
+    seeds = None
+    if not isinstance(init, str):
+        seeds = np.asarray(init).reshape(-1).tolist()
+        if len(seeds) != k or any(int(s) != s for s in seeds) or len(set(seeds)) != len(seeds):
+            raise ValueError("init must be one of %s or %d distinct conformer indices (got %r)" % (listed, k, init))
+        seeds = [int(s) for s in seeds]
+    elif init not in names:
+        raise ValueError("init must be one of %s or a sequence of conformer indices (got %r)" % (listed, init))
+
+    def check_seeds(G, mask, why):
+        for s in seeds or ():
+            if not 0 <= s < G:
+                raise ValueError("init: %d is not the index of a conformer, 0 .. %d" % (s, G - 1))
+            if mask is not None and not mask[s]:
+                raise ValueError("init: %d is a conformer %s" % (s, why))
+    return seeds, check_seeds
+
+
+def _seed_tensor(m, k, init, seeds):
+    """The seeds of a walk over the usable conformers of the namespace m (at least one), in their compacted numbering: (int32
+    tensor [K] on the device, K).  `seeds`: checked explicit ones in the item's own numbering (K = k); None: `init` says --
+    "first", the first K = min(k, G); anything else, the first k MaxMin picks from the first usable conformer, K of them."""
+    import torch
+    dev, K = m.out.device, min(int(k), m.G)
+    if seeds is not None:
+        return torch.tensor(seeds if m.mask is None else [int(m.mask[:s].sum()) for s in seeds], dtype=torch.int32, device=dev), K
+    if init == "first":
+        return torch.arange(K, dtype=torch.int32, device=dev), K
+    picks, _, _, _, n_picked, _ = maxmin_pick(m.out, m.G, K)
+    K = int(n_picked.item())
+    return picks[:K].contiguous(), K
 
 
 def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=True, device="cuda", valid=None, fix_handedness=False,
@@ -97,21 +148,7 @@ def medoid_conformers(item, k, metric="rmsd", init="maxmin", max_iter=32, align=
         raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
     if int(max_iter) != max_iter or not 1 <= max_iter <= MAX_ITER:
         raise ValueError("max_iter must be a count in 1 .. %d (got %r)" % (MAX_ITER, max_iter))
-    seeds = None
-    if not isinstance(init, str):
-        seeds = [s for s in np.asarray(init).reshape(-1).tolist()]
-        if len(seeds) != k or any(int(s) != s for s in seeds) or len(set(seeds)) != len(seeds):
-            raise ValueError("init must be 'maxmin', 'first' or %d distinct conformer indices (got %r)" % (k, init))
-        seeds = [int(s) for s in seeds]
-    elif init not in ("maxmin", "first"):
-        raise ValueError("init must be 'maxmin', 'first' or a sequence of conformer indices (got %r)" % (init,))
-
-    def check_seeds(G, mask, why):
-        for s in seeds or ():
-            if not 0 <= s < G:
-                raise ValueError("init: %d is not the index of a conformer, 0 .. %d" % (s, G - 1))
-            if mask is not None and not mask[s]:
-                raise ValueError("init: %d is a conformer %s" % (s, why))
+    seeds, check_seeds = _explicit_seeds(init, k, ("maxmin", "first"))
     m = _usable_matrix(item, "medoid_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_seeds)
     return _from_matrix(m, k, init, seeds, max_iter, align)
 
@@ -126,17 +163,8 @@ def _from_matrix(m, k, init, seeds, max_iter, align):
                            "near": _scatter(m, none(torch.float32), float("nan")), "count": none(torch.int32),
                            "population": none(torch.float32), "within": none(torch.float64), "cost": 0.0, "iters": 0,
                            "converged": True, "pos": m.gen[:0]})
-    G, out, dev = m.G, m.out, m.out.device
-    K = min(int(k), G)
-    if seeds is not None:                                # (K == k: the seeds are distinct usable conformers) in compacted numbering
-        first = torch.tensor(seeds if m.mask is None else [int(m.mask[:s].sum()) for s in seeds], dtype=torch.int32, device=dev)
-    elif init == "first":
-        first = torch.arange(K, dtype=torch.int32, device=dev)
-    else:
-        picks, _, _, _, n_picked, _ = maxmin_pick(out, G, K)
-        K = int(n_picked.item())
-        first = picks[:K].contiguous()
-    return _result(m, kmedoids(out, G, first, max_iter=max_iter), seeds, align)
+    first, _ = _seed_tensor(m, k, init, seeds)
+    return _result(m, kmedoids(m.out, m.G, first, max_iter=max_iter), seeds, align)
 
 
 def _result(m, walked, seeds, align):
@@ -166,19 +194,29 @@ def _parser():
                 self.error("--count must be at least 1")
             if not 1 <= args.max_iter <= MAX_ITER:
                 self.error("--max-iter must be in 1 .. %d" % MAX_ITER)
-            if args.tfd_rings and not args.tfd:
-                self.error("--tfd-rings goes with --tfd")
+            _check_tfd_flags(self, args)
             return args
     ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     _add_shared_flags(ap)
     ap.add_argument("--count", type=int, required=True, help="the number of medoids per molecule")
-    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
-    ap.add_argument("--tfd-rings", action="store_true",
-                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+    _add_tfd_flags(ap)
     ap.add_argument("--init", choices=("maxmin", "first"), default="maxmin",
                     help="the seeds: the first K MaxMin picks (agdiff_amd.picks), or the first K conformers that are not left out")
     ap.add_argument("--max-iter", type=int, default=32, help="at most this many updates (1 .. %d)" % MAX_ITER)
     return ap
+
+
+def _write_medoids(out, i, res, steps_key, count=True):
+    """molecule i's result of medoid_conformers (steps_key "iters") or pam.pam_conformers ("swaps") into `out`, as python -m
+    agdiff_amd.medoids, .pam and .silhouette --sweep write it; count=False (the sweep, whose silhouette part writes the same
+    `count_<i>`) leaves that key out"""
+    for key, name in (("medoids", "medoid"), ("labels", "cluster"), ("near", "dist"), ("count", "count"),
+                      ("population", "population"), ("within", "within"), ("pos", "pos")):
+        if count or key != "count":
+            out["%s_%d" % (name, i)] = res[key].cpu().numpy()
+    out["cost_%d" % i] = np.float64(res["cost"])
+    out["%s_%d" % (steps_key, i)] = np.int32(res[steps_key])
+    out["converged_%d" % i] = np.int8(res["converged"])
 
 
 def main(argv=None):
@@ -199,12 +237,7 @@ def main(argv=None):
         res = medoid_conformers(item, args.count, metric=metric, init=args.init, max_iter=args.max_iter, align=args.align,
                                 device=args.device, valid=valid, fix_handedness=args.fix_handedness,
                                 fix_double_bonds=args.fix_double_bonds, tfd_rings=args.tfd_rings)
-        for key, name in (("medoids", "medoid"), ("labels", "cluster"), ("near", "dist"), ("count", "count"),
-                          ("population", "population"), ("within", "within"), ("pos", "pos")):
-            out["%s_%d" % (name, i)] = res[key].cpu().numpy()
-        out["cost_%d" % i] = np.float64(res["cost"])
-        out["iters_%d" % i] = np.int32(res["iters"])
-        out["converged_%d" % i] = np.int8(res["converged"])
+        _write_medoids(out, i, res, "iters")
         _write_tail(out, mol, res)
         total += int(res["labels"].shape[0])
         found += int(res["medoids"].shape[0])

@@ -26,27 +26,14 @@ is no switch for it in `silhouette --sweep` and no driver flag.  Agreement with 
 import numpy as np
 
 from . import _lib
-from .ensemble import _add_shared_flags, _checked_items, _usable_matrix, _write_tail
-from .medoids import MAX_ITER, _from_matrix, _result, kmedoids
+from .ensemble import _add_shared_flags, _add_tfd_flags, _check_tfd_flags, _checked_items, _usable_matrix, _write_tail
+from .medoids import (MAX_ITER, _check_dist, _check_init, _explicit_seeds, _from_matrix, _outputs, _result, _seed_tensor,
+                      _write_medoids, kmedoids)
 from .molecule import sampled_items
-from .picks import maxmin_pick
 
 MAX_SWAPS = _lib.DEFINES["AGDIFF_PAM_MAX_SWAPS"]
 WORK_BYTES = _lib.DEFINES["AGDIFF_PAM_WORK_BYTES"]
 INITS = ("build", "maxmin", "first", "alternate")
-
-
-def _outputs(dist, G, K):
-    import torch
-    _lib.require_device_table(dist, "dist must be a contiguous float32 tensor [G, G] on the GPU")
-    if tuple(dist.shape) != (G, G):
-        raise ValueError("dist must be [%d, %d] (got %s)" % (G, G, tuple(dist.shape)))
-    dev = dist.device
-    return (torch.empty(K, dtype=torch.int32, device=dev), torch.empty(G, dtype=torch.int32, device=dev),
-            torch.empty(G, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.int32, device=dev),
-            torch.empty(K, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float64, device=dev),
-            torch.empty(1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
-            torch.empty(WORK_BYTES // 8, dtype=torch.int64, device=dev))
 
 
 def pam_build(dist, G, k, anchor=0):
@@ -59,7 +46,8 @@ def pam_build(dist, G, k, anchor=0):
         raise ValueError("k must be a count of at least 1 (got %r)" % (k,))
     if int(anchor) != anchor:
         raise ValueError("anchor must be a conformer index (got %r)" % (anchor,))
-    outs = _outputs(dist, G, int(k))
+    _check_dist(dist, G)
+    outs = _outputs(dist, G, int(k), WORK_BYTES)
     _lib.call("agdiff_pam_build", dist, int(G), int(k), int(anchor), *outs)
     return outs[:8]
 
@@ -71,16 +59,14 @@ def pam_swap(dist, G, init, anchor=None, max_swaps=64):
     in n_iter's place; status 0 (no exchange lowers the cost), 1 (max_swaps were made and nothing was looked for after the last)
     or 2 (a seed or the anchor out of range, a seed twice or unusable: nothing was computed).  Calling again with the returned
     medoids and the same anchor continues the same walk."""
-    import torch
-    if not (torch.is_tensor(init) and init.is_cuda and init.dtype == torch.int32 and init.dim() == 1 and init.is_contiguous()
-            and init.shape[0] >= 1):
-        raise ValueError("init must be a contiguous int32 tensor [K] on the GPU, K >= 1")
+    _check_init(init, at_least=1)
     if int(max_swaps) != max_swaps or not 0 <= max_swaps <= MAX_SWAPS:
         raise ValueError("max_swaps must be a count in 0 .. %d (got %r)" % (MAX_SWAPS, max_swaps))
     if anchor is not None and int(anchor) != anchor:
         raise ValueError("anchor must be a conformer index or None (got %r)" % (anchor,))
     K = int(init.shape[0])
-    outs = _outputs(dist, G, K)
+    _check_dist(dist, G)
+    outs = _outputs(dist, G, K, WORK_BYTES)
     if anchor is None:
         anchor = int(init[0].item())
     _lib.call("agdiff_pam_swap", dist, int(G), K, init, int(anchor), int(max_swaps), *outs)
@@ -106,21 +92,7 @@ def pam_conformers(item, k, metric="rmsd", init="build", max_swaps=4096, chunk=6
         raise ValueError("max_swaps must be a count of at least 0 (got %r)" % (max_swaps,))
     if int(chunk) != chunk or not 1 <= chunk <= MAX_SWAPS:
         raise ValueError("chunk must be a count in 1 .. %d (got %r)" % (MAX_SWAPS, chunk))
-    seeds = None
-    if not isinstance(init, str):
-        seeds = [s for s in np.asarray(init).reshape(-1).tolist()]
-        if len(seeds) != k or any(int(s) != s for s in seeds) or len(set(seeds)) != len(seeds):
-            raise ValueError("init must be one of %s or %d distinct conformer indices (got %r)" % (", ".join(map(repr, INITS)), k, init))
-        seeds = [int(s) for s in seeds]
-    elif init not in INITS:
-        raise ValueError("init must be one of %s or a sequence of conformer indices (got %r)" % (", ".join(map(repr, INITS)), init))
-
-    def check_seeds(G, mask, why):
-        for s in seeds or ():
-            if not 0 <= s < G:
-                raise ValueError("init: %d is not the index of a conformer, 0 .. %d" % (s, G - 1))
-            if mask is not None and not mask[s]:
-                raise ValueError("init: %d is a conformer %s" % (s, why))
+    seeds, check_seeds = _explicit_seeds(init, k, INITS)
     m = _usable_matrix(item, "pam_conformers", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings, check=check_seeds)
     return _walk(m, k, init, seeds, max_swaps, chunk, align)
 
@@ -135,25 +107,20 @@ def _walk(m, k, init, seeds, max_swaps, chunk, align):
         if init == "build":
             res["build_cost"] = 0.0
         return res
-    G, out, dev = m.G, m.out, m.out.device
-    K, build_cost = min(int(k), G), None
-    if seeds is not None:                                # in compacted numbering
-        med = torch.tensor(seeds if m.mask is None else [int(m.mask[:s].sum()) for s in seeds], dtype=torch.int32, device=dev)
-        anchor = int(med[0].item())
-    elif init == "build":
-        anchor = 0
+    G, out = m.G, m.out
+    anchor, build_cost = 0, None                         # (the first usable conformer's row marks the usable ones)
+    if seeds is None and init == "build":
+        K = min(int(k), G)
         built = pam_build(out, G, K, anchor)
         if int(built[7].item()) == 2:
             raise ValueError("pam_conformers: fewer than %d conformers are usable together with conformer 0 (a distance to it that "
                              "is not a number >= 0 and <= %d)" % (K, _lib.DEFINES["AGDIFF_KMEDOIDS_MAX_DIST"]))
         med, build_cost = built[0], float(built[5].item())
-    elif init == "first":
-        med, anchor = torch.arange(K, dtype=torch.int32, device=dev), 0
-    else:                                                # MaxMin seeds, from the first usable conformer
-        picks, _, _, _, n_picked, _ = maxmin_pick(out, G, K)
-        K, anchor = int(n_picked.item()), 0
-        med = picks[:K].contiguous()
-        if init == "alternate":
+    else:                                                # explicit seeds, the first K, or MaxMin seeds ("maxmin", "alternate")
+        med, _ = _seed_tensor(m, k, init, seeds)
+        if seeds is not None:
+            anchor = int(med[0].item())
+        elif init == "alternate":
             med = kmedoids(out, G, med, max_iter=MAX_ITER)[0]
     total = 0
     while True:                                          # (memoryless: the chunks are one walk)
@@ -179,15 +146,12 @@ def _parser():
                 self.error("--count must be at least 1")
             if args.max_swaps < 0:
                 self.error("--max-swaps must be at least 0")
-            if args.tfd_rings and not args.tfd:
-                self.error("--tfd-rings goes with --tfd")
+            _check_tfd_flags(self, args)
             return args
     ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     _add_shared_flags(ap)
     ap.add_argument("--count", type=int, required=True, help="the number of medoids per molecule")
-    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
-    ap.add_argument("--tfd-rings", action="store_true",
-                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+    _add_tfd_flags(ap)
     ap.add_argument("--init", choices=INITS, default="build",
                     help="where the swaps start: PAM's BUILD, the first K MaxMin picks, the first K conformers that are not left out, "
                          "or what python -m agdiff_amd.medoids ends at from MaxMin seeds")
@@ -211,12 +175,7 @@ def main(argv=None):
         res = pam_conformers(item, args.count, metric=metric, init=args.init, max_swaps=args.max_swaps, align=args.align,
                              device=args.device, valid=valid, fix_handedness=args.fix_handedness,
                              fix_double_bonds=args.fix_double_bonds, tfd_rings=args.tfd_rings)
-        for key, name in (("medoids", "medoid"), ("labels", "cluster"), ("near", "dist"), ("count", "count"),
-                          ("population", "population"), ("within", "within"), ("pos", "pos")):
-            out["%s_%d" % (name, i)] = res[key].cpu().numpy()
-        out["cost_%d" % i] = np.float64(res["cost"])
-        out["swaps_%d" % i] = np.int32(res["swaps"])
-        out["converged_%d" % i] = np.int8(res["converged"])
+        _write_medoids(out, i, res, "swaps")
         if "build_cost" in res:
             out["build_cost_%d" % i] = np.float64(res["build_cost"])
         _write_tail(out, mol, res)

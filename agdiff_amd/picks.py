@@ -21,7 +21,8 @@ takes the count.  Agreement with rdkit's MaxMinPicker is not claimed: that one d
 import numpy as np
 
 from . import _lib
-from .ensemble import _add_shared_flags, _attach, _checked_items, _chosen, _own, _scatter, _usable_matrix, _write_tail
+from .ensemble import (_add_shared_flags, _add_tfd_flags, _attach, _check_tfd_flags, _checked_items, _chosen, _own, _scatter,
+                       _usable_matrix, _write_tail)
 from .molecule import check_threshold, sampled_items
 
 
@@ -108,8 +109,7 @@ def _parser():
             args = super().parse_args(*a, **kw)
             if args.count is None and args.radius is None:
                 self.error("at least one of --count and --radius is required")
-            if args.tfd_rings and not args.tfd:
-                self.error("--tfd-rings goes with --tfd")
+            _check_tfd_flags(self, args)
             return args
     ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     _add_shared_flags(ap)
@@ -117,9 +117,7 @@ def _parser():
     ap.add_argument("--radius", type=float, default=None,
                     help="stop once every conformer is within this distance of a pick (Angstrom of heavy-atom RMSD; with --tfd a TFD "
                          "in [0, 1]); with --count, whichever comes first")
-    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
-    ap.add_argument("--tfd-rings", action="store_true",
-                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+    _add_tfd_flags(ap)
     ap.add_argument("--first", type=int, default=None, help="the conformer picked first (default: the first one that is not left out)")
     return ap
 

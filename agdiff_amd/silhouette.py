@@ -28,10 +28,10 @@ trained checkpoint's ensembles.
 import numpy as np
 
 from . import _lib
-from .ensemble import _add_shared_flags, _attach, _checked_items, _scatter, _usable_matrix, _write_tail
-from .medoids import MAX_ITER, _result, kmedoids
+from .ensemble import (_add_shared_flags, _add_tfd_flags, _attach, _check_tfd_flags, _checked_items, _scatter, _usable_matrix,
+                       _write_tail)
+from .medoids import MAX_ITER, _check_dist, _result, _seed_tensor, _write_medoids, kmedoids
 from .molecule import as_host, num_atoms, sampled_items
-from .picks import maxmin_pick
 
 MAX_CONFS = _lib.DEFINES["AGDIFF_PRUNE_MAX_CONFS"]
 WORK_BYTES = _lib.DEFINES["AGDIFF_SILHOUETTE_WORK_BYTES"]
@@ -47,9 +47,7 @@ def silhouette(dist, G, labels, K):
     (NaN when empty) and of all members, and 0 / 2 (a label outside -1 .. K - 1: nothing was computed, everything is NaN, -1
     or 0).  The labels are checked on the device and never read here.  More than AGDIFF_PRUNE_MAX_CONFS conformers: AgdiffLimitError."""
     import torch
-    _lib.require_device_table(dist, "dist must be a contiguous float32 tensor [G, G] on the GPU")
-    if tuple(dist.shape) != (G, G):
-        raise ValueError("dist must be [%d, %d] (got %s)" % (G, G, tuple(dist.shape)))
+    _check_dist(dist, G)
     if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int32 and labels.dim() == 1 and labels.is_contiguous()
             and labels.shape[0] == G):
         raise ValueError("labels must be a contiguous int32 tensor [%d] on the GPU" % G)
@@ -167,13 +165,8 @@ def sweep_medoids(item, k_min, k_max, metric="rmsd", init="maxmin", max_iter=32,
     _check_sweep(k_min, k_max, init, max_iter)
     m = _usable_matrix(item, "sweep_medoids", metric, device, valid, fix_handedness, fix_double_bonds, tfd_rings)
     hi = min(int(k_max), m.G)
-    seeds = None
-    if hi >= k_min:
-        if init == "first":
-            seeds = torch.arange(hi, dtype=torch.int32, device=m.out.device)
-        else:
-            seeds, _, _, _, n_picked, _ = maxmin_pick(m.out, m.G, hi)
-            hi = int(n_picked.item())
+    if hi >= k_min:                                      # the seeds of k_max, made once: those of every K are a prefix
+        seeds, hi = _seed_tensor(m, hi, init, None)
     ks = list(range(int(k_min), hi + 1))
     if not ks:
         none = lambda dtype: np.zeros(0, dtype=dtype)
@@ -212,8 +205,7 @@ def _parser():
                     self.error("--sweep runs at most %d values of K" % MAX_SWEEP)
             if not 1 <= args.max_iter <= MAX_ITER:
                 self.error("--max-iter must be in 1 .. %d" % MAX_ITER)
-            if args.tfd_rings and not args.tfd:
-                self.error("--tfd-rings goes with --tfd")
+            _check_tfd_flags(self, args)
             return args
     ap = Parser(description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     _add_shared_flags(ap)
@@ -222,9 +214,7 @@ def _parser():
     ap.add_argument("--label-key", default="cluster", help="the key of --labels: cluster (default), or owner for python -m agdiff_amd.picks")
     ap.add_argument("--sweep", type=int, nargs=2, metavar=("LO", "HI"), default=None,
                     help="no labels: run k-medoids for K = LO .. HI and keep the K with the highest mean silhouette")
-    ap.add_argument("--tfd", action="store_true", help="the torsion fingerprint deviation (agdiff_amd.torsions) in the RMSD's place")
-    ap.add_argument("--tfd-rings", action="store_true",
-                    help="with --tfd: the rings are terms of the TFD too (agdiff_amd.rings): chair and boat are far apart")
+    _add_tfd_flags(ap)
     ap.add_argument("--init", choices=("maxmin", "first"), default="maxmin", help="with --sweep: k-medoids' seeds (agdiff_amd.medoids)")
     ap.add_argument("--max-iter", type=int, default=32, help="with --sweep: at most this many updates per K (1 .. %d)" % MAX_ITER)
     return ap
@@ -266,12 +256,7 @@ def main(argv=None):
                 sil = tail = silhouette_conformers(item, np.full(everybody, -1), valid=valid, **kw)
             else:
                 sil, tail = sweep["silhouette"], sweep["medoids"]
-                for key, name in (("medoids", "medoid"), ("labels", "cluster"), ("near", "dist"), ("population", "population"),
-                                  ("within", "within"), ("pos", "pos")):
-                    out["%s_%d" % (name, i)] = tail[key].cpu().numpy()
-                out["cost_%d" % i] = np.float64(tail["cost"])
-                out["iters_%d" % i] = np.int32(tail["iters"])
-                out["converged_%d" % i] = np.int8(tail["converged"])
+                _write_medoids(out, i, tail, "iters", count=False)     # (`count_<i>` is written below: the same array)
         for key, name in (("s", "sil"), ("a", "sil_a"), ("b", "sil_b"), ("other", "sil_other"), ("cluster_mean", "sil_cluster"),
                           ("count", "count")):
             out["%s_%d" % (name, i)] = sil[key].cpu().numpy()

@@ -471,7 +471,8 @@ def test_command_line_round_trip(tmp_path, capsys):
                                 ("cluster", np.int32, (G,)), ("dist", np.float32, (G,)), ("count", np.int32, (K,)),
                                 ("population", np.float32, (K,)), ("within", np.float64, (K,)), ("cost", np.float64, ()),
                                 ("iters", np.int32, ()), ("converged", np.int8, ()), ("pos", np.float32, (K, n, 3)),
-                                ("sil", np.float64, (G,)), ("sil_other", np.int32, (G,)), ("sil_cluster", np.float64, (K,))):
+                                ("sil", np.float64, (G,)), ("sil_a", np.float64, (G,)), ("sil_b", np.float64, (G,)),
+                                ("sil_other", np.int32, (G,)), ("sil_cluster", np.float64, (K,)), ("sil_mean", np.float64, ())):
             assert z["%s_%d" % (k, i)].dtype == dtype and z["%s_%d" % (k, i)].shape == shape, (k, i)
         assert z["sil_mean_%d" % i] == z["sweep_sil_%d" % i][K - 2] == z["sweep_sil_%d" % i].max()
         assert z["cost_%d" % i] == z["sweep_cost_%d" % i][K - 2] and z["count_%d" % i].sum() == G
