@@ -239,16 +239,8 @@ int local_branch(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdi
   }
   if (split && split_ready && hipEventRecord(split_ready, (hipStream_t)stream) != hipSuccess) return AGDIFF_ERR_LAUNCH;
   AG_TRY(agdiff_gin_encoder(p, topo, ws, canon ? 1 : 0, stream));
-  if (topo->num_local > 0) {
-    agdiff_head_params_t hl = p->head_local;       // (the hidden layer's range flags go to this workspace)
-    hl.range_rows = ws->range_rows;
-    if (canon)
-      AG_TRY(agdiff_pair_head(&hl, ws->num_local_canon, ctiles, topo->lc_src, topo->lc_dst, ws->hl, nullptr,
-                              ws->l_attr_rows, topo->lc_pos, topo->lc_mir, ws->l_inv, stream));
-    else
-      AG_TRY(agdiff_pair_head(&hl, ws->num_local, ltiles, topo->loc_src, topo->loc_dst, ws->hl, nullptr,
-                              ws->l_attr_rows, nullptr, nullptr, ws->l_inv, stream));
-  }
+  // (over the type-pure tiles with the edge_attr half by polynomial where the host packed head sets: agdiff_local_head)
+  if (topo->num_local > 0) AG_TRY(agdiff_local_head(p, topo, ws, canon ? 1 : 0, stream));
   return AGDIFF_OK;
 }
 

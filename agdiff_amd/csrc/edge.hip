@@ -983,6 +983,136 @@ __global__ void __launch_bounds__(64 * AG_PERSIST_WAVES, 4) k_pair_head_poly(Hea
   }
 }
 
+// ------------------------------------------------------------------------------ local pair head over type-pure tiles
+struct HeadTypedArgs {
+  agdiff_head_params_t hp;
+  const int32_t* idx;         // [16 tiles] canonical index (row of attr_rows, entry of len) or -1: topo->lh_*
+  const int32_t* src;
+  const int32_t* dst;
+  const int32_t* pos;
+  const int32_t* mir;
+  const int32_t* tile_type;   // [tiles]
+  const float* len;           // [Lc]
+  const float* node_h;        // [N][128]
+  const float* attr_rows;     // [Lc][128]
+  const float* sets;          // [near + far sets] x pkk [1][8]
+  const int32_t* near_set;    // [100] type -> set or -1
+  const int32_t* far_set;     // [100] or null
+  float* out;
+  int64_t tiles;
+  int32_t lds_sets;           // sets 0..lds_sets-1 are copied to LDS, the others are read from L2
+  float cutoff;
+  float two_over_rc;
+  float far_hi;
+  float two_over_far;
+};
+#define AG_HEADT_LDS_SETS 4      // 64 + 32 KiB of weights + 4 x 16 KiB of coefficients = 160 KiB
+
+// k_pair_head for the canonical local edges in tiles of ONE edge type (agdiff_topo_t.lh_*): the edge_attr half of the first layer,
+// layers.0.weight[:, 128:] @ edge_attr(d, type), as one k-tile from the type's coefficient set where every length of the tile lies in
+// the set's range -- near [0, cutoff] or far (cutoff, far_hi] -- and from the edge_attr rows otherwise (a type without a set, a
+// length outside the ranges or not finite, both ranges in one tile): then the four k-tiles of k_pair_head in its order, with that
+// half of the weights streamed from L2 (it has no place in LDS next to the sets), so those tiles' results are k_pair_head's bits.
+// The branch is uniform per tile.  Pad rows (idx < 0) write nothing.
+template <int MODE>
+__global__ void __launch_bounds__(64 * AG_PERSIST_WAVES, 4) k_pair_head_typed(HeadTypedArgs a) {
+  extern __shared__ u32x4 ag_headt_smem[];
+  lds_u32x4* lw1 = (lds_u32x4*)ag_headt_smem;     // k-tiles 0..3 of pkk [8][8] (h_src * h_dst half) = 32 blocks
+  lds_u32x4* lw2 = lw1 + 32 * 128;                // pk  [4][4] = 16 blocks
+  lds_u32x4* lws = lw2 + 16 * 128;                // lds_sets x pkk [1][8]
+  ag_copy_lds(lw1, reinterpret_cast<const u32x4*>(a.hp.w1_pk), 32 * 128);
+  ag_copy_lds(lw2, reinterpret_cast<const u32x4*>(a.hp.w2_pk), 16 * 128);
+  if (a.lds_sets > 0) ag_copy_lds(lws, reinterpret_cast<const u32x4*>(a.sets), a.lds_sets * 8 * 128);
+  __syncthreads();
+  const int lane0 = ag_lane();
+  const int64_t stride = (int64_t)gridDim.x * AG_PERSIST_WAVES;
+  const int64_t wg = (gridDim.x % 8 == 0) ? (int64_t)(blockIdx.x % 8) * (gridDim.x / 8) + blockIdx.x / 8 : (int64_t)blockIdx.x;
+  for (int64_t tile = wg * AG_PERSIST_WAVES + (threadIdx.x >> 6); tile < a.tiles; tile += stride) {
+    int lane = lane0;
+    asm volatile("" : "+v"(lane));
+    const int q = lane >> 4;
+    const int64_t e = tile * AG_TW + (lane & 15);
+    const int c = a.idx[e];
+    const bool valid = c >= 0;
+    const int s = valid ? a.src[e] : 0, t = valid ? a.dst[e] : 0;
+    const float d = valid ? a.len[c] : 0.0f;
+    const int ty = a.tile_type[tile];
+    const int nset = a.near_set[ty], fset = a.far_set ? a.far_set[ty] : -1;
+    // (NaN lengths by their bit pattern: this file is built with -fno-honor-nans)
+    const bool is_nan = (__float_as_uint(d) & 0x7FFFFFFFu) > 0x7F800000u;
+    const bool in_near = !is_nan && d >= 0.0f && d <= a.cutoff;
+    const bool in_far = !is_nan && d > a.cutoff && d <= a.far_hi;
+    const bool all_near = nset >= 0 && __ballot(valid && !in_near) == 0;
+    const bool all_far = !all_near && fset >= 0 && __ballot(valid && !in_far) == 0;
+    const int set = all_near ? nset : all_far ? fset : -1;
+
+    f32x4 y1[8];
+    ag_init_vec<8>(y1, a.hp.b1, q);
+    {
+      const float* hs = a.node_h + (size_t)ag_piece_row_value(s, lane) * 128;
+      const float* ht = a.node_h + (size_t)ag_piece_row_value(t, lane) * 128;
+      const int to_op = ag_to_operand_addr(lane);
+      AgIn<MODE> sl[2];
+      f32x4 raw[4];
+      auto fetch = [&](f32x4 (&r)[4], int k) {
+        ag_load_slice_pieces(r[0], r[1], hs, k, lane);
+        ag_load_slice_pieces(r[2], r[3], ht, k, lane);
+      };
+      auto finish = [&](AgIn<MODE>& dst, const f32x4 (&r)[4]) {
+        ag_cvt(ag_permute4(r[0] * r[2], to_op), ag_permute4(r[1] * r[3], to_op), dst);
+      };
+      fetch(raw, 0);
+      finish(sl[0], raw);
+      const lds_u32x4* lw1_l = ag_lds_base(lw1, lane);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k + 1 < 4) fetch(raw, k + 1);       // one slice ahead: the loads fly during slice k's MFMAs
+        if (k & 1) ag_dense_lds<MODE, false, true, 1, 8, 1, 0>(sl, y1, lw1_l + (k * 8) * 128, 0);
+        else ag_dense_lds<MODE, false, true, 1, 8, 0, 0>(sl, y1, lw1_l + (k * 8) * 128, 0);
+        if (k + 1 < 4) finish(sl[(k + 1) & 1], raw);
+      }
+      if (set >= 0) {
+        AgIn<MODE> ph[1];
+        ag_poly_features<MODE, 1>(all_near ? d : d - a.cutoff, all_near ? a.two_over_rc : a.two_over_far, q, ph);
+        if (set < a.lds_sets)
+          ag_dense_lds<MODE, false, true, 1, 8, 0, 0>(ph, y1, ag_lds_base(lws + (size_t)set * (8 * 128), lane), 0);
+        else
+          ag_dense<MODE, false, true, 1, 8, 0, 0, 2>(ph, y1, a.sets + (size_t)set * (8 * 512), lane);
+      } else {
+        // the rows of this tile in the piece layout, as k_pair_head reads them
+        const float* ar = a.attr_rows + (size_t)ag_piece_row_value(valid ? c : 0, lane) * 128;
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+          f32x4 r0, r1;
+          ag_load_slice_pieces(r0, r1, ar, k, lane);
+          AgIn<MODE> x[1];
+          ag_cvt(ag_permute4(r0, to_op), ag_permute4(r1, to_op), x[0]);
+          ag_dense<MODE, false, true, 1, 8, 0, 0, 2>(x, y1, ag_wblock(a.hp.w1_pk, (4 + k) * 8), lane);
+        }
+      }
+    }
+    ag_head_act<8>(y1, a.hp.act);
+    f32x4 y2[4];
+    ag_init_vec<4>(y2, a.hp.b2, q);
+    {
+      AgIn<MODE> y1b[4];
+      ag_report_range<MODE>(ag_absmax<MODE, 8>(y1, 0.0f), a.hp.range_rows, s, valid);      // (the hidden layer as an operand: common.hpp)
+      ag_cvt_tiles<MODE, 4, 0>(y1, y1b);
+      ag_dense_lds<MODE, false, false, 4, 4, 0, 0>(y1b, y2, ag_lds_base(lw2, lane), 0);
+    }
+    ag_head_act<4>(y2, a.hp.act);
+    const float o = ag_dot_vec<4>(y2, a.hp.w3, q) + a.hp.b3;
+    if (valid && q == 0) {
+      int l2 = lane0;
+      asm volatile("" : "+v"(l2));
+      const int64_t e2 = tile * AG_TW + (l2 & 15);
+      a.out[a.pos[e2]] = o;
+      const int pm = a.mir[e2];
+      if (pm >= 0) a.out[pm] = o;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------ stand-alone aggregate
 // out[i][:] = sum_{e in in-list of i} x[src[e]][:] * W[e][:]   (PyG propagate, schnet.py:156,161-162).
 // One wave per target node: F/4 lanes cover one edge row with 16-byte loads, so a wave streams
@@ -1357,6 +1487,63 @@ extern "C" int agdiff_pair_head(const agdiff_head_params_t* hp, const int32_t* n
     k_pair_head<decltype(M)::value><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
   });
   AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+// include/agdiff_hip.h: the local head as agdiff_score_forward's local branch runs it
+extern "C" int agdiff_local_head(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, int32_t canonical,
+                                 void* stream) {
+  if (!p || !topo || !ws || !ws->hl || !ws->l_attr_rows || !ws->l_inv) return AGDIFF_ERR_ARG;
+  if (topo->num_local == 0) return AGDIFF_OK;
+  agdiff_head_params_t hl = p->head_local;       // (the hidden layer's range flags go to this workspace)
+  hl.range_rows = ws->range_rows;
+  if (!canonical)
+    return agdiff_pair_head(&hl, ws->num_local, (topo->num_local + AG_TW - 1) / AG_TW, topo->loc_src, topo->loc_dst, ws->hl, nullptr,
+                            ws->l_attr_rows, nullptr, nullptr, ws->l_inv, stream);
+  const bool typed = !p->tune_local_head_poly_off && p->edge_encoder == 0 && p->poly_kt == 1 && p->head_local_poly_pk &&
+                     p->head_local_near_set && p->head_local_near_sets > 0 && topo->num_head_tiles > 0 && topo->lh_idx &&
+                     topo->lh_src && topo->lh_dst && topo->lh_pos && topo->lh_mir && topo->lh_type && ws->lc_len;
+  if (!typed)
+    return agdiff_pair_head(&hl, ws->num_local_canon, (topo->num_local_canon + AG_TW - 1) / AG_TW, topo->lc_src, topo->lc_dst, ws->hl,
+                            nullptr, ws->l_attr_rows, topo->lc_pos, topo->lc_mir, ws->l_inv, stream);
+  if (p->head_local_far_sets < 0 || (p->head_local_far_sets > 0 && (!p->head_local_far_set || !(p->attr_poly_far_hi > p->cutoff))))
+    return AGDIFF_ERR_ARG;
+  HeadTypedArgs a;
+  a.hp = hl;
+  a.idx = topo->lh_idx;
+  a.src = topo->lh_src;
+  a.dst = topo->lh_dst;
+  a.pos = topo->lh_pos;
+  a.mir = topo->lh_mir;
+  a.tile_type = topo->lh_type;
+  a.len = ws->lc_len;
+  a.node_h = ws->hl;
+  a.attr_rows = ws->l_attr_rows;
+  a.sets = p->head_local_poly_pk;
+  a.near_set = p->head_local_near_set;
+  a.far_set = p->head_local_far_sets > 0 ? p->head_local_far_set : nullptr;
+  a.out = ws->l_inv;
+  a.tiles = topo->num_head_tiles;
+  const int nsets = p->head_local_near_sets + p->head_local_far_sets;
+  int lds = p->tune_local_head_lds_sets < 0 ? 0 : (int)ag_tune(p->tune_local_head_lds_sets, AG_HEADT_LDS_SETS);
+  if (lds > AG_HEADT_LDS_SETS) lds = AG_HEADT_LDS_SETS;
+  a.lds_sets = lds < nsets ? lds : nsets;
+  a.cutoff = p->cutoff;
+  a.two_over_rc = 2.0f / p->cutoff;
+  a.far_hi = a.far_set ? p->attr_poly_far_hi : p->cutoff;
+  a.two_over_far = a.far_set ? 2.0f / (p->attr_poly_far_hi - p->cutoff) : 0.0f;
+  int64_t wgs = (a.tiles + AG_PERSIST_WAVES - 1) / AG_PERSIST_WAVES;
+  if (wgs > 256) wgs = 256;
+  const size_t smem = (size_t)(48 + 8 * a.lds_sets) * 2048;
+  static std::atomic<uint64_t> attr_done{0};
+  if (!ag_allow_big_lds(attr_done, (size_t)(48 + 8 * AG_HEADT_LDS_SETS) * 2048, k_pair_head_typed<AG_BF3>, k_pair_head_typed<AG_F32>,
+                        k_pair_head_typed<AG_H3>))
+    return AGDIFF_ERR_LAUNCH;
+  ag_by_mode(hl.precision, [&](auto M) {
+    k_pair_head_typed<decltype(M)::value><<<dim3((unsigned)wgs), dim3(64 * AG_PERSIST_WAVES), smem, (hipStream_t)stream>>>(a);
+  });
+  AG_CHECK_LAUNCH();
+  ag_log_variant(ws, AGDIFF_VAR_LOCAL_HEAD_POLY);
   return AGDIFF_OK;
 }
 

@@ -227,6 +227,24 @@ def fit_attr_far(sd, cfg, typ):
     return _FIT_CACHE[key]
 
 
+def fit_head_local(sd, cfg, typ, far=False):
+    """(coefficients [128, 32] in natural packed column order, error) of the edge_attr half of the LOCAL head's first layer,
+    grad_local_dist_mlp.layers.0.weight[:, 128:] @ edge_attr(d, typ) (common.py:106-109, dualenc.py:226-239), on [0, cutoff] --
+    far: on [cutoff, ATTR_FAR_FACTOR cutoff] -- fitted like every set (float64, Chebyshev nodes, product basis; error on the
+    4,097-point grid relative to the largest value).  agdiff_params_t.head_local_poly_pk."""
+    Wb = sd["grad_local_dist_mlp.layers.0.weight"].detach().cpu().double()[:, H:]
+    import hashlib
+    key = (_poly_weights_digest(sd, cfg), hashlib.sha1(np.ascontiguousarray(Wb.numpy()).tobytes()).hexdigest(), float(cfg.cutoff),
+           int(typ), bool(far), "head_local")
+    if key not in _FIT_CACHE:
+        attr = _edge_attr_fn(sd, "edge_encoder_global", typ)
+        fn = lambda d: (attr(d) @ Wb.T).numpy()
+        rc = float(cfg.cutoff)
+        c, err = fit_poly(fn, ATTR_FAR_FACTOR * rc, 32, lo=rc) if far else fit_poly(fn, rc, 32)
+        _FIT_CACHE[key] = (c[:, poly_feature_order(1)], err)
+    return _FIT_CACHE[key]
+
+
 def _edge_attr_fn(sd, e, typ):
     """d[M] (float64 numpy) -> edge_attr [M, 128] of edges of type `typ`, MLPEdgeEncoder.forward (edge.py:84-103) in
     float64; the trailing attention factor is a softmax over a size-1 axis, i.e. 1."""
@@ -937,6 +955,7 @@ class PackedParams:
             prm.attr_poly_far_set = ctypes.c_void_p(self.attr_far_table.data_ptr())
             prm.attr_poly_far_slots = int((far_table >= 0).sum())
             prm.attr_poly_far_hi = ATTR_FAR_FACTOR * float(self._cfg.cutoff)
+            self._pack_local_head_sets(by_slot)
         table = np.full(100, -1, dtype=np.int32)
         for t, sl in self.local_slots.items():
             table[t] = sl
@@ -950,8 +969,43 @@ class PackedParams:
             prm.poly_slot_mask[w] = sm[w] - (1 << 64) if sm[w] >= (1 << 63) else sm[w]
         return not any(int(t) in self.poly_refused_types for t in types)
 
+    def _pack_local_head_sets(self, by_slot):
+        """agdiff_params_t.head_local_poly_pk: for every slotted local type the edge_attr half of the local head's first layer
+        as a polynomial of d (fit_head_local), near sets in slot order -- the types with the most rows first: the kernel keeps
+        the first four in LDS -- then the far sets of the types that have one.  A type whose fit misses POLY_TOL has no set:
+        its tiles read the edge_attr rows.  Three MFMA passes for every term (no one-pass plan for these sets).  Packed again
+        with every new slot; a set's bits do not depend on the others."""
+        import torch
+        prm = self.struct
+        n0 = self.head_norm["head_local"][0]
+        near, far = np.full(100, -1, dtype=np.int32), np.full(100, -1, dtype=np.int32)
+        sets = []
+        for want_far, table in ((False, near), (True, far)):
+            if want_far and not self.attr_far:
+                break
+            for t in by_slot:
+                c, err = fit_head_local(self._sd, self._cfg, t, far=want_far)
+                self.poly_errors["head_local_type%d%s" % (t, "_far" if want_far else "")] = err
+                if err > POLY_TOL or (want_far and near[t] < 0):
+                    continue
+                table[t] = len(sets)
+                sets.append(pack_blocks(np.asarray(c, dtype=np.float64) * n0, kouter=True, mode=self._mode_local))
+        self.head_local_sets = {"near": near, "far": far}
+        if not sets:
+            prm.head_local_poly_pk = prm.head_local_near_set = prm.head_local_far_set = None
+            prm.head_local_near_sets = prm.head_local_far_sets = 0
+            return
+        self.head_local_flat = torch.from_numpy(np.concatenate(sets)).to(self.device)
+        self.head_local_tables = torch.from_numpy(np.concatenate([near, far])).to(self.device)
+        prm.head_local_poly_pk = ctypes.c_void_p(self.head_local_flat.data_ptr())
+        prm.head_local_near_set = ctypes.c_void_p(self.head_local_tables.data_ptr())
+        prm.head_local_far_set = ctypes.c_void_p(self.head_local_tables.data_ptr() + 400)
+        prm.head_local_near_sets = int((near >= 0).sum())
+        prm.head_local_far_sets = int((far >= 0).sum())
+
     TUNING = ("share_rows_min_nodes", "node_ldsw_min_tiles", "node_split_max_tiles", "serial_branches", "local_poly_off",
-              "attr_poly_off", "poly_lds_sets", "cfconv_four_min_quads", "cfconv_quad_tiles")
+              "attr_poly_off", "poly_lds_sets", "cfconv_four_min_quads", "cfconv_quad_tiles", "local_head_poly_off",
+              "local_head_lds_sets")
 
     def set_tuning(self, **kw):
         """Kernel-variant thresholds (include/agdiff_hip.h: agdiff_params_t.tune_*; 0 = library default)."""

@@ -114,6 +114,39 @@ def extend_graph_order_sparse(n, bond_src, bond_dst, bond_type, order=3, num_typ
     return key[keep] // n, key[keep] % n, typ[keep]
 
 
+HEAD_TILE_MAX_PAD = 0.08      # head_tile_permutation: most pad rows, as a share of the tiles' rows
+
+
+def head_tile_permutation(mol, typ, max_pad=HEAD_TILE_MAX_PAD):
+    """agdiff_topo_t.lh_idx / lh_type: the canonical local edges (mol, typ per edge, in canonical order: molecule ascending) in
+    16-row tiles of ONE edge type each, for the local head's per-type coefficient sets.  The molecules are cut into runs of R
+    consecutive ones; inside a run the edges are sorted by type (canonical order kept inside a type, so a molecule's edges -- and
+    the h rows they gather -- stay together) and every (run, type) segment is padded to a multiple of 16 rows.  R = the smallest
+    power of two for which the pad rows are at most `max_pad` of all rows (a segment wastes 7.5 rows on average: per molecule
+    that is a quarter of a drug-like molecule's ~180 canonical edges, over four molecules 6 %), the whole batch as one run at the
+    latest.  Returns (idx [16 Th] canonical index or -1, tile type [Th], R)."""
+    mol, typ = np.asarray(mol, dtype=np.int64), np.asarray(typ, dtype=np.int64)
+    n = mol.shape[0]
+    if n == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), 1
+    assert np.all(np.diff(mol) >= 0) and typ.min() >= 0 and typ.max() < 128
+    R, n_mol = 1, int(mol[-1]) + 1
+    while True:
+        key = (mol // R) * 128 + typ
+        order = np.argsort(key, kind="stable")
+        seg_key, seg_first, seg_cnt = np.unique(key[order], return_index=True, return_counts=True)
+        padded = (seg_cnt + 15) // 16 * 16
+        total = int(padded.sum())
+        if total - n <= max_pad * total or R >= n_mol:
+            break
+        R *= 2
+    seg_of = np.repeat(np.arange(seg_key.shape[0]), seg_cnt)
+    pos = (np.cumsum(padded) - padded)[seg_of] + np.arange(n) - seg_first[seg_of]
+    idx = np.full(total, -1, dtype=np.int64)
+    idx[pos] = order
+    return idx, np.repeat(seg_key % 128, padded // 16), R
+
+
 class BatchTopology:
     # agdiff_cfconv_node gives a wave a GROUP of targets (quad_tgt): four for batches that fill the chip that way (one
     # 16-row local tile then serves four targets: fewest tiles), two or one for small batches, where there are more wave
@@ -374,6 +407,13 @@ class BatchTopology:
         self.lc_tpos = i32(tpos[lc_pos])
         self.lc_tmir = i32(np.where(lc_mir >= 0, tpos[np.maximum(lc_mir, 0)], -1))
         self.lcm_ptr = i32(np.searchsorted(ba[src[lc_pos]], np.arange(G + 1)) if L else np.zeros(G + 1))
+        # the canonical list in type-pure tiles for the local head (agdiff_topo_t.lh_*)
+        lh_idx, lh_type, self.head_run_molecules = head_tile_permutation(ba[src[lc_pos]], typ[lc_pos])
+        lh_real, lh_c = lh_idx >= 0, np.maximum(lh_idx, 0)
+        self.Th = int(lh_type.shape[0])
+        self.lh_idx, self.lh_type = i32(lh_idx), i32(lh_type)
+        self.lh_src, self.lh_dst = i32(np.where(lh_real, src[lc_pos][lh_c], 0) if L else lh_idx), i32(np.where(lh_real, dst[lc_pos][lh_c], 0) if L else lh_idx)
+        self.lh_pos, self.lh_mir = i32(np.where(lh_real, lc_pos[lh_c], -1) if L else lh_idx), i32(np.where(lh_real, lc_mir[lh_c], -1) if L else lh_idx)
         self.local_types = np.unique(typ)                 # PackedParams.ensure_local_types (per-type filter polynomials)
         # int64 copies of the local edges for the API results (forward() returns int64 indices)
         self.loc_index64 = torch.from_numpy(np.stack([src, dst])).to(device)
@@ -387,6 +427,7 @@ class BatchTopology:
         t.num_local_canon = self.Lc
         t.num_local_padded = self.Lp
         t.num_local_tiles = self.T
+        t.num_head_tiles = self.Th
         t.num_quads = self.Q
         t.group_targets = self.group_targets
         tm = [0, 0]
@@ -400,7 +441,8 @@ class BatchTopology:
     _POINTER_FIELDS = ("graph_ptr", "atom_type", "loc_src", "loc_dst", "loc_type", "loc_out_ptr", "loc_in_ptr", "loc_in_eid",
                        "lc_src", "lc_dst", "lc_type", "lc_pos", "lc_mir", "loc_row", "loc_in_src",
                        "loc_in_row", "lp_ptr", "lp_src", "lp_dst", "lp_type", "lp_row", "lc_ppos", "lc_pmir",
-                       "quad_tgt", "lt_ptr", "lt_src", "lt_type", "lc_tpos", "lc_tmir", "lcm_ptr", "loc_bits")
+                       "quad_tgt", "lt_ptr", "lt_src", "lt_type", "lc_tpos", "lc_tmir", "lcm_ptr", "loc_bits",
+                       "lh_idx", "lh_src", "lh_dst", "lh_pos", "lh_mir", "lh_type")
 
     def _set_pointers(self):
         for f in self._POINTER_FIELDS:

@@ -285,6 +285,22 @@ typedef struct agdiff_params {
                                          below, the 12-wave shape (more workgroups for the same quads); -1: never */
   int32_t dist_union_kinks;    /* K: kink slots at the head of dist_union (a power of two in [2, 512]) */
   int32_t dist_union_segments; /* S: segments (= kinks in (0, cutoff] + 1 <= K) whose lines follow */
+  /* The LOCAL head's edge_attr half by polynomial (agdiff_local_head): layers.0.weight[:, 128:] @ edge_attr(d, type) of
+   * grad_local_dist_mlp is linear in the edge_attr row, and the row of a slotted type is a 32-term polynomial of d, so the
+   * product is one too -- one k-tile per edge instead of four, and no 512-byte row to read.  One coefficient set per local
+   * edge type whose fit the host accepted (packing.py fit_head_local: <= POLY_TOL like every fit), packed in precision_local
+   * with head_local's first-layer scale; only with poly_kt == 1. */
+  const float* head_local_poly_pk;     /* [head_local_near_sets + head_local_far_sets] x pkk [1][8] or null: the near sets (d in
+                                          [0, cutoff]) in order of expected row count, then the far sets (d in (cutoff,
+                                          attr_poly_far_hi]); the first tune_local_head_lds_sets stay in LDS, the others are read
+                                          from L2 by the tiles that meet them */
+  const int32_t* head_local_near_set;  /* [100] or null: edge type -> index of its near set in head_local_poly_pk, or -1 */
+  const int32_t* head_local_far_set;   /* [100] or null: ... of its far set, or -1 (its rows beyond the cutoff read l_attr_rows) */
+  int32_t head_local_near_sets;
+  int32_t head_local_far_sets;
+  int32_t tune_local_head_poly_off;    /* [0] 1: the local head reads the edge_attr rows for every tile (k_pair_head) */
+  int32_t tune_local_head_lds_sets;    /* [0 = 4] coefficient sets of the local head kept in LDS next to its weights (at most 4:
+                                          96 KiB of weights + 4 x 16 KiB); -1: none, every set is read from L2 */
 } agdiff_params_t;
 
 /* bits of agdiff_ws_t.variant_log: which kernel variants the launchers chose since the host last cleared it */
@@ -304,6 +320,8 @@ typedef struct agdiff_params {
 #define AGDIFF_VAR_FUSED_FRONT 8192     /* agdiff_sampler_front: update of step t + radius graph of step t + 1 in one launch */
 #define AGDIFF_VAR_CFCONV_NODE_FOUR 16384 /* agdiff_cfconv_node ran its four-waves-per-SIMD shape (tune_cfconv_four_min_quads) */
 #define AGDIFF_VAR_CFCONV_NODE_QUAD 32768 /* agdiff_cfconv_node walked the radius rows in quad tiles (tune_cfconv_quad_tiles) */
+#define AGDIFF_VAR_LOCAL_HEAD_POLY 131072 /* agdiff_local_head: the local head took the edge_attr half of its first layer from per-type
+                                           polynomials over the type-pure tiles (topo->lh_*) */
 #define AGDIFF_VAR_GRAPH_LARGE 65536    /* graph build without adjacency masks (agdiff_graph_build_large: a molecule of more than
                                            AGDIFF_MAX_ATOMS_PER_GRAPH atoms in the batch, or called directly) */
 
@@ -375,6 +393,17 @@ typedef struct agdiff_topo {
   const int32_t* quad_wg_ptr;/* [257] or null: workgroup w of agdiff_cfconv_node's 256 persistent workgroups (k_cfconv_quad) owns the quads
                                 [quad_wg_ptr[w], quad_wg_ptr[w+1]) -- contiguous ranges of like tile counts; null (or fewer workgroups):
                                 equal quad counts */
+  /* The canonical local edges once more for the local head (agdiff_local_head): a static permutation whose 16-row tiles each hold
+   * ONE edge type.  The canonical list is cut into runs of consecutive molecules (the shortest power of two for which the pad
+   * rows stay under 8 % of the rows); inside a run the edges are sorted by type, and every (run, type) segment is padded to a
+   * multiple of 16 rows -- a molecule's h rows stay in one L2, and a tile needs one coefficient set.  Only the head walks it. */
+  int64_t num_head_tiles;    /* Th */
+  const int32_t* lh_idx;     /* [16 Th]: canonical index (row of l_attr_rows, entry of lc_len) of the row's edge, -1 for pad rows */
+  const int32_t* lh_src;     /* [16 Th]: lc_src / lc_dst / lc_pos / lc_mir of that edge (pad rows: 0, 0, -1, -1) */
+  const int32_t* lh_dst;
+  const int32_t* lh_pos;
+  const int32_t* lh_mir;
+  const int32_t* lh_type;    /* [Th]: the tile's edge type */
   const int32_t* loc_bits;   /* (null for batches with max_atoms_per_graph > AGDIFF_MAX_ATOMS_PER_GRAPH) [N][W], W = 2 ceil(max_atoms_per_graph / 64) 32-bit words, or null: the static local in-adjacency of
                                 every atom as a bit mask over its molecule's atoms -- bit (j - graph_ptr[g]) of row i is set when
                                 the local edge j -> i exists.  agdiff_sampler_front copies a molecule's rows into LDS (the radius
@@ -701,6 +730,16 @@ int agdiff_step_graph_destroy(void* graph /* [host] */);
  * there): results to ws->inv_r at the entry's radius row and its mirror's. */
 int agdiff_pair_head_poly_rows(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, int32_t parity,
                                void* stream);
+
+/* grad_local_dist_mlp over the local edges (dualenc.py:226-239), what agdiff_score_forward's local branch ends with: ws->l_inv from
+ * ws->hl and the edge_attr rows ws->l_attr_rows.  canonical != 0: one evaluation per canonical local edge, written to its own
+ * and its mirror's entry of l_inv.  Then, when the host has packed head sets (agdiff_params_t.head_local_poly_pk), poly_kt == 1,
+ * the encoder is the MLP one and tune_local_head_poly_off is 0, the head walks the type-pure tiles topo->lh_*: a tile whose
+ * type has a set and whose lengths all lie in [0, cutoff] (or all in (cutoff, attr_poly_far_hi] with a far set) takes the
+ * edge_attr half of the first layer from that set as ONE k-tile of ws->lc_len; every other tile -- a type without a set, a
+ * length outside those ranges or not finite, both ranges in one tile -- reads its rows of l_attr_rows and runs the four
+ * k-tiles with the arithmetic of agdiff_pair_head (bit-identical results for those tiles).  No atomics: reproducible. */
+int agdiff_local_head(const agdiff_params_t* p, const agdiff_topo_t* topo, const agdiff_ws_t* ws, int32_t canonical, void* stream);
 
 /* In-step timing of the dominant kernel (bench.py's roofline object): between agdiff_profile_cfconv(1) and (0) every CFConv
  * launch that agdiff_score_forward issues for the global branch (one InteractionBlock's agdiff_cfconv_node [+ agdiff_cfconv_local],
