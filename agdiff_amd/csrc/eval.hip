@@ -810,11 +810,10 @@ __global__ void __launch_bounds__(256) k_kmed_costs(const float* __restrict__ di
   if (lane == 0) keys[i] = (sum << 12) | (uint64_t)i;
 }
 
-__global__ void __launch_bounds__(1024) k_kmed_choose(int G, int K, int max_iter, const int32_t* __restrict__ labels,
-                                                      const uint64_t* __restrict__ keys, int32_t* __restrict__ medoids,
-                                                      int32_t* __restrict__ ctl) {
-  if (ctl[KM_DONE] != 0) return;                    // (block-uniform: ctl is written only after the barriers below)
-  __shared__ unsigned long long s_best[AGDIFF_PRUNE_MAX_CONFS];
+// the per-cluster arg-min of k_kmed_choose and k_link_medoids, by one workgroup of 1024 threads: s_best[r] becomes the smallest
+// key cost << 12 | index among the members of rank r (all ones: no member) -- lowest cost, then lowest index.  Ends on a barrier.
+__device__ __forceinline__ void ag_kmed_best(int G, int K, const int32_t* __restrict__ labels, const uint64_t* __restrict__ keys,
+                                             unsigned long long* s_best) {
   const int t = threadIdx.x;
   for (int r = t; r < K; r += 1024) s_best[r] = ~0ull;
   __syncthreads();
@@ -823,6 +822,15 @@ __global__ void __launch_bounds__(1024) k_kmed_choose(int G, int K, int max_iter
     if (l >= 0) atomicMin(&s_best[l], (unsigned long long)keys[j]);   // lowest cost, then lowest index
   }
   __syncthreads();
+}
+
+__global__ void __launch_bounds__(1024) k_kmed_choose(int G, int K, int max_iter, const int32_t* __restrict__ labels,
+                                                      const uint64_t* __restrict__ keys, int32_t* __restrict__ medoids,
+                                                      int32_t* __restrict__ ctl) {
+  if (ctl[KM_DONE] != 0) return;                    // (block-uniform: ctl is written only after the barriers below)
+  __shared__ unsigned long long s_best[AGDIFF_PRUNE_MAX_CONFS];
+  const int t = threadIdx.x;
+  ag_kmed_best(G, K, labels, keys, s_best);
   int changed = 0;
   for (int r = t; r < K; r += 1024) {
     const uint64_t best = s_best[r], mine = keys[medoids[r]];
@@ -1230,6 +1238,301 @@ __global__ void __launch_bounds__(1024) k_pam_build_pick(const float* __restrict
     if (o == bj) tag[o] = 1;
   }
   if (t == 0) medoids[p] = bj;
+}
+
+// Agglomerative linkage over the same float matrix (the rule: include/agdiff_hip.h, agdiff_linkage).  A merge depends on the one
+// before it, so the tree is a SEQUENCE OF LAUNCHES again, two per merge, the kernel boundary the only grid-wide ordering:
+//   k_link_head    one workgroup: the anchor, who is eligible, M, the per-slot state, the empty-tree fill of every output
+//   k_link_rows    one wave per row k (the row scaffold ag_row_pass<4>, no bins): W[k][j] = Q(dist[k][j]) for the live j > k and
+//                  the row's nearest neighbour (nn_key, nn_idx): the smallest key, ties to the lowest j
+//   k_link_choose  one workgroup: the arg-min of (nn_key, k) over the live rows -- lowest key, lowest a, and nn_idx[a] is the
+//                  lowest b --, the merge record, the list splice, size[a], live[b], the control words a, b, the counter
+//   k_link_update  one wave per slot c, writers disjoint by construction: entries with b in them are never written; wave a is
+//                  the only writer of (a, c), c > a, and rescans row a from the values it just made; wave c < a is the only
+//                  writer of (c, a) and rescans row c only if nn_idx[c] was a or b, otherwise it compares the new (key, a) with
+//                  what it holds; wave c > a writes nothing and rescans only if nn_idx[c] was b.  No wave reads what another
+//                  writes in the same launch: (b, c), (c, b) and the sizes and live flags are written by k_link_choose alone.
+//   k_link_order   one workgroup: the list's ranks by pointer jumping in LDS, 12 rounds
+// `work`: 16 control words, nn_key, nn_idx, size, live, next, tail per slot, then at AGDIFF_LINKAGE_WORK_FIXED_BYTES the G x G
+// uint64 square, of which the pairs of eligible conformers k < j are used and all of those are written by k_link_rows.
+enum { LK_COUNT = 0, LK_M = 1, LK_A = 2, LK_B = 3, LK_CTL_WORDS = 16 };   // int32 words at the head of `work`
+struct ag_link_work {
+  int32_t* ctl; double* nn_key; int32_t *nn_idx, *csize, *live, *next, *tail; uint64_t* W;
+  explicit ag_link_work(uint64_t* work)
+      : ctl((int32_t*)work), nn_key((double*)(work + LK_CTL_WORDS * 4 / 8)), nn_idx((int32_t*)(nn_key + AGDIFF_PRUNE_MAX_CONFS)),
+        csize(nn_idx + AGDIFF_PRUNE_MAX_CONFS), live(csize + AGDIFF_PRUNE_MAX_CONFS), next(live + AGDIFF_PRUNE_MAX_CONFS),
+        tail(next + AGDIFF_PRUNE_MAX_CONFS), W(work + AGDIFF_LINKAGE_WORK_FIXED_BYTES / 8) {}
+};
+static_assert(AGDIFF_LINKAGE_WORK_FIXED_BYTES >= LK_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * (8 + 5 * 4) && AGDIFF_LINKAGE_WORK_FIXED_BYTES % 8 == 0,
+              "agdiff_linkage: control words + nn_key, nn_idx, size, live, next, tail per slot");
+static_assert(AGDIFF_PRUNE_MAX_CONFS == 1 << 12 && AGDIFF_KMEDOIDS_MAX_DIST == 4096, "agdiff_linkage: 2^22 pairs of 2^40 fit 64 bits; 12 rounds rank a list");
+static_assert(AGDIFF_LINKAGE_CUT_WORK_BYTES >= KM_CTL_WORDS * 4 + AGDIFF_PRUNE_MAX_CONFS * 8, "agdiff_linkage_cut: control words + one key per conformer");
+#define AG_LINK_NONE 0x7fffffff
+
+__device__ __forceinline__ uint64_t ag_link_join(int method, uint64_t x, uint64_t y) {
+  return method == AGDIFF_LINKAGE_SINGLE ? (x < y ? x : y) : (method == AGDIFF_LINKAGE_COMPLETE ? (x > y ? x : y) : x + y);
+}
+
+// the key of two clusters of sa and sc members with pair weight w, in units of 2^-28: the conversion rounds to nearest even (exact
+// below 2^53), the count is exact, the division is one correctly rounded fp64 division
+__device__ __forceinline__ double ag_link_key(int method, uint64_t w, int sa, int sc) {
+  const double x = (double)w;
+  return method == AGDIFF_LINKAGE_AVERAGE ? x / (double)((uint64_t)sa * (uint64_t)sc) : x;
+}
+
+// row k's nearest neighbour by the wave that owns it: the smallest key over the live j > k, ties to the lowest j, from
+// entry(j), the pair weight of (k, j); (inf, -1) when no live j is left
+template <typename F>
+__device__ __forceinline__ void ag_link_scan(const ag_link_work& w, const ag_row_pass<4>& rp, int method, int G, int k, F entry) {
+  const int sk = w.csize[k];
+  double bk = __builtin_inf();
+  int bj = AG_LINK_NONE;
+  for (int j = k + 1 + rp.tid; j < G; j += 64) {
+    if (!w.live[j]) continue;
+    ag_min_pair(bk, bj, ag_link_key(method, entry(j), sk, w.csize[j]), j);
+  }
+  rp.min_pair(bk, bj);
+  if (rp.tid == 0) {
+    w.nn_key[k] = bk;
+    w.nn_idx[k] = bj == AG_LINK_NONE ? -1 : bj;
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_link_head(const float* __restrict__ dist, int G, int anchor, ag_link_work w,
+                                                    int32_t* __restrict__ left, int32_t* __restrict__ right, double* __restrict__ height,
+                                                    int32_t* __restrict__ size, int32_t* __restrict__ order, int32_t* __restrict__ status) {
+  const int t = threadIdx.x;
+  const bool ok = (unsigned)anchor < (unsigned)G;   // (block-uniform)
+  int M = 0;
+  for (int base = 0; base < G; base += 1024) {      // (every thread reaches every barrier)
+    const int j = base + t;
+    const bool e = ok && j < G && (j == anchor || ag_kmed_valid(dist[(size_t)anchor * (size_t)G + j]));
+    if (j < G) {
+      w.csize[j] = e ? 1 : 0;                       // (0 for good: who is eligible, after the live flags have gone)
+      w.live[j] = e ? 1 : 0;
+      w.next[j] = -1;
+      w.tail[j] = j;
+      w.nn_key[j] = __builtin_inf();
+      w.nn_idx[j] = -1;
+      left[j] = -1;
+      right[j] = -1;
+      height[j] = __builtin_nan("");
+      size[j] = 0;
+      order[j] = -1;
+    }
+    M += __syncthreads_count(e);
+  }
+  if (t < LK_CTL_WORDS) w.ctl[t] = t == LK_M ? M : 0;
+  if (t == 0) status[0] = ok ? 0 : 2;
+}
+
+__global__ void __launch_bounds__(256) k_link_rows(const float* __restrict__ dist, int G, int method, ag_link_work w) {
+  if (w.ctl[LK_M] < 2) return;                      // (nothing to merge)
+  const ag_row_pass<4> rp(nullptr, 0);
+  const int k = rp.i;                               // (wave-uniform)
+  if (k >= G || !w.live[k]) return;
+  const float* __restrict__ row = dist + (size_t)k * (size_t)G;
+  uint64_t* wrow = w.W + (size_t)k * (size_t)G;
+  ag_link_scan(w, rp, method, G, k, [&](int j) {
+    const uint64_t q = ag_kmed_q(row[j]);
+    wrow[j] = q;
+    return q;
+  });
+}
+
+__global__ void __launch_bounds__(1024) k_link_choose(ag_link_work w, int G, int32_t* __restrict__ left, int32_t* __restrict__ right,
+                                                      double* __restrict__ height, int32_t* __restrict__ size) {
+  const int t = w.ctl[LK_COUNT];
+  if (t >= w.ctl[LK_M] - 1) return;                 // (block-uniform: ctl is written only after the barrier of ag_min_pair_over)
+  double bk = __builtin_inf();
+  int a = AG_LINK_NONE;
+  for (int k = threadIdx.x; k < G; k += 1024)
+    if (w.live[k] && w.nn_idx[k] >= 0) ag_min_pair(bk, a, w.nn_key[k], k);
+  ag_min_pair_over<16>(bk, a);
+  if (threadIdx.x != 0 || a == AG_LINK_NONE) return;     // (never none: two live clusters are a pair)
+  const int b = w.nn_idx[a];
+  if (b <= a || b >= G) return;                     // (never)
+  const int sa = w.csize[a], sb = w.csize[b];
+  left[t] = a;
+  right[t] = b;
+  height[t] = bk * (1.0 / 268435456.0);
+  size[t] = sa + sb;
+  w.next[w.tail[a]] = b;                            // b's leaves after a's
+  w.tail[a] = w.tail[b];
+  w.csize[a] = sa + sb;
+  w.live[b] = 0;
+  w.ctl[LK_A] = a;
+  w.ctl[LK_B] = b;
+  w.ctl[LK_COUNT] = t + 1;
+}
+
+// `it`: the number of this launch among the G - 1; merge `it` was made iff the counter has passed it
+__global__ void __launch_bounds__(256) k_link_update(ag_link_work w, int G, int method, int it) {
+  if (it >= w.ctl[LK_COUNT]) return;
+  const ag_row_pass<4> rp(nullptr, 0);
+  const int c = rp.i;                               // (wave-uniform)
+  if (c >= G || !w.live[c]) return;                 // (b is dead already)
+  const int a = w.ctl[LK_A], b = w.ctl[LK_B];
+  uint64_t* W = w.W;
+  uint64_t* wrow = W + (size_t)c * (size_t)G;
+  if (c == a) {
+    ag_link_scan(w, rp, method, G, a, [&](int j) {
+      const uint64_t x = ag_link_join(method, wrow[j], j > b ? W[(size_t)b * (size_t)G + j] : W[(size_t)j * (size_t)G + b]);
+      wrow[j] = x;
+      return x;
+    });
+  } else if (c < a) {
+    const uint64_t x = ag_link_join(method, wrow[a], wrow[b]);
+    const int nn = w.nn_idx[c];
+    if (rp.tid == 0) wrow[a] = x;
+    if (nn == a || nn == b) {
+      ag_link_scan(w, rp, method, G, c, [&](int j) { return j == a ? x : wrow[j]; });
+    } else if (rp.tid == 0) {                       // the new key may be smaller, or tie with a lower index
+      double bk = w.nn_key[c];
+      int bj = nn;
+      ag_min_pair(bk, bj, ag_link_key(method, x, w.csize[c], w.csize[a]), a);
+      w.nn_key[c] = bk;
+      w.nn_idx[c] = bj;
+    }
+  } else if (w.nn_idx[c] == b) {
+    ag_link_scan(w, rp, method, G, c, [&](int j) { return wrow[j]; });
+  }
+}
+
+__global__ void __launch_bounds__(1024) k_link_order(ag_link_work w, int G, int32_t* __restrict__ order) {
+  __shared__ int32_t s_next[AGDIFF_PRUNE_MAX_CONFS], s_after[AGDIFF_PRUNE_MAX_CONFS];
+  const int t = threadIdx.x;
+  for (int j = t; j < G; j += 1024) {
+    const int n = w.csize[j] > 0 ? w.next[j] : -1;
+    s_next[j] = (unsigned)n < (unsigned)G ? n : -1;
+    s_after[j] = s_next[j] >= 0 ? 1 : 0;            // the leaves after j in its list, so far
+  }
+  __syncthreads();
+  for (int round = 0; round < 12; ++round) {        // pointer jumping: 2^12 >= the longest list
+    int nx[4], af[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = t + e * 1024;
+      nx[e] = -1;
+      af[e] = 0;
+      if (j < G) {
+        const int n = s_next[j];
+        af[e] = s_after[j] + (n >= 0 ? s_after[n] : 0);
+        nx[e] = n >= 0 ? s_next[n] : -1;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int j = t + e * 1024;
+      if (j < G) { s_next[j] = nx[e]; s_after[j] = af[e]; }
+    }
+    __syncthreads();
+  }
+  const int M = w.ctl[LK_M];
+  for (int j = t; j < G; j += 1024) order[j] = w.csize[j] > 0 ? M - 1 - s_after[j] : -1;
+}
+
+// The cut of a tree (agdiff_linkage_cut), one workgroup.  The number of merges to apply is the first t that fails a test, a
+// block min; parent[b] = a of the applied ones sits in LDS; thread t takes the conformers 4 t .. 4 t + 3, chases each to its
+// root (a parent has a lower index: at most G steps) and the root flags' prefix sum gives the ranks.  Then the control words of
+// the k-medoids launches that follow: not done, status 0, n_clusters in the updates' place.
+__global__ void __launch_bounds__(1024) k_link_cut(int G, const int32_t* __restrict__ left, const int32_t* __restrict__ right,
+                                                   const double* __restrict__ height, const int32_t* __restrict__ order, int count,
+                                                   double bound, int32_t* __restrict__ medoids, int32_t* __restrict__ labels,
+                                                   float* __restrict__ near, int32_t* __restrict__ size, double* __restrict__ within,
+                                                   double* __restrict__ cost, int32_t* __restrict__ n_clusters,
+                                                   int32_t* __restrict__ status, int32_t* __restrict__ ctl) {
+  __shared__ int32_t s_parent[AGDIFF_PRUNE_MAX_CONFS], s_rank[AGDIFF_PRUNE_MAX_CONFS];
+  __shared__ int32_t s_wave[16];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  int M = 0;
+  for (int base = 0; base < G; base += 1024) {      // (every thread reaches every barrier)
+    const int j = base + t;
+    if (j < G) s_parent[j] = -1;
+    M += __syncthreads_count(j < G && order[j] >= 0);
+  }
+  int n_apply = G - 1, dummy = 0;
+  for (int m = t; m < G - 1; m += 1024)
+    if (left[m] < 0 || M - m <= count || !(height[m] <= bound)) { n_apply = m; break; }     // (M - m clusters are left before merge m)
+  ag_min_pair_over<16>(n_apply, dummy);
+  int bad = 0;
+  for (int m = t; m < n_apply; m += 1024) {
+    const int a = left[m], b = right[m];
+    if (a < 0 || a >= b || b >= G || order[a] < 0 || order[b] < 0) bad = 1;
+    else s_parent[b] = a;
+  }
+  if (__syncthreads_or(bad)) {                      // not a tree: agdiff_kmedoids' status-2 fill, and nothing after this runs
+    ag_kmed_fill_bad(G, G, medoids, labels, near, size, within, cost, n_clusters, status, ctl);
+    return;
+  }
+  int root[4], flag[4], mine = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int j = 4 * t + e;
+    root[e] = -1;
+    flag[e] = 0;
+    if (j < G && order[j] >= 0) {
+      int r = j;
+      for (int s = 0; s < G; ++s) {
+        const int p = s_parent[r];
+        if (p < 0) break;
+        r = p;
+      }
+      root[e] = r;
+      flag[e] = r == j ? 1 : 0;
+    }
+    mine += flag[e];
+  }
+  int incl = mine;                                  // the inclusive prefix sum of the threads' counts: the wave, then the waves
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) s_wave[wv] = incl;
+  __syncthreads();
+  int before = incl - mine, total = 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    before += v < wv ? s_wave[v] : 0;
+    total += s_wave[v];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int j = 4 * t + e;
+    if (j < G) s_rank[j] = before;
+    before += flag[e];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int j = 4 * t + e;
+    if (j < G) labels[j] = root[e] >= 0 ? s_rank[root[e]] : -1;
+  }
+  if (t < KM_CTL_WORDS) ctl[t] = t == KM_ITERS ? total : 0;
+}
+
+// the medoid of every cluster of a cut -- k-medoids' update without an incumbent, from k_kmed_costs' keys through its arg-min --
+// and near relative to it, as ag_kmed_columns writes it; the ranks past the last cluster get -1
+__global__ void __launch_bounds__(1024) k_link_medoids(const float* __restrict__ dist, int G, const int32_t* __restrict__ labels,
+                                                       const uint64_t* __restrict__ keys, int32_t* __restrict__ medoids,
+                                                       float* __restrict__ near, const int32_t* __restrict__ ctl) {
+  if (ctl[KM_DONE] != 0) return;                    // (not a tree: k_link_cut wrote everything)
+  __shared__ unsigned long long s_best[AGDIFF_PRUNE_MAX_CONFS];
+  const int t = threadIdx.x;
+  ag_kmed_best(G, G, labels, keys, s_best);
+  for (int r = t; r < G; r += 1024) medoids[r] = s_best[r] == ~0ull ? -1 : (int)(s_best[r] & 4095);
+  for (int j = t; j < G; j += 1024) {
+    const int l = labels[j];
+    float x = __builtin_nanf("");
+    if (l >= 0) {
+      const int m = (int)(s_best[l] & 4095);
+      x = dist[(size_t)m * (size_t)G + j];
+      x = (m == j || x == 0.0f) ? 0.0f : x;         // (-0 is written as +0)
+    }
+    near[j] = x;
+  }
 }
 
 // eigen-decomposition of the symmetric 4x4 matrix k (upper triangle as in ag_horn_key) by ag_jacobi4 with the rotations
@@ -3028,6 +3331,60 @@ extern "C" int agdiff_silhouette(const float* dist, int32_t G, int32_t K, const 
   k_rows<<<rows.grid, dim3(256), rows.lds, st>>>(dist, G, K, labels, size, a, b, s, other, T, ctl);
   AG_CHECK_LAUNCH();
   k_sil_finish<<<dim3(1), dim3(1024), 0, st>>>(G, K, labels, T, size, cluster_mean, mean, status, ctl);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_linkage(const float* dist, int32_t G, int32_t method, int32_t anchor, int32_t* left, int32_t* right,
+                              double* height, int32_t* size, int32_t* order, int32_t* status, uint64_t* work, void* stream) {
+  if (!dist || !left || !right || !height || !size || !order || !status || !work || G < 0) return AGDIFF_ERR_ARG;
+  if (method < AGDIFF_LINKAGE_SINGLE || method > AGDIFF_LINKAGE_AVERAGE) return AGDIFF_ERR_ARG;
+  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  hipStream_t st = (hipStream_t)stream;
+  if (G == 0) return ag_fill_outputs({{status, 0, 4}}, st);      // no launch: status = 0
+  const ag_link_work w(work);
+  const dim3 rows((unsigned)((G + 3) / 4));
+  k_link_head<<<dim3(1), dim3(1024), 0, st>>>(dist, G, anchor, w, left, right, height, size, order, status);
+  AG_CHECK_LAUNCH();
+  k_link_rows<<<rows, dim3(256), 0, st>>>(dist, G, method, w);
+  AG_CHECK_LAUNCH();
+  for (int it = 0; it < G - 1; ++it) {              // every launch returns at once past the M - 1 merges there are
+    k_link_choose<<<dim3(1), dim3(1024), 0, st>>>(w, G, left, right, height, size);
+    AG_CHECK_LAUNCH();
+    k_link_update<<<rows, dim3(256), 0, st>>>(w, G, method, it);
+    AG_CHECK_LAUNCH();
+  }
+  k_link_order<<<dim3(1), dim3(1024), 0, st>>>(w, G, order);
+  AG_CHECK_LAUNCH();
+  return AGDIFF_OK;
+}
+
+extern "C" int agdiff_linkage_cut(const float* dist, int32_t G, const int32_t* left, const int32_t* right, const double* height,
+                                  const int32_t* order, int32_t count, float stop_height, int32_t* medoids, int32_t* labels,
+                                  float* near, int32_t* size, double* within, double* cost, int32_t* n_clusters, int32_t* status,
+                                  uint64_t* work, void* stream) {
+  if (!dist || !left || !right || !height || !order || !medoids || !labels || !near || !size || !within || !cost || !n_clusters ||
+      !status || !work || G < 0)
+    return AGDIFF_ERR_ARG;
+  const bool unbounded = stop_height > 0.0f && stop_height - stop_height != 0.0f;      // +inf
+  if (count < 1 || !(unbounded || (stop_height >= 0.0f && stop_height <= (float)AGDIFF_KMEDOIDS_MAX_DIST))) return AGDIFF_ERR_ARG;
+  if ((uintptr_t)work & 7) return AGDIFF_ERR_ARG;
+  if (G > AGDIFF_PRUNE_MAX_CONFS) return AGDIFF_ERR_LIMIT;
+  hipStream_t st = (hipStream_t)stream;
+  if (G == 0) return ag_fill_outputs({{n_clusters, 0, 4}, {status, 0, 4}, {cost, 0, 8}}, st);      // no launch
+  // Q(T) * 2^-28: the product is exact in fp64 and nearbyint rounds it half to even, as the kernels' Q does
+  const double bound = unbounded ? (double)stop_height : __builtin_nearbyint((double)stop_height * 268435456.0) * (1.0 / 268435456.0);
+  int32_t* ctl = (int32_t*)work;
+  uint64_t* keys = work + KM_CTL_WORDS * 4 / 8;
+  k_link_cut<<<dim3(1), dim3(1024), 0, st>>>(G, left, right, height, order, count, bound, medoids, labels, near, size, within, cost,
+                                             n_clusters, status, ctl);
+  AG_CHECK_LAUNCH();
+  k_kmed_costs<<<dim3((unsigned)((G + 3) / 4)), dim3(256), 0, st>>>(dist, G, labels, keys, ctl);
+  AG_CHECK_LAUNCH();
+  k_link_medoids<<<dim3(1), dim3(1024), 0, st>>>(dist, G, labels, keys, medoids, near, ctl);
+  AG_CHECK_LAUNCH();
+  k_kmed_finish<<<dim3(1), dim3(1024), 0, st>>>(G, G, labels, near, size, within, cost, n_clusters, status, ctl);
   AG_CHECK_LAUNCH();
   return AGDIFF_OK;
 }

@@ -48,6 +48,11 @@ extern "C" {
 #define AGDIFF_SILHOUETTE_WORK_BYTES 65536 /* the scratch agdiff_silhouette is handed: control words and one 64-bit integer per conformer */
 #define AGDIFF_PAM_MAX_SWAPS 256 /* most swaps one agdiff_pam_swap call may be asked for: it enqueues three launches for each */
 #define AGDIFF_PAM_WORK_BYTES 135168 /* the scratch agdiff_pam_build / agdiff_pam_swap are handed: control words, three 64-bit and two 32-bit words per conformer */
+#define AGDIFF_LINKAGE_SINGLE 0 /* agdiff_linkage: the pair weight of two clusters is the minimum over their pairs */
+#define AGDIFF_LINKAGE_COMPLETE 1 /* ... the maximum */
+#define AGDIFF_LINKAGE_AVERAGE 2 /* ... the sum, and the key its mean (UPGMA) */
+#define AGDIFF_LINKAGE_WORK_FIXED_BYTES 131072 /* agdiff_linkage's scratch is 8 G G bytes + this: control words and 28 bytes per slot, then the uint64 square */
+#define AGDIFF_LINKAGE_CUT_WORK_BYTES 65536 /* the scratch agdiff_linkage_cut is handed: control words and one 64-bit key per conformer */
 #define AGDIFF_TFD_MAX_COLUMNS 512/* most dihedral columns per conformer in agdiff_tfd_matrix: 32 rows of them are 64 KB of LDS */
 #define AGDIFF_RING_MAX_ATOMS 32 /* most atoms of one ring of agdiff_ring_coords (the fewest: 4) */
 #define AGDIFF_CLASH_SLICE 256 /* atoms per workgroup of agdiff_clash_scan, and per LDS tile of the atoms it walks (4 KB) */
@@ -1041,6 +1046,76 @@ int agdiff_silhouette(const float* dist, int32_t G, int32_t K, const int32_t* la
                       double* a, double* b, double* s, int32_t* other,
                       int32_t* size, double* cluster_mean, double* mean, int32_t* status,
                       uint64_t* work, void* stream);
+
+/* The conformer family tree: agglomerative (hierarchical) linkage clustering over the same FLOAT matrix, dist [G][G] fp32,
+ * contiguous -- one tree per molecule, and any cut of it is a clustering, so no threshold and no count is needed before it runs.
+ * valid(x), Q(x) and the cap are agdiff_kmedoids'.  ONLY THE STRICT UPPER TRIANGLE IS READ: the pair {i, j} with i < j takes
+ * Q(dist[i][j]); the diagonal and the lower triangle are never read.
+ *   - eligibility is agdiff_pam_build's, with an explicit `anchor`: conformer j is eligible iff j == anchor or
+ *     valid(dist[anchor][j]), read along row `anchor` (the one place where an entry at or below the diagonal is read).  M is the
+ *     number of eligible conformers.  Among eligible conformers an entry that is not valid counts as 2^40.  An ineligible
+ *     conformer takes no part.
+ *   - clusters: every eligible conformer starts as a cluster.  A cluster is named by its lowest member index, its SLOT.
+ *   - the pair weight W(A, B), a uint64: method AGDIFF_LINKAGE_SINGLE the minimum of Q over the pairs between A and B,
+ *     AGDIFF_LINKAGE_COMPLETE the maximum, AGDIFF_LINKAGE_AVERAGE (UPGMA) the SUM, at most 2^22 pairs x 2^40 = 2^62.
+ *   - the key of a pair of clusters, an fp64 in units of 2^-28: (double)W for single and complete, which is exact; for average
+ *     (double)W / (double)(|A| |B|): W converted round-to-nearest-even (exact below 2^53), the count converted exactly, then ONE
+ *     correctly rounded division, as agdiff_silhouette makes its means.
+ *   - a merge: among all pairs of live clusters with slots a < b the smallest key is taken, TIES TO THE LOWEST a, THEN TO THE
+ *     LOWEST b.  The union takes slot a and b dies.  For every other live cluster c, W(a, c) becomes the min, the max or the sum
+ *     of W(a, c) and W(b, c): integer arithmetic only.  Merge t records left[t] = a, right[t] = b, height[t] = key * 2^-28 (an
+ *     exact scaling) and size[t] = |A| + |B|.  There are M - 1 merges; the entries t >= M - 1 are -1, -1, NaN and 0.
+ *   - the leaf order: a merge puts b's leaves after a's.  order[j] is conformer j's position, 0 .. M - 1, in the resulting
+ *     left-to-right order; -1 for an ineligible conformer.  (A cluster's list always starts at its slot, so a merge is
+ *     next[tail[a]] = b; tail[a] = tail[b].)
+ *   - HEIGHTS ARE NOT PROMISED MONOTONE.  In exact arithmetic all three linkages are monotone; with the one rounding of `average`
+ *     above 2^53 an inversion of one ulp cannot be excluded, so nothing here is defined through monotonicity.  It is guaranteed
+ *     whenever every sum stays below 2^53: always for single and complete, and for average e.g. when every entry is <= 1 (2^28)
+ *     or the largest product |A| |B| times the largest entry stays below 2^25.
+ * agdiff_linkage outputs, every entry written in every case: left [G], right [G], height [G] (fp64), size [G], order [G],
+ * status [1]: 0, or 2 for an `anchor` outside [0, G), judged on the device: everything is then filled as on an empty tree (-1,
+ * -1, NaN, 0; order all -1).
+ * work: caller-provided scratch of 8 G G + AGDIFF_LINKAGE_WORK_FIXED_BYTES bytes, 8-byte aligned; its contents are ignored on
+ * entry and unspecified on return.  `dist` needs 4-byte alignment only, and any G, odd ones included.
+ * The working state is a uint64 square of which the upper triangle is used and, per slot, the size, a live flag and (nn_key,
+ * nn_idx): the smallest key of row k over the live j > k, ties to the lowest j.  Launches: the head (one workgroup: the anchor,
+ * eligibility, the fills), the rows (one wave per row: W from Q and every row's nearest neighbour), then G - 1 times two
+ * launches -- choose (one workgroup: the arg-min of (nn_key, k) over the live rows, the merge record, the list splice) and
+ * update (one wave per slot: wave a rewrites and rescans row a, a wave c < a rewrites (c, a) and rescans only when its nearest
+ * neighbour was a or b, a wave c > a rescans only when it was b; no wave reads what another writes in the same launch) -- and
+ * one that ranks the list into `order`.  Every launch of the loop reads a device-side merge counter first and returns at once
+ * past M - 1.  No cooperative launch, no workgroup waits on another, no atomics on global memory; every loop is counted;
+ * deterministic bit for bit.
+ *
+ * agdiff_linkage_cut turns the tree into a clustering.  It reads the tree (left, right, height, order as agdiff_linkage wrote
+ * them; order[j] >= 0 says who is eligible), not the working matrix, and takes `count` K >= 1 and `stop_height` T, +inf or
+ * valid(T).  The merges are applied in order, t = 0, 1, ..., while more than K clusters remain AND height[t] <=
+ * Q(T) * 2^-28 (no bound for +inf); the first merge that fails either test ends it, whatever comes later.  count = 1 with
+ * T = +inf is the whole tree; count >= M applies nothing.
+ *   - the clusters are ranked by ascending slot; labels [G] is the rank, -1 for an ineligible conformer: agdiff_silhouette's
+ *     input as it stands; n_clusters [1];
+ *   - medoids [G]: medoids[c] is the member with the smallest sum of Q(dist[i][j]) over the members j != i along row i, ties to
+ *     the lowest index: agdiff_kmedoids' update without an incumbent (its member-cost pass and per-cluster arg-min);
+ *   - near [G], size [G], within [G], cost [1] as agdiff_kmedoids defines them, relative to `medoids`;
+ *   - the arrays indexed by rank are [G] long and filled up to n_clusters; the rest is -1 (medoids), 0 (size) or 0.0 (within);
+ *   - status [1]: 0, or 2 for an applied merge that is not one (not 0 <= left < right < G between eligible conformers): the
+ *     fill is then agdiff_kmedoids' and n_clusters = 0.
+ * work: caller-provided scratch of AGDIFF_LINKAGE_CUT_WORK_BYTES, 8-byte aligned.  Four launches: the cut (one workgroup:
+ * parent[b] = a of the applied merges in LDS, one thread per conformer chasing parents to the root -- a parent has a lower index,
+ * so the loop is counted by G --, a prefix sum over the root flags for the ranks), the member costs, the per-cluster arg-min
+ * with near, and agdiff_kmedoids' sums.
+ * Both: a null pointer, G < 0, a method outside 0 .. 2, count < 1, a T that is NaN, negative or finite above the cap, or a
+ * `work` that is not 8-byte aligned: AGDIFF_ERR_ARG; G > AGDIFF_PRUNE_MAX_CONFS: AGDIFF_ERR_LIMIT (the argument errors come
+ * first); G == 0: no launch, status = 0 (and n_clusters = 0, cost = 0).
+ * Not built: Ward, centroid and median linkage (the matrix is not Euclidean), optimal leaf ordering.  Agreement with
+ * scipy.cluster.hierarchy.linkage is by the definition and on tie-free input only: its tie order is its own. */
+int agdiff_linkage(const float* dist, int32_t G, int32_t method, int32_t anchor,
+                   int32_t* left, int32_t* right, double* height, int32_t* size, int32_t* order, int32_t* status,
+                   uint64_t* work, void* stream);
+int agdiff_linkage_cut(const float* dist, int32_t G, const int32_t* left, const int32_t* right, const double* height,
+                       const int32_t* order, int32_t count, float stop_height,
+                       int32_t* medoids, int32_t* labels, float* near, int32_t* size, double* within,
+                       double* cost, int32_t* n_clusters, int32_t* status, uint64_t* work, void* stream);
 
 /* Rigid superposition (rdkit AlignMolConformers: atoms keep their labels, identity mapping): for each conformer the proper
  * rotation R and translation that minimise the RMSD to `target` over the atoms `atom_idx` (Horn's quaternion, fp64), applied
